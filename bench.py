@@ -10,6 +10,11 @@ head '512', num_classes 1000, bs=256 per GPU, synthetic 3x224x224 fp32 batches r
 CrossEntropyLoss, Adam(lr=1e-3), model.train(); one step = forward + backward + gradient all-reduce (N>1) +
 optimizer.  Weak scaling: global batch = 256*N.  Prints ONE JSON line on rank 0.
 
+Timing: W warm-up steps and a fixed number of untimed calibration steps, then exactly K timed steps between barrier +
+synchronize; `ms_per_step` in the JSON line is that window's time / K.  --min-seconds S repeats the K-step window until S
+seconds of timed work exist and reports the median window.  --dump-outputs DIR writes what the last timed step returned to its
+caller (loss, logits, gradients, updated parameters, BatchNorm buffers) as DIR/<name>.npy.
+
 Extra objects in the JSON line:
   roofline     -- for the kernel class that takes the most time in the step: algorithmic bytes it must move
                   (its input and output tensors once, bf16 NHWC) / its launch time measured with
@@ -31,6 +36,44 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
 MFMA_PEAK_TFLOPS = 2500.0    # dense bf16 MFMA peak (no sparsity), MI355X_MICROARCH.md
+
+# --dump-outputs: what one Trainer.step hands back to its caller, in the order written
+DUMPED_OUTPUTS = (("loss", "the loss Trainer.step returns"),
+                  ("logits", "the logits the loss was taken of, [batch, classes]"),
+                  ("grads", "the flat gradient buffer of the step (all-reduced over ranks)"),
+                  ("params", "the flat parameter buffer after the optimizer update"),
+                  ("bn_buffers", "every floating-point buffer of the model (BatchNorm running statistics), concatenated"))
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, trainer, model, loss):
+    """Writes DUMPED_OUTPUTS as <path>/<name>.npy, float32.  If together they exceed DUMP_LIMIT_BYTES, the budget is shared out
+    smallest array first and an array larger than its share is replaced by a fixed sample of its flattened elements (seeded
+    indices, ascending: the same elements every run).  Returns {name: {"shape": full shape, "sampled": elements kept or None}}."""
+    import numpy as np
+    if trainer.flat_p.is_cuda:
+        torch.cuda.synchronize()
+    bufs = [b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+    src = {"loss": loss.detach().float().reshape(1),
+           "logits": trainer.last_logits,
+           "grads": trainer.flat_g,
+           "params": trainer.flat_p,
+           "bn_buffers": torch.cat(bufs) if bufs else None}
+    arrays = {n: src[n].detach().float().cpu().numpy() for n, _ in DUMPED_OUTPUTS if src[n] is not None}
+    os.makedirs(path, exist_ok=True)
+    info, budget = {}, DUMP_LIMIT_BYTES - 4096 * len(arrays)          # room for the .npy headers
+    for i, name in enumerate(sorted(arrays, key=lambda n: arrays[n].size)):
+        a = arrays[name]
+        share = budget // (len(arrays) - i)
+        keep = None
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.default_rng(20240).choice(a.size, keep, replace=False))
+            a = np.ascontiguousarray(a.reshape(-1)[idx])
+        np.save(os.path.join(path, name + ".npy"), a)
+        budget -= a.nbytes
+        info[name] = {"shape": list(arrays[name].shape), "sampled": keep}
+    return info
 
 
 def parse():
@@ -78,11 +121,18 @@ def parse():
                          "(MAX over ranks), the launch lists are replayed as hipGraphs (Engine.use_graphs: 0.6 ms of host time per step at "
                          "+0.5 %% GPU time) for the measurement; 0 disables the guard.  Reported as graph_mode.auto in the JSON line.")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="repeat the K-step timed window until this much timed work exists; "
-                                                                   "the median window is reported")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the K-step timed window until this much timed work exists; "
+                                                                   "the median window is reported.  Default 0: ONE window, i.e. exactly "
+                                                                   "--steps timed steps (with > 0 the step count depends on the timing)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all: %s); the inputs depend on the arguments only, so two builds can be "
+                         "compared output for output" % ", ".join(n for n, _ in DUMPED_OUTPUTS))
     args = ap.parse_args()
     if args.batch is None:
         args.batch = 64 if args.clusters else 256
+    if args.dump_outputs and args.clusters:
+        ap.error("--dump-outputs covers the single-shape step, not --clusters")
     return args
 
 
@@ -725,6 +775,9 @@ def main():
                 eng.use_graphs = False
                 eng.reset_programs()
                 auto_graph["error"] = repr(e)
+        else:                                     # the same number of untimed steps either way: the steps run before the timed
+            for _ in range(2):                    # region must not depend on the host's timing (--dump-outputs compares builds)
+                trainer.step(x, target)
         barrier()
     # ---- roofline calibration (untimed, rank 0): bracket EVERY conv-kernel launch with HIP events for two steps, find the
     # kernel class with the largest time, then bracket only that class inside the timed region (bracketing all ~190
@@ -747,8 +800,9 @@ def main():
         for _ in range(2):                           # launch lists are captured and instantiated -- outside the timed windows
             trainer.step(x, target)
     # ---- timed region: windows of EXACTLY --steps steps, each bracketed by barrier + synchronize on both sides and reduced with
-    # MAX over ranks; windows are repeated until >= --min-seconds of timed work exist (a 20-step window is 0.2 s: too short for
-    # an external GPU-busy sampler to see) and the MEDIAN window is reported
+    # MAX over ranks; by default ONE window (exactly --steps timed steps); with --min-seconds S windows are repeated until >= S
+    # seconds of timed work exist (a 20-step window is 0.2 s: too short for an external GPU-busy sampler to see) and the MEDIAN
+    # window is reported
     windows, host_dts = [], []
     while True:
         barrier()
@@ -769,6 +823,7 @@ def main():
         host_dts.append(host_dt)
         if sum(windows) >= args.min_seconds or len(windows) >= 200:     # same decision on every rank (dt is the all-reduced MAX)
             break
+    dumped = dump_outputs(args.dump_outputs, trainer, model, loss) if (args.dump_outputs and rank == 0) else None
     if probe is not None:
         box["after"] = probe.measure()
         pr = torch.cuda.get_device_properties(dev)
@@ -875,6 +930,8 @@ def main():
                                                  "gives a pure replay measurement)" % args.steps if profile else "")}
     if box is not None:
         res["box"] = box
+    if dumped is not None:
+        res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if args.h2d and world == 1:
         res["pcie_inclusive"] = h2d_mode(trainer, model, x, target, args.steps, dev)
     if world == 1 and not args.no_cpu_baseline:

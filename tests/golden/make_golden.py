@@ -132,23 +132,31 @@ def gen_sepconvs():
     np.savez_compressed(os.path.join(HERE, "sepconvs.npz"), **out)
 
 
-def gen_nets():
+def gen_nets(dtype=torch.float32, fname="nets.npz"):
+    """dtype float64 (nets_f64.npz): the training cases computed in double precision, where the CPU's summation order (MKL /
+    oneDNN pick different kernels on different processors) stays far below the tests' tolerances through 57 tiny-batch
+    BatchNorm layers.  Their outputs and full gradients are STORED rounded to float32 (at most 6e-8 of each element, the same
+    on every processor, far under the 1e-5 / 1e-4 tolerances; keeps the file small); the summaries stay float64."""
     out = {}
+    wide = dtype == torch.float32
+    store = npy if wide else (lambda t: npy(t).astype(np.float32))
     for name, (ccf, N, H, W, train, pg) in C.NETS.items():
-        m = R.Mnasnet(cut_channels_first=ccf)
+        if not (train or wide):
+            continue
+        m = R.Mnasnet(cut_channels_first=ccf).to(dtype)
         m.load_state_dict(O.init_state(ccf, C.STATE_SEED, proj_gamma=pg))
         m.train(train)
-        x = C.det_input((N, 3, H, W))
+        x = C.det_input((N, 3, H, W)).to(dtype)
         if train:
             y = m(x)
-            (y * C.cotangent(tuple(y.shape))).sum().backward()
-            out[name + "/y"] = npy(y)
+            (y * C.cotangent(tuple(y.shape)).to(dtype)).sum().backward()
+            out[name + "/y"] = store(y)
             for kk, p in m.named_parameters():
                 out[name + "/gsum/" + kk] = np.array(C.summarize(p.grad))
             # full gradients for a handful of small tensors (first/last stage, one shared block)
             for kk, p in m.named_parameters():
                 if kk.startswith("features.0.") or kk.startswith("features.1.") or ".bn." in kk and kk.startswith("features.2."):
-                    out[name + "/g/" + kk] = npy(p.grad)
+                    out[name + "/g/" + kk] = store(p.grad)
             for kk, v in m.state_dict().items():
                 if "running" in kk:
                     out[name + "/ssum/" + kk] = np.array(C.summarize(v))
@@ -159,7 +167,25 @@ def gen_nets():
                 y = m(x)
             out[name + "/y"] = npy(y)
             out[name + "/ysum"] = np.array(C.summarize(y))
-    np.savez_compressed(os.path.join(HERE, "nets.npz"), **out)
+    np.savez_compressed(os.path.join(HERE, fname), **(out if wide else pack_per_case(out)))
+
+
+def pack_per_case(out):
+    """<case>/gsum/<param>, <case>/ssum/<buffer> and <case>/<...num_batches_tracked> entries -> ONE array per case and kind
+    (<case>/gsum [n, 3], <case>/ssum [n, 3], <case>/tracked [n]) plus its key list (<case>/<kind>_keys): one archive member per
+    case instead of one per tensor."""
+    packed, groups = {}, {}
+    for k, v in out.items():
+        case, rest = k.split("/", 1)
+        kind = rest.split("/", 1)[0] if rest.startswith(("gsum/", "ssum/")) else ("tracked" if "tracked" in rest else None)
+        if kind is None:
+            packed[k] = v
+        else:
+            groups.setdefault((case, kind), []).append((rest.split("/", 1)[1] if kind != "tracked" else rest, v))
+    for (case, kind), items in groups.items():
+        packed[case + "/" + kind + "_keys"] = np.array([k for k, _ in items])
+        packed[case + "/" + kind] = np.stack([np.asarray(v) for _, v in items])
+    return packed
 
 
 def gen_keys():
@@ -171,13 +197,15 @@ def gen_keys():
                 f.write("%s %s %s\n" % (k, "x".join(map(str, v.shape)) or "scalar", str(v.dtype).replace("torch.", "")))
 
 
-def gen_heads():
+def gen_heads(dtype=torch.float32, fname="heads.npz"):
     """FineTuneModelPool over load_model('mnasnet') (classifiers.py:7-17,19-111): eval forward for the four
     head configs, and two Adam train steps (train.py:423-440) with the Dropout probabilities forced to 0 at
-    run time (dropout draws torch RNG; the step arithmetic is what is pinned)."""
+    run time (dropout draws torch RNG; the step arithmetic is what is pinned).  dtype float64 (heads_f64.npz): the train
+    steps only, in double precision -- in fp32 the gradient of a conv bias that feeds BatchNorm is rounding noise of the
+    size of Adam's eps, and the step it gets depends on the processor the arithmetic ran on."""
     out = {}
     num_classes = 10
-    for cfg in C.HEADS:
+    for cfg in (C.HEADS if dtype == torch.float32 else ()):
         base = RC.load_model("mnasnet")
         model = RC.FineTuneModelPool(base, "mnasnet", num_classes, cfg)
         fsd = {"features." + k[len("features."):]: v for k, v in O.init_state(False, C.STATE_SEED).items()}
@@ -192,6 +220,7 @@ def gen_heads():
     model = RC.FineTuneModelPool(base, "mnasnet", num_classes, "512")
     fsd = {k: v for k, v in O.init_state(False, C.STATE_SEED).items()}
     model.load_state_dict({**fsd, **O.init_head_state("512", num_classes, C.STATE_SEED)})
+    model.to(dtype)
     for mod in model.modules():
         if isinstance(mod, torch.nn.Dropout):
             mod.p = 0.0
@@ -202,7 +231,7 @@ def gen_heads():
     target = torch.tensor([1, 3, 5, 7])
     losses = []
     for _ in range(2):
-        out_ = model(x.float())
+        out_ = model(x.to(dtype))
         loss = crit(out_, target)
         opt.zero_grad()
         loss.backward()
@@ -211,7 +240,7 @@ def gen_heads():
     out["step/losses"] = np.array(losses)
     for kk, p in model.named_parameters():
         out["step/psum/" + kk] = np.array(C.summarize(p))
-    np.savez_compressed(os.path.join(HERE, "heads.npz"), **out)
+    np.savez_compressed(os.path.join(HERE, fname), **out)
 
 
 if __name__ == "__main__":
@@ -222,6 +251,8 @@ if __name__ == "__main__":
     gen_sepconvs()
     gen_nets()
     gen_heads()
+    gen_nets(torch.float64, "nets_f64.npz")
+    gen_heads(torch.float64, "heads_f64.npz")
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz") or f.endswith(".txt"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -68,3 +68,51 @@ def test_gpu_maybe_initialised_guard(monkeypatch):
     monkeypatch.delenv("LD_PRELOAD")
     monkeypatch.setenv("ROCPROF_OUTPUT_PATH", "/tmp/x")
     assert b.gpu_maybe_initialised()
+
+
+def test_dump_outputs_names_dtype_and_cap(tmp_path, monkeypatch):
+    """--dump-outputs: every output of a step as float32 <name>.npy (bf16 logits widened, BatchNorm buffers concatenated,
+    integer buffers left out); above the byte cap the large arrays become a fixed sample of their elements, the same every run."""
+    import types
+
+    import numpy as np
+    import torch
+    b = _bench()
+    model = torch.nn.Sequential(torch.nn.BatchNorm2d(3), torch.nn.BatchNorm2d(2))
+    g = torch.Generator().manual_seed(3)
+    tr = types.SimpleNamespace(last_logits=torch.randn(4, 10, generator=g).to(torch.bfloat16),
+                               flat_g=torch.randn(5000, generator=g), flat_p=torch.randn(5000, generator=g))
+    loss = torch.tensor(2.5)
+    info = b.dump_outputs(str(tmp_path / "full"), tr, model, loss)
+    names = [n for n, _ in b.DUMPED_OUTPUTS]
+    assert sorted(info) == sorted(names) and all(v["sampled"] is None for v in info.values())
+    got = {n: np.load(tmp_path / "full" / (n + ".npy")) for n in names}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"].tolist() == [2.5] and got["logits"].shape == (4, 10)
+    assert np.array_equal(got["logits"], tr.last_logits.float().numpy())
+    assert np.array_equal(got["grads"], tr.flat_g.numpy()) and np.array_equal(got["params"], tr.flat_p.numpy())
+    assert got["bn_buffers"].size == 2 * (3 + 2)                  # running_mean + running_var, num_batches_tracked is not float
+
+    limit = 4096 * len(names) + 8000
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", limit)
+    dirs = [tmp_path / "cap0", tmp_path / "cap1"]
+    infos = [b.dump_outputs(str(d), tr, model, loss) for d in dirs]
+    assert infos[0] == infos[1] and infos[0]["params"]["sampled"] and infos[0]["grads"]["sampled"]
+    assert infos[0]["params"]["shape"] == [5000] and infos[0]["loss"]["sampled"] is None
+    for d in dirs:
+        assert sum(os.path.getsize(d / (n + ".npy")) for n in names) <= limit
+    p0, p1 = (np.load(d / "params.npy") for d in dirs)
+    assert np.array_equal(p0, p1) and np.isin(p0, tr.flat_p.numpy()).all()
+
+
+def test_steps_default_is_one_window():
+    """--steps K is the number of timed steps: without --min-seconds the timed region is one K-step window."""
+    import sys
+    b = _bench()
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "1"]
+        a = b.parse()
+    finally:
+        sys.argv = argv
+    assert a.steps == 7 and a.min_seconds == 0 and a.dump_outputs == ""

@@ -26,6 +26,9 @@ from world2_worker import rank_batch
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
+# The GPU test machines are shared: at most 6 processes may have the GPU open at once, and this pytest process is one of them.
+GPU_PROCESS_LIMIT = 6
+WIDE_WORLD = 4              # the widest one-device world the suite starts: 4 ranks + this process
 
 
 def _free_port():
@@ -35,6 +38,7 @@ def _free_port():
 
 
 def _run_world2(tmp_path, side, opt="adam", mixed=False, world=2):
+    assert world + 1 <= GPU_PROCESS_LIMIT, "world %d on one device would exceed %d GPU processes" % (world, GPU_PROCESS_LIMIT)
     port = _free_port()
     outs = [str(tmp_path / ("rank%d_side%d.pt" % (r, side))) for r in range(world)]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -199,6 +203,32 @@ def test_bench_host_bound_guard_switches_to_graphs():
     assert d["n_gpus"] == 2 and d["host_bound_guard"]["switched"] is True and d["graph_mode"]["auto"] is True and d["value"] > 0
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """bench.py --dump-outputs DIR: ONE timed window of exactly --steps steps, and what its last step returned to the caller -- loss,
+    logits, gradients, updated parameters, BatchNorm buffers -- as float32 .npy, at most 64 MB; the inputs depend on the
+    arguments only, so two runs with the same arguments write the same arrays bit for bit."""
+    import numpy as np
+    root = os.path.dirname(HERE)
+    base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "32", "--size", "64",
+            "--no-box", "--no-cpu-baseline", "--auto-graphs", "0"]
+    names = ("loss", "logits", "grads", "params", "bn_buffers")
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        d = _bench_line(base + ["--dump-outputs", str(out)])
+        assert d["steps"] == 4 and d["windows"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["dump_outputs"]["dir"] == str(out) and sorted(d["dump_outputs"]["arrays"]) == sorted(names)
+        assert sum(os.path.getsize(out / (n + ".npy")) for n in names) <= 64 << 20
+        runs.append({n: np.load(out / (n + ".npy")) for n in names})
+    a, b = runs
+    assert a["loss"].shape == (1,) and a["logits"].shape == (32, 1000) and a["grads"].shape == a["params"].shape
+    assert abs(float(a["loss"][0]) - d["config"]["loss"]) < 1e-3
+    for n in names:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all(), n
+        assert np.array_equal(a[n], b[n]), "%s differs between two runs with the same arguments" % n
+    assert np.abs(a["grads"]).max() > 0
+
+
 def test_bench_distributed_path_on_rccl_one_rank():
     """bench.py's N > 1 branches on the REAL backend: `--gpus 1 --force-distributed` initialises the process group on "nccl" (= RCCL)
     with device_id, builds Trainer(distributed=True) (rank-0 broadcast, two gradient buckets all-reduced asynchronously on RCCL's
@@ -211,19 +241,21 @@ def test_bench_distributed_path_on_rccl_one_rank():
     assert d["config"]["parallelism"] == "dp1"
 
 
-# ---- world 8 on one device (round 6): the day an 8-GPU node exists, the first real run must not fail on plumbing -----------------
-def test_real_engine_world8_one_gpu(tmp_path):
-    """Eight real Trainer(distributed=True) ranks on cuda:0 over gloo (ranks 2..7 have never existed before round 6): ranks start
-    from eight different parameter sets, see eight different batches (even ranks 64x96, odd ranks 96x64: two compiled programs),
-    and after 3 Adam steps hold ONE model bit for bit; bucket 0 goes out right after stage 5 on every rank in every step;
-    BatchNorm statistics stay per rank."""
-    res = _run_world2(tmp_path, 0, "adam", mixed=True, world=8)
-    assert all(r["world"] == 8 for r in res)
+# ---- wider worlds on one device: the day a multi-GPU node exists, the first real run must not fail on plumbing ---------------------
+# (WIDE_WORLD ranks, not 8: eight ranks on one device and this process would hold the GPU open nine times over, above the limit)
+def test_real_engine_world4_one_gpu(tmp_path):
+    """WIDE_WORLD real Trainer(distributed=True) ranks on cuda:0 over gloo (ranks >= 2 exist only here): ranks start from
+    different parameter sets, see different batches (even ranks 64x96, odd ranks 96x64: two compiled programs), and after 3 Adam
+    steps hold ONE model bit for bit; bucket 0 goes out right after stage 5 on every rank in every step; BatchNorm statistics
+    stay per rank."""
+    world = WIDE_WORLD
+    res = _run_world2(tmp_path, 0, "adam", mixed=True, world=world)
+    assert len(res) == world and all(r["world"] == world for r in res)
     for r in res[1:]:
         assert torch.equal(res[0]["flat_p0"], r["flat_p0"]) and torch.equal(res[0]["flat_g1"], r["flat_g1"])
         assert torch.equal(res[0]["flat_p"], r["flat_p"])
     assert torch.isfinite(res[0]["flat_p"]).all() and not torch.equal(res[0]["flat_p"], res[0]["flat_p0"])
-    assert len({r["rm0"].numpy().tobytes() for r in res}) == 8                      # per-rank running statistics
+    assert len({r["rm0"].numpy().tobytes() for r in res}) == world                  # per-rank running statistics
     for r in res:
         assert len(r["logs"]) == 3
         for log in r["logs"]:
@@ -233,31 +265,32 @@ def test_real_engine_world8_one_gpu(tmp_path):
             assert log.count(("launch", 0)) == 1 and log[-1] == ("launch", 1)
 
 
-def test_bench_world8_dry_run_on_one_gpu(tmp_path):
-    """The driver's multi-GPU command line, dry: plain `python3 bench.py --gpus 8 --one-device --batch 32 --steps 5 --warmup 2`
-    (bench.py starts its eight ranks as a CHILD torch.distributed.run on a free port; nothing is exec'ed from a process that
-    has touched the GPU).  ONE JSON line, n_gpus 8, global batch 256; every rank finished with bit-equal parameters and the same
+def test_bench_world4_dry_run_on_one_gpu(tmp_path):
+    """The driver's multi-GPU command line, dry: plain `python3 bench.py --gpus 4 --one-device --batch 32 --steps 5 --warmup 2`
+    (bench.py starts its ranks as a CHILD torch.distributed.run on a free port; nothing is exec'ed from a process that has
+    touched the GPU).  ONE JSON line, n_gpus 4, global batch 128; every rank finished with bit-equal parameters and the same
     bucket order; only rank 0 ran the roofline calibration; per-rank BatchNorm statistics differ."""
     import json
+    world = WIDE_WORLD
     root = os.path.dirname(HERE)
     dump = str(tmp_path / "state")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--one-device", "--batch", "32", "--steps", "5", "--warmup", "2",
-           "--min-seconds", "0", "--dump-state", dump]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--one-device", "--batch", "32", "--steps", "5",
+           "--warmup", "2", "--min-seconds", "0", "--dump-state", dump]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 8 and d["scaling"] == "weak" and d["steps"] == 5 and d["warmup"] == 2
-    assert d["config"]["global_batch"] == 256 and d["config"]["parallelism"] == "dp8" and "cpu_baseline" not in d
+    assert d["n_gpus"] == world and d["scaling"] == "weak" and d["steps"] == 5 and d["warmup"] == 2
+    assert d["config"]["global_batch"] == 32 * world and d["config"]["parallelism"] == "dp%d" % world and "cpu_baseline" not in d
     assert d["value"] > 0 and d["roofline"]["launches_per_step"] >= 1 and any("--one-device" in o for o in d["overrides"])
     assert "copy4_nt_GBps" in d["box"]["before"] and "read_GBps" in d["box"]["after"]
-    st = [json.load(open(os.path.join(dump, "rank%d.json" % k))) for k in range(8)]
-    assert [s["rank"] for s in st] == list(range(8)) and all(s["world"] == 8 for s in st)
-    assert len({s["flat_p_sha256"] for s in st}) == 1                       # one model on all eight ranks, bit for bit
-    assert len({s["running_mean0_sha256"] for s in st}) == 8                # per-rank BatchNorm statistics (different data per rank)
-    assert [s["profiled"] for s in st] == [True] + [False] * 7              # roofline calibration on rank 0 only
+    st = [json.load(open(os.path.join(dump, "rank%d.json" % k))) for k in range(world)]
+    assert [s["rank"] for s in st] == list(range(world)) and all(s["world"] == world for s in st)
+    assert len({s["flat_p_sha256"] for s in st}) == 1                       # one model on every rank, bit for bit
+    assert len({s["running_mean0_sha256"] for s in st}) == world            # per-rank BatchNorm statistics (different data per rank)
+    assert [s["profiled"] for s in st] == [True] + [False] * (world - 1)    # roofline calibration on rank 0 only
     for s in st:
         log = [tuple(e) for e in s["schedule"]]
         assert log.index(("launch", 0)) == log.index(("stage", 5)) + 1 and log[-1] == ("launch", 1)

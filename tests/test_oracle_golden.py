@@ -44,6 +44,12 @@ def prim_state(name, spec, seed=C.STATE_SEED):
     return st
 
 
+def as_f64(st):
+    """float64 copy of a state dict in which the aliases of a shared block still point at ONE tensor (their gradients add up)."""
+    memo = {}
+    return {k: memo.setdefault(id(v), v.double() if v.dtype.is_floating_point else v) for k, v in st.items()}
+
+
 def req_grad(st):
     for k, v in st.items():
         if v.dtype.is_floating_point and "running" not in k:
@@ -188,36 +194,42 @@ def test_stage(name):
 
 @pytest.mark.parametrize("name", sorted(C.NETS))
 def test_net(name):
-    g = load("nets")
+    """Eval cases in fp32 against nets.npz.  Training cases in float64 against the reference run in float64 (nets_f64.npz;
+    outputs and full gradients stored rounded to float32, at most 6e-8 of each element): in fp32, 57 tiny-batch BatchNorm layers
+    amplify the summation-order differences between processors (MKL / oneDNN choose different kernels) past 1e-5."""
     ccf, N, H, W, train, pg = C.NETS[name]
-    st = O.init_state(ccf, C.STATE_SEED, proj_gamma=pg)
-    x = C.det_input((N, 3, H, W))
     if not train:
+        g = load("nets")
+        st = O.init_state(ccf, C.STATE_SEED, proj_gamma=pg)
         with torch.no_grad():
-            y = O.features_forward(x, st, ccf, False)
+            y = O.features_forward(C.det_input((N, 3, H, W)), st, ccf, False)
         close(y, g[name + "/y"])
         close(C.summarize(y), g[name + "/ysum"], 1e-4)
         return
+    g = load("nets_f64")
+    st = as_f64(O.init_state(ccf, C.STATE_SEED, proj_gamma=pg))
+    x = C.det_input((N, 3, H, W)).double()
     req_grad(st)
     y = O.features_forward(x, st, ccf, True)
-    (y * C.cotangent(tuple(y.shape))).sum().backward()
+    (y * C.cotangent(tuple(y.shape)).double()).sum().backward()
     close(y.detach(), g[name + "/y"])
     checked = 0
     for key in g.files:
         if key.startswith(name + "/g/") and not key.endswith("conv.bias"):
             close(st[key[len(name) + 3:]].grad, g[key], 1e-4)
             checked += 1
-        elif key.startswith(name + "/gsum/") and not key.endswith("conv.bias"):
-            got = C.summarize(st[key[len(name) + 6:]].grad)
-            ref = g[key]
-            assert abs(got[2] - ref[2]) <= 1e-4 * max(ref[2], 1e-12)       # L2
-            assert abs(got[1] - ref[1]) <= 1e-4 * max(ref[1], 1e-12)       # L1
-            checked += 1
-        elif key.startswith(name + "/ssum/"):
-            got = C.summarize(st[key[len(name) + 6:]])
-            assert abs(got[1] - g[key][1]) <= 1e-5 * max(g[key][1], 1e-12)
-        elif "tracked" in key and key.startswith(name + "/"):
-            assert int(st[key[len(name) + 1:]]) == int(g[key])
+    for k, ref in zip(g[name + "/gsum_keys"], g[name + "/gsum"]):
+        if k.endswith("conv.bias"):
+            continue
+        got = C.summarize(st[str(k)].grad)
+        assert abs(got[2] - ref[2]) <= 1e-4 * max(ref[2], 1e-12)       # L2
+        assert abs(got[1] - ref[1]) <= 1e-4 * max(ref[1], 1e-12)       # L1
+        checked += 1
+    for k, ref in zip(g[name + "/ssum_keys"], g[name + "/ssum"]):
+        got = C.summarize(st[str(k)])
+        assert abs(got[1] - ref[1]) <= 1e-5 * max(ref[1], 1e-12)
+    for k, ref in zip(g[name + "/tracked_keys"], g[name + "/tracked"]):
+        assert int(st[str(k)]) == int(ref)
     assert checked > 90
 
 
@@ -248,16 +260,18 @@ def test_head_eval(cfg):
 
 
 def test_train_step():
-    """train.py:423-440 with Adam(lr=1e-3) + CrossEntropyLoss, two steps, dropout p=0."""
-    g = load("heads")
-    net = O.OracleNet(ccf=False, head="512", num_classes=10, seed=C.STATE_SEED).train()
+    """train.py:423-440 with Adam(lr=1e-3) + CrossEntropyLoss, two steps, dropout p=0; float64 against the reference run in
+    float64 (heads_f64.npz): in fp32 the gradient of a conv bias that feeds BatchNorm is rounding noise of the size of Adam's
+    eps, so the step it gets depends on the processor."""
+    g = load("heads_f64")
+    net = O.OracleNet(ccf=False, head="512", num_classes=10, seed=C.STATE_SEED).double().train()
     opt = torch.optim.Adam(net.parameters(), lr=1e-3)
-    x = C.det_input((4, 3, 64, 64))
+    x = C.det_input((4, 3, 64, 64)).double()
     target = torch.tensor([1, 3, 5, 7])
     crit = torch.nn.CrossEntropyLoss()
     losses = []
     for _ in range(2):
-        out = net(x.float(), dropout=False)
+        out = net(x, dropout=False)
         loss = crit(out, target)
         opt.zero_grad()
         loss.backward()
