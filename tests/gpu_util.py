@@ -90,3 +90,121 @@ def dy_ref(g, y, b, rounded=True):
     dz = g * ((s * y + t) > 0)
     d = c1 * dz + c2 * y + c3
     return bf16r(d) if rounded else d
+
+
+# ---- guarded output buffers ----------------------------------------------------------------------------------------------
+# A kernel's output view sits inside a larger buffer filled with a NaN bit pattern that no kernel produces (the canonical NaN is
+# 0x7fc0 / 0x7fc00000).  check(): the canaries before and after the view are bit-unchanged (no write outside the tensor) and no
+# element of the view still holds the pattern (every element was written: what "fully overwritten" in include/mnas.h promises).
+_FILL = {2: 0x7FA5, 4: 0x7FA5A5A5}
+_RAW = {2: torch.int16, 4: torch.int32}
+CANARY_BYTES = 4096
+
+
+def guarded(shape, dtype, device="cuda"):
+    esz = torch.empty((), dtype=dtype).element_size()
+    pad = CANARY_BYTES // esz
+    n = 1
+    for s in shape:
+        n *= int(s)
+    raw = torch.full((pad + n + pad,), _FILL[esz], dtype=_RAW[esz], device=device)
+    view = raw[pad:pad + n].view(dtype).view(*shape)
+
+    def check(what="output", written=True):
+        fill = _FILL[esz]
+        assert bool((raw[:pad] == fill).all()), "%s: write before the tensor (leading canary changed)" % what
+        assert bool((raw[pad + n:] == fill).all()), "%s: write past the end of the tensor (trailing canary changed)" % what
+        if written:
+            left = raw[pad:pad + n] == fill
+            if bool(left.any()):
+                idx = int(left.nonzero()[0])
+                raise AssertionError("%s: %d of %d elements never written (first: flat index %d of shape %s)"
+                                     % (what, int(left.sum()), n, idx, tuple(shape)))
+    return view, check
+
+
+def bits_equal(a, b, what="tensor", signed_zero=True):
+    """Bit-for-bit comparison of two tensors of one dtype; signed_zero=False counts +0 and -0 as equal.  The message names the
+    first differing element (index in the tensor's own shape)."""
+    assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape, a.dtype, b.dtype)
+    esz = a.element_size()
+    ra, rb = a.contiguous().view(_RAW[esz]), b.contiguous().view(_RAW[esz])
+    if not signed_zero:
+        sign = -(1 << (8 * esz - 1))
+        ra = torch.where(ra == sign, torch.zeros_like(ra), ra)
+        rb = torch.where(rb == sign, torch.zeros_like(rb), rb)
+    diff = ra != rb
+    if bool(diff.any()):
+        flat = int(diff.reshape(-1).nonzero()[0])
+        idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(flat), a.shape))
+        raise AssertionError("%s: %d of %d elements differ in their bits; first at %s: %r vs %r"
+                             % (what, int(diff.sum()), diff.numel(), idx, float(a[idx]), float(b[idx])))
+
+
+# ---- fp64 references built from slicing, matmul / einsum and elementwise ops only (no convolution call: nothing goes to a
+# vendor convolution library on the device).  NHWC layouts as the kernels use them; `device` is where the fp64 math runs. -------
+def _f64(t, device):
+    return t.to(device=device, dtype=torch.float64)
+
+
+def ref_dy(g, y, coef, device="cpu"):
+    """dy = c1*g*[s*y+t > 0] + c2*y + c3 over the last (channel) dimension; coef: bnbuf rows 0..4 ([>=5][C])"""
+    g, y, cf = _f64(g, device), _f64(y, device), _f64(coef, device)
+    s, t, c1, c2, c3 = cf[0], cf[1], cf[2], cf[3], cf[4]
+    return c1 * g * ((s * y + t) > 0) + c2 * y + c3
+
+
+def ref_dw_fwd(x, w, device="cpu"):
+    """depthwise k x k, stride 1, pad k//2: x (N,H,W,C), w (C,k,k) -> (N,H,W,C)"""
+    x, w = _f64(x, device), _f64(w, device)
+    N, H, W, C_ = x.shape
+    k = w.shape[-1]
+    p = k // 2
+    xp = torch.zeros((N, H + 2 * p, W + 2 * p, C_), dtype=torch.float64, device=device)
+    xp[:, p:p + H, p:p + W] = x
+    y = torch.zeros_like(x)
+    for kh in range(k):
+        for kw in range(k):
+            y += xp[:, kh:kh + H, kw:kw + W] * w[:, kh, kw]
+    return y
+
+
+def ref_dw_dgrad(dy, w, device="cpu"):
+    """input gradient of ref_dw_fwd: dy (N,H,W,C) -> (N,H,W,C)"""
+    dy, w = _f64(dy, device), _f64(w, device)
+    N, H, W, C_ = dy.shape
+    k = w.shape[-1]
+    p = k // 2
+    gp = torch.zeros((N, H + 2 * p, W + 2 * p, C_), dtype=torch.float64, device=device)
+    for kh in range(k):
+        for kw in range(k):
+            gp[:, kh:kh + H, kw:kw + W] += dy * w[:, kh, kw]
+    return gp[:, p:p + H, p:p + W].contiguous()
+
+
+def ref_dw_wgrad(x, dy, k, device="cpu"):
+    """weight gradient of ref_dw_fwd: x, dy (N,H,W,C) -> (C,k,k)"""
+    x, dy = _f64(x, device), _f64(dy, device)
+    N, H, W, C_ = x.shape
+    p = k // 2
+    xp = torch.zeros((N, H + 2 * p, W + 2 * p, C_), dtype=torch.float64, device=device)
+    xp[:, p:p + H, p:p + W] = x
+    dw = torch.zeros((C_, k, k), dtype=torch.float64, device=device)
+    for kh in range(k):
+        for kw in range(k):
+            dw[:, kh, kw] = torch.einsum("nhwc,nhwc->c", xp[:, kh:kh + H, kw:kw + W], dy)
+    return dw
+
+
+def ref_dense_s2_dgrad(dy, w, H, W, device="cpu"):
+    """input gradient of a dense 3x3 stride-2 pad-1 conv: dy (N,Ho,Wo,Co), w (Co,Ci,3,3) -> (N,H,W,Ci).  Forward pixel h reads
+    input row 2*ho + kh - 1, so tap (kh, kw) scatters dy[ho, wo] @ w[:, :, kh, kw] to padded row 2*ho + kh."""
+    dy, w = _f64(dy, device), _f64(w, device)
+    N, Ho, Wo, Co = dy.shape
+    Ci = w.shape[1]
+    Hp, Wp = max(H + 2, 2 * Ho + 1), max(W + 2, 2 * Wo + 1)
+    gp = torch.zeros((N, Hp, Wp, Ci), dtype=torch.float64, device=device)
+    for kh in range(3):
+        for kw in range(3):
+            gp[:, kh:kh + 2 * Ho:2, kw:kw + 2 * Wo:2] += torch.matmul(dy, w[:, :, kh, kw])
+    return gp[:, 1:1 + H, 1:1 + W].contiguous()
