@@ -55,7 +55,7 @@ typedef struct MnasGradIn {
     const float* coef;    /* float[5][C] */
 } MnasGradIn;
 
-int mnas_version(void);                 /* ABI version: 8 (round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
+int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform, additive: no layout or opcode changed; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
                                          * 5 = squeeze-excite on load: MnasConvGemm.gate, MnasPwBwd.seg_px -- and in round 5: 6 = the opt-in
                                          * forms that lost their A/B are gone (MnasPwBwd.dy_out / red4, MnasDwBwd.src_* / g_gate / g_bias,
                                          * mnas_dw_exp_*, mnas_irb_*, mnas_gram*, mnas_se_bn_assemble); their opcode numbers stay retired) */
@@ -541,6 +541,37 @@ int mnas_probe_valu(float* out, int blocks, int iters, void* stream);
 int mnas_probe_copy4(const void* src, void* dst, int64_t bytes, int blocks, void* stream);
 int mnas_probe_read(const void* src, void* sink, int64_t bytes, int blocks, void* stream);
 int mnas_probe_empty(int blocks, int threads, void* stream);      /* a kernel that does nothing: the cost of one launch in a stream */
+
+/* ---- image batch transform (csrc/mnas_imgx.hip; additive within ABI 8, outside the launch lists): the geometric half of the
+ * reference's PIL input pipeline (datasets.py preprocess_img: crop, Resize / RandomResizedCrop with BILINEAR, flips) on the GPU.
+ * Every output image is, byte for byte,
+ *     flips(window(PIL.Image.crop(src, box).resize((rw, rh), Image.BILINEAR)))
+ * with src a decoded HWC uint8 image (C = 1 is replicated to RGB, C = 4 drops alpha), the window Ho x Wo at (win_top, win_left)
+ * of the rh x rw resized box, and the flips applied to the window.  Output: NCHW uint8 (N, 3, Ho, Wo), contiguous -- what the
+ * stem's uint8 input path reads.  Per axis the box may be downscaled at most MNAS_IMGX_MAX_DOWNSCALE times (any upscale). */
+#define MNAS_IMGX_HFLIP 1
+#define MNAS_IMGX_VFLIP 2
+#define MNAS_IMGX_MAX_DOWNSCALE 32
+#define MNAS_IMGX_MAX_DIM 65536        /* source and resized sides */
+#define MNAS_IMGX_MAX_OUT 16384        /* Ho, Wo */
+typedef struct MnasImgXform {          /* 64 bytes */
+    int64_t src_offset;                /* byte offset of the image in `src` */
+    int32_t src_h, src_w, src_c, src_stride;     /* HWC uint8, c in {1, 3, 4}, row stride in bytes */
+    int32_t box_top, box_left, box_h, box_w;     /* crop box, inside the image */
+    int32_t rh, rw;                    /* the box is resized to rh x rw (PIL bilinear) */
+    int32_t win_top, win_left;         /* Ho x Wo window inside the resized box */
+    int32_t flags;                     /* MNAS_IMGX_HFLIP | MNAS_IMGX_VFLIP */
+    int32_t reserved;                  /* 0 */
+} MnasImgXform;
+/* Host-side validation, no launch: every item's box inside its image, its window inside the resized box, its bytes inside
+ * [0, src_bytes), c in {1, 3, 4}, sizes >= 1, downscale within range, unknown flags 0; n in [0, 65535], Ho, Wo in
+ * [1, MNAS_IMGX_MAX_OUT], src_bytes a positive multiple of 16.  0 or MNAS_EINVAL.  items_host: HOST pointer. */
+int mnas_img_xform_check(const MnasImgXform* items_host, int n, int Ho, int Wo, int64_t src_bytes);
+/* items (n descriptors), src (16-byte aligned, src_bytes % 16 == 0) and out (4-byte aligned, n*3*Ho*Wo bytes): device.
+ * Run the host check on the same descriptors first; the kernel re-checks each descriptor it reads, writes nothing for one it
+ * refuses, and clamps every source address into [0, src_bytes). */
+int mnas_img_xform(const MnasImgXform* items, int n, int Ho, int Wo, const void* src, int64_t src_bytes, void* out_u8_nchw,
+                   void* stream);
 
 #ifdef __cplusplus
 }

@@ -89,6 +89,16 @@ class MnasStemWgrad(C.Structure):
                 ("in_affine", c_void_p), ("in_u8", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MnasImgXform(C.Structure):
+    _fields_ = [("src_offset", c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32), ("src_c", C.c_int32),
+                ("src_stride", C.c_int32), ("box_top", C.c_int32), ("box_left", C.c_int32), ("box_h", C.c_int32),
+                ("box_w", C.c_int32), ("rh", C.c_int32), ("rw", C.c_int32), ("win_top", C.c_int32), ("win_left", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+IMGX_HFLIP, IMGX_VFLIP = 1, 2         # MNAS_IMGX_HFLIP / _VFLIP
+
+
 class MnasOp(C.Structure):
     _fields_ = [("opcode", C.c_int32), ("i", C.c_int32 * 15), ("d", C.c_double * 4), ("p", c_void_p * 16)]
 
@@ -192,6 +202,8 @@ SYMBOLS = {
     "mnas_probe_copy4": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "mnas_probe_read": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "mnas_probe_empty": (c_int, [c_int, c_int, c_void_p]),
+    "mnas_img_xform_check": (c_int, [C.POINTER(MnasImgXform), c_int, c_int, c_int, c_int64]),
+    "mnas_img_xform": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None
