@@ -55,7 +55,7 @@ typedef struct MnasGradIn {
     const float* coef;    /* float[5][C] */
 } MnasGradIn;
 
-int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform, additive: no layout or opcode changed; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
+int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, additive: no layout or opcode changed; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
                                          * 5 = squeeze-excite on load: MnasConvGemm.gate, MnasPwBwd.seg_px -- and in round 5: 6 = the opt-in
                                          * forms that lost their A/B are gone (MnasPwBwd.dy_out / red4, MnasDwBwd.src_* / g_gate / g_bias,
                                          * mnas_dw_exp_*, mnas_irb_*, mnas_gram*, mnas_se_bn_assemble); their opcode numbers stay retired) */
@@ -572,6 +572,42 @@ int mnas_img_xform_check(const MnasImgXform* items_host, int n, int Ho, int Wo, 
  * refuses, and clamps every source address into [0, src_bytes). */
 int mnas_img_xform(const MnasImgXform* items, int n, int Ho, int Wo, const void* src, int64_t src_bytes, void* out_u8_nchw,
                    void* stream);
+
+/* ---- photometric image ops (csrc/mnas_imgc.hip; additive within ABI 8, outside the launch lists): the other half of the
+ * reference's input pipeline (preprocessing type 3: torchvision 0.2.x ColorJitter, RandomGrayscale) on uint8 RGB batches, byte
+ * for byte what Pillow computes:
+ *     BRIGHTNESS / CONTRAST / SATURATION f = ImageEnhance.*.enhance(f) = Image.blend(degenerate, img, (float)f)
+ *         degenerate: 0 / the image's grey mean int(sum(L) / (H*W) + 0.5) / the pixel's grey L
+ *     HUE         img.convert('HSV'), H = (H + hue_shift) mod 256, .convert('RGB')   (adjust_hue: hue_shift = int(f*255) mod 256)
+ *     GRAY        (L, L, L), L = convert('L') = (19595 r + 38470 g + 7471 b + 0x8000) >> 16
+ * Each item holds one image's ops, applied in order; a CONTRAST mean is taken over the image as the ops before it left it. */
+#define MNAS_IMGC_BRIGHTNESS 1         /* blend with 0 */
+#define MNAS_IMGC_CONTRAST   2         /* blend with the image's rounded grey mean; at most one per item */
+#define MNAS_IMGC_SATURATION 3         /* blend with the pixel's grey */
+#define MNAS_IMGC_HUE        4         /* RGB -> HSV, H += hue_shift mod 256, HSV -> RGB */
+#define MNAS_IMGC_GRAY       5         /* (L, L, L) */
+#define MNAS_IMGC_MAX_OPS    5
+#define MNAS_IMGC_NCHW 0               /* (n, 3, H, W) uint8 */
+#define MNAS_IMGC_NHWC 1               /* (n, H, W, 3) uint8 */
+typedef struct MnasImgColor {          /* 52 bytes */
+    int32_t nops;                      /* 0..MNAS_IMGC_MAX_OPS, applied in order; 0 = copy (in place: the image is not touched) */
+    int32_t op[MNAS_IMGC_MAX_OPS];     /* MNAS_IMGC_BRIGHTNESS .. MNAS_IMGC_GRAY */
+    float factor[MNAS_IMGC_MAX_OPS];   /* blend alpha of BRIGHTNESS / CONTRAST / SATURATION; finite and >= 0 for every k < nops */
+    int32_t hue_shift;                 /* 0..255, used by HUE */
+    int32_t reserved;                  /* 0 */
+} MnasImgColor;
+/* Host-side validation, no launch: every item's nops in [0, MAX_OPS], ops known, at most one CONTRAST, factors finite and >= 0,
+ * hue_shift in [0, 255], reserved 0; n in [0, 65535], H, W in [1, MNAS_IMGX_MAX_OUT].  0 or MNAS_EINVAL.  items_host: HOST. */
+int mnas_img_color_check(const MnasImgColor* items_host, int n, int H, int W);
+/* Bytes of device workspace mnas_img_color needs when some item has CONTRAST (per-image partial sums); -1 for a bad shape. */
+int64_t mnas_img_color_workspace_bytes(int n, int H, int W);
+/* items (n descriptors), in and out (n*3*H*W bytes each, contiguous, in the given layouts) and workspace: device.  in == out
+ * (in place) only with in_layout == out_layout; otherwise the two must not overlap.  workspace: mnas_img_color_workspace_bytes
+ * bytes, 4-byte aligned, or null when no item has CONTRAST (the mean pass is then skipped).  Two launches when workspace is
+ * given (the per-image grey sums, then the ops), one otherwise.  Run the host check first; the kernels re-check each
+ * descriptor they read and write nothing for one they refuse (a CONTRAST item without a workspace included). */
+int mnas_img_color(const MnasImgColor* items, int n, int H, int W, int in_layout, const void* in, int out_layout, void* out,
+                   void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,9 @@ from . import _lib  # noqa: F401
 from .mnasnet import ConvBlock, MBConv, MBConv_block, Mnasnet, SepConv  # noqa: F401
 from .classifiers import FineTuneModelPool, load_model  # noqa: F401
 from .sampler import ClusterRandomSampler, DistributedClusterSampler  # noqa: F401
-from .transforms import DeviceTransform, ImageBatch, collate_decoded  # noqa: F401
+from .transforms import (DeviceColorJitter, DevicePipeline, DeviceRandomGrayscale, DeviceTransform, ImageBatch,  # noqa: F401
+                         collate_decoded)
 
 __all__ = ["Mnasnet", "ConvBlock", "SepConv", "MBConv_block", "MBConv", "load_model", "FineTuneModelPool",
-           "ClusterRandomSampler", "DistributedClusterSampler", "DeviceTransform", "ImageBatch", "collate_decoded"]
+           "ClusterRandomSampler", "DistributedClusterSampler", "DeviceTransform", "ImageBatch", "collate_decoded",
+           "DevicePipeline", "DeviceColorJitter", "DeviceRandomGrayscale"]

@@ -99,6 +99,16 @@ class MnasImgXform(C.Structure):
 IMGX_HFLIP, IMGX_VFLIP = 1, 2         # MNAS_IMGX_HFLIP / _VFLIP
 
 
+class MnasImgColor(C.Structure):
+    _fields_ = [("nops", C.c_int32), ("op", C.c_int32 * 5), ("factor", C.c_float * 5), ("hue_shift", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+IMGC_BRIGHTNESS, IMGC_CONTRAST, IMGC_SATURATION, IMGC_HUE, IMGC_GRAY = 1, 2, 3, 4, 5     # MNAS_IMGC_*
+IMGC_MAX_OPS = 5
+IMGC_NCHW, IMGC_NHWC = 0, 1
+
+
 class MnasOp(C.Structure):
     _fields_ = [("opcode", C.c_int32), ("i", C.c_int32 * 15), ("d", C.c_double * 4), ("p", c_void_p * 16)]
 
@@ -204,6 +214,9 @@ SYMBOLS = {
     "mnas_probe_empty": (c_int, [c_int, c_int, c_void_p]),
     "mnas_img_xform_check": (c_int, [C.POINTER(MnasImgXform), c_int, c_int, c_int, c_int64]),
     "mnas_img_xform": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "mnas_img_color_check": (c_int, [C.POINTER(MnasImgColor), c_int, c_int, c_int]),
+    "mnas_img_color_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "mnas_img_color": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
