@@ -381,6 +381,55 @@ int mnas_head_dropout_mask(void* out_u8, int64_t n, float p, uint64_t seed, void
 int mnas_head_cross_entropy(const void* logits, const void* target, int N, int C, int64_t ignore_index,
                             void* loss_rows, void* loss, void* dlogits, void* bad_flag, void* stream);
 
+/* ---- device-resident loss / top-k accuracy meters (csrc/mnas_head.hip) ------------------------------------
+ * The lines that follow the step in the reference's loops -- losses.update(loss.item(), input.size(0)) (train.py:447, :575),
+ * accuracy(sm(out), target, topk=(1, 5)) and the two acc meters' update(prec.item(), n) (train.py:465-468, :589-592), with
+ * AverageMeter and accuracy() as defined at train.py:657-700 -- cost three host reads per batch there.  Here one MnasMeters
+ * block in DEVICE memory is moved by the kernels of the step and copied to the host when the caller wants to print.
+ * Every field is 8 bytes wide: the first MNAS_METERS_NUM_I64 are int64, the last MNAS_METERS_NUM_F64 double, so the block
+ * is two tensors for an all-reduce.
+ *
+ * Correctness rule: row n is correct@k iff rank_n < k, where, with t = target[n] and z = logits,
+ *     rank_n = #{j : z[n][j] > z[n][t]} + #{j < t : z[n][j] == z[n][t]}          (ties go to the lower index).
+ * Rows whose target is ignore_index, outside [0, C), or whose target logit is not finite are wrong for every k and still count
+ * in `samples` (the reference divides by the batch size).  k > C is clamped to C.  The counts are integers summed in a fixed
+ * order: exact and identical from run to run.  The rule is evaluated on the LOGITS; the reference evaluates it on
+ * softmax(out) in fp32, which is monotone up to rounding.
+ *
+ * loss_sum += (double)loss * (double)N, one thread, step order, product and sum rounded separately: bit for bit the Python-float
+ * AverageMeter.sum fed with loss.item().  AverageMeter.avg = loss_sum / loss_samples, .val = last_loss; accuracy in percent =
+ * correct[i] * 100 / samples (avg) and last_correct[i] * 100 / last_n (val). */
+#define MNAS_METERS_MAX_K   4
+#define MNAS_METERS_NUM_I64 14
+#define MNAS_METERS_NUM_F64 3
+typedef struct MnasMeters {
+    /* running */
+    int64_t steps;                               /* updates since the block was zeroed */
+    int64_t samples;                             /* sum of N over all updates */
+    int64_t loss_samples;                        /* sum of N over the updates that carried a loss (AverageMeter.count of the loss) */
+    int64_t nonfinite_steps;                     /* updates whose loss was NaN / Inf */
+    int64_t correct[MNAS_METERS_MAX_K];          /* rows correct@ks[i] */
+    /* last update (AverageMeter.val) */
+    int64_t last_n;
+    int64_t last_loss_n;                         /* N of the last update that carried a loss */
+    int64_t last_correct[MNAS_METERS_MAX_K];
+    double  loss_sum;                            /* running: sum of (double)loss_i * N_i */
+    double  last_loss;                           /* loss of the last update that carried one */
+    double  last_loss_sum;                       /* last_loss * last_loss_n (what an all-reduce sums: val over ranks = sum / n) */
+} MnasMeters;
+/* Both calls: stream-ordered, no allocation, no host read of device memory, capturable in a hipGraph.  ks: nk (1..4) values of
+ * k >= 1 in HOST memory, read at call time; correct[i] belongs to ks[i], so one block is always fed with the same ks.
+ * rank_rows: int32 [N] scratch.  Zero the block (hipMemsetAsync) to reset it.
+ *   mnas_head_cross_entropy_metrics : mnas_head_cross_entropy plus the update of *meters with its loss, in the same two launches
+ *                                     (loss, dlogits and bad_flag are bit-identical to it)
+ *   mnas_head_metrics               : logits from anywhere; loss = device fp32 scalar or NULL (then only steps, samples and the
+ *                                     accuracy fields move).  No ignore_index: any target outside [0, C) is a wrong row. */
+int mnas_head_cross_entropy_metrics(const void* logits, const void* target, int N, int C, int64_t ignore_index,
+                                    void* loss_rows, void* loss, void* dlogits, void* bad_flag, const int* ks, int nk,
+                                    void* rank_rows, MnasMeters* meters, void* stream);
+int mnas_head_metrics(const void* logits, const void* target, int N, int C, const int* ks, int nk, const void* loss,
+                      void* rank_rows, MnasMeters* meters, void* stream);
+
 /* ---- squeeze-and-excitation of the SE variant of MBConv_block (BASELINE config 4; build-defined -- the reference has no SE
  * block; csrc/mnas_se.hip, restated in oracle.se_apply).  a = the activated depthwise output (act-on-load of y2), u = the
  * excite logits fp32 [N][C] (mnas_pool_act -> mnas_head_linear_fwd x2 produce them).

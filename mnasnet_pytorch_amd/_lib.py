@@ -133,6 +133,16 @@ class MnasHeadLinear(C.Structure):
                 ("relu_mask", c_void_p)]
 
 
+METERS_MAX_K, METERS_NUM_I64, METERS_NUM_F64 = 4, 14, 3        # MNAS_METERS_*
+
+
+class MnasMeters(C.Structure):
+    """include/mnas.h: 14 int64 then 3 double, every field 8 bytes wide (the block is also viewed as two tensors)"""
+    _fields_ = [("steps", c_int64), ("samples", c_int64), ("loss_samples", c_int64), ("nonfinite_steps", c_int64),
+                ("correct", c_int64 * 4), ("last_n", c_int64), ("last_loss_n", c_int64), ("last_correct", c_int64 * 4),
+                ("loss_sum", c_double), ("last_loss", c_double), ("last_loss_sum", c_double)]
+
+
 SYMBOLS = {
     "mnas_conv_img_parts": (c_int, [c_int] * 11),
     "mnas_stem_parts": (c_int, [c_int, c_int, c_int, c_int, c_int]),
@@ -142,6 +152,10 @@ SYMBOLS = {
     "mnas_head_dropout_mask": (c_int, [c_void_p, c_int64, c_float, C.c_uint64, c_void_p]),
     "mnas_head_cross_entropy": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
+    "mnas_head_cross_entropy_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                C.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
+    "mnas_head_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, C.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
     "mnas_se_scale": (c_int, [C.POINTER(MnasActIn), c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mnas_se_bwd_reduce": (c_int, [c_void_p, C.POINTER(MnasActIn), c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mnas_se_scratch_bytes": (c_int64, [c_int, c_int, c_int]),

@@ -291,9 +291,66 @@ __device__ __forceinline__ float head_wg_reduce(float v, float* red, bool is_max
     return is_max ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+// ---- device-resident meters (train.py:447,465-468,575,589-592: AverageMeter.update(loss.item(), n) and accuracy(out, target,
+// topk=(1, 5)) without the three host reads per step).  METRICS = true adds, to the two loss kernels, the rank of every row's
+// target and the update of one MnasMeters block; METRICS = false is the code as it was (same instructions on the loss path:
+// the extra work hangs off the row's max pass and the tail of the one-workgroup mean stage).
+// rank_n = #{j : z[n,j] > z[n,t]} + #{j < t : z[n,j] == z[n,t]}; row n is correct@k iff rank_n < k (include/mnas.h).
+#define HEAD_RANK_WRONG 0x7fffffff       // target ignored / out of range / its logit not finite: wrong for every k
+
+struct HeadKs { int k[MNAS_METERS_MAX_K]; int nk; };
+
+__device__ __forceinline__ int head_wg_reduce_int(int v, int* red) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// one workgroup of 256: rows correct@k from the per-row ranks (integer sums in a fixed order), then ONE thread moves the block.
+// loss == NULL: only steps / samples / accuracy fields move.
+__device__ __forceinline__ void head_meters_update(const int* rank_rows, int N, HeadKs ks, const float* loss, MnasMeters* m, int* redi) {
+    int c[MNAS_METERS_MAX_K];
+#pragma unroll
+    for (int q = 0; q < MNAS_METERS_MAX_K; ++q) c[q] = 0;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        const int r = rank_rows[i];
+#pragma unroll
+        for (int q = 0; q < MNAS_METERS_MAX_K; ++q) c[q] += (q < ks.nk && r < ks.k[q]) ? 1 : 0;
+    }
+#pragma unroll
+    for (int q = 0; q < MNAS_METERS_MAX_K; ++q) c[q] = head_wg_reduce_int(c[q], redi);
+    if (threadIdx.x != 0) return;
+    m->steps += 1;
+    m->samples += N;
+    m->last_n = N;
+#pragma unroll
+    for (int q = 0; q < MNAS_METERS_MAX_K; ++q) {
+        m->correct[q] += c[q];
+        m->last_correct[q] = c[q];
+    }
+    if (loss) {
+        // AverageMeter.update(loss.item(), n): sum += val * n in Python floats = one rounded double product and one rounded
+        // double sum per step, in step order (no fused multiply-add: it would round once instead of twice)
+        const float l = *loss;
+        const double d = (double)l, dn = __dmul_rn(d, (double)N);
+        m->loss_sum = __dadd_rn(m->loss_sum, dn);
+        m->loss_samples += N;
+        m->last_loss = d;
+        m->last_loss_sum = dn;
+        m->last_loss_n = N;
+        if (!isfinite(l)) m->nonfinite_steps += 1;
+    }
+}
+
+template <bool METRICS>
 __global__ __launch_bounds__(256) void k_head_ce(const float* x, const long long* target, int N, int C, long long ignore_index,
-                                                 float* loss_rows, float* dlogits, int* bad) {
+                                                 float* loss_rows, float* dlogits, int* bad, int* rank_rows) {
     __shared__ float red[4];
+    __shared__ int redi[4];
     const int n = blockIdx.x, tid = threadIdx.x;
     const float* row = x + (size_t)n * C;
     float cnt = 0.f;
@@ -306,7 +363,20 @@ __global__ __launch_bounds__(256) void k_head_ce(const float* x, const long long
     }
     const bool valid = !ignored && t >= 0 && t < C;
     float mx = -INFINITY;
-    for (int c = tid; c < C; c += 256) mx = fmaxf(mx, row[c]);
+    if (METRICS) {
+        const float zt = valid ? row[t] : 0.f;
+        const int ti = (int)t;
+        int above = 0;
+        for (int c = tid; c < C; c += 256) {
+            const float z = row[c];
+            mx = fmaxf(mx, z);
+            above += (z > zt || (z == zt && c < ti)) ? 1 : 0;
+        }
+        above = head_wg_reduce_int(above, redi);
+        if (tid == 0) rank_rows[n] = (valid && isfinite(zt)) ? above : HEAD_RANK_WRONG;
+    } else {
+        for (int c = tid; c < C; c += 256) mx = fmaxf(mx, row[c]);
+    }
     mx = head_wg_reduce(mx, red, true);
     float se = 0.f;
     for (int c = tid; c < C; c += 256) se += expf(row[c] - mx);
@@ -321,25 +391,93 @@ __global__ __launch_bounds__(256) void k_head_ce(const float* x, const long long
 }
 
 // loss = sum(loss_rows) / count, fixed order (thread-strided partials, then a tree)
+template <bool METRICS>
 __global__ __launch_bounds__(256) void k_head_loss_mean(const float* loss_rows, const long long* target, int N, long long ignore_index,
-                                                        float* loss) {
+                                                        float* loss, const int* rank_rows, HeadKs ks, MnasMeters* meters) {
     __shared__ float red[4];
+    __shared__ int redi[4];
     float s = 0.f, cnt = 0.f;
     for (int i = threadIdx.x; i < N; i += 256) { s += loss_rows[i]; cnt += target[i] != ignore_index ? 1.f : 0.f; }
     s = head_wg_reduce(s, red, false);
     cnt = head_wg_reduce(cnt, red, false);
     if (threadIdx.x == 0) *loss = s / cnt;       // 0/0 = nan when every row is ignored, as ATen
+    if (METRICS) head_meters_update(rank_rows, N, ks, loss, meters, redi);   // thread 0 reads back its own store
 }
 
 extern "C" int mnas_head_cross_entropy(const void* logits, const void* target, int N, int C, int64_t ignore_index,
                                        void* loss_rows, void* loss, void* dlogits, void* bad_flag, void* stream) {
     if (!logits || !target || !loss_rows || !loss || !bad_flag || N < 1 || C < 1) return MNAS_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_head_ce, dim3(N), dim3(256), 0, s, (const float*)logits, (const long long*)target, N, C,
-                       (long long)ignore_index, (float*)loss_rows, (float*)dlogits, (int*)bad_flag);
+    hipLaunchKernelGGL(k_head_ce<false>, dim3(N), dim3(256), 0, s, (const float*)logits, (const long long*)target, N, C,
+                       (long long)ignore_index, (float*)loss_rows, (float*)dlogits, (int*)bad_flag, (int*)nullptr);
     MNAS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_head_loss_mean, dim3(1), dim3(256), 0, s, (const float*)loss_rows, (const long long*)target, N,
-                       (long long)ignore_index, (float*)loss);
+    hipLaunchKernelGGL(k_head_loss_mean<false>, dim3(1), dim3(256), 0, s, (const float*)loss_rows, (const long long*)target, N,
+                       (long long)ignore_index, (float*)loss, (const int*)nullptr, HeadKs{}, (MnasMeters*)nullptr);
+    MNAS_CHECK_LAUNCH();
+    return MNAS_OK;
+}
+
+// k of every meter clamped to [1, C] (top-k over C classes with k > C is top-C); k < 1 or more than MNAS_METERS_MAX_K of them: invalid
+static int head_ks(const int* ks, int nk, int C, HeadKs* out) {
+    if (!ks || nk < 1 || nk > MNAS_METERS_MAX_K) return MNAS_EINVAL;
+    *out = HeadKs{};
+    out->nk = nk;
+    for (int i = 0; i < nk; ++i) {
+        if (ks[i] < 1) return MNAS_EINVAL;
+        out->k[i] = ks[i] < C ? ks[i] : C;
+    }
+    return MNAS_OK;
+}
+
+extern "C" int mnas_head_cross_entropy_metrics(const void* logits, const void* target, int N, int C, int64_t ignore_index,
+                                               void* loss_rows, void* loss, void* dlogits, void* bad_flag, const int* ks, int nk,
+                                               void* rank_rows, MnasMeters* meters, void* stream) {
+    if (!logits || !target || !loss_rows || !loss || !bad_flag || !rank_rows || !meters || N < 1 || C < 1) return MNAS_EINVAL;
+    HeadKs k;
+    if (head_ks(ks, nk, C, &k) != MNAS_OK) return MNAS_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_head_ce<true>, dim3(N), dim3(256), 0, s, (const float*)logits, (const long long*)target, N, C,
+                       (long long)ignore_index, (float*)loss_rows, (float*)dlogits, (int*)bad_flag, (int*)rank_rows);
+    MNAS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_head_loss_mean<true>, dim3(1), dim3(256), 0, s, (const float*)loss_rows, (const long long*)target, N,
+                       (long long)ignore_index, (float*)loss, (const int*)rank_rows, k, meters);
+    MNAS_CHECK_LAUNCH();
+    return MNAS_OK;
+}
+
+// ---- the same counts for logits from anywhere (module path, another criterion, no loss at all): one workgroup per row for the
+// ranks, one workgroup for the block.  No ignore_index here: a target outside [0, C) is a wrong row.
+__global__ __launch_bounds__(256) void k_head_rank(const float* x, const long long* target, int C, int* rank_rows) {
+    __shared__ int redi[4];
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const float* row = x + (size_t)n * C;
+    const long long t = target[n];
+    const bool valid = t >= 0 && t < C;
+    const float zt = valid ? row[t] : 0.f;
+    const int ti = (int)t;
+    int above = 0;
+    for (int c = tid; c < C; c += 256) {
+        const float z = row[c];
+        above += (z > zt || (z == zt && c < ti)) ? 1 : 0;
+    }
+    above = head_wg_reduce_int(above, redi);
+    if (tid == 0) rank_rows[n] = (valid && isfinite(zt)) ? above : HEAD_RANK_WRONG;
+}
+
+__global__ __launch_bounds__(256) void k_head_meters(const int* rank_rows, int N, HeadKs ks, const float* loss, MnasMeters* meters) {
+    __shared__ int redi[4];
+    head_meters_update(rank_rows, N, ks, loss, meters, redi);
+}
+
+extern "C" int mnas_head_metrics(const void* logits, const void* target, int N, int C, const int* ks, int nk, const void* loss,
+                                 void* rank_rows, MnasMeters* meters, void* stream) {
+    if (!logits || !target || !rank_rows || !meters || N < 1 || C < 1) return MNAS_EINVAL;
+    HeadKs k;
+    if (head_ks(ks, nk, C, &k) != MNAS_OK) return MNAS_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_head_rank, dim3(N), dim3(256), 0, s, (const float*)logits, (const long long*)target, C, (int*)rank_rows);
+    MNAS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_head_meters, dim3(1), dim3(256), 0, s, (const int*)rank_rows, N, k, (const float*)loss, meters);
     MNAS_CHECK_LAUNCH();
     return MNAS_OK;
 }

@@ -174,8 +174,9 @@ class NativeHead:
             dz = dx
         return dz
 
-    def cross_entropy(self, logits, target, ignore_index=-100, need_grad=True):
-        """-> (loss 0-d tensor, dlogits or None).  nn.CrossEntropyLoss(reduction='mean') semantics."""
+    def cross_entropy(self, logits, target, ignore_index=-100, need_grad=True, meters=None):
+        """-> (loss 0-d tensor, dlogits or None).  nn.CrossEntropyLoss(reduction='mean') semantics.  ``meters`` (a
+        metrics.DeviceMeters): the same two launches also update its loss / top-k accuracy block (train.py:447,465-468)."""
         N, Cn = logits.shape
         if target.dtype != torch.int64 or target.shape != (N,):
             raise ValueError("target must be int64 of shape (N,)")
@@ -188,6 +189,12 @@ class NativeHead:
         rows, bad = self._scratch[key]
         loss = torch.empty((), dtype=torch.float32, device=dev)
         dl = torch.empty_like(logits) if need_grad else None
+        if meters is not None:
+            ks, nk, ranks, blk = meters.kernel_args(N, dev)
+            L.check(self.lib.mnas_head_cross_entropy_metrics(logits.data_ptr(), target.contiguous().data_ptr(), N, Cn, int(ignore_index),
+                                                             rows.data_ptr(), loss.data_ptr(), L.ptr(dl), bad.data_ptr(), ks, nk,
+                                                             ranks, blk, L.cur_stream()), "head_cross_entropy_metrics")
+            return loss, dl
         L.check(self.lib.mnas_head_cross_entropy(logits.data_ptr(), target.contiguous().data_ptr(), N, Cn, int(ignore_index),
                                                  rows.data_ptr(), loss.data_ptr(), L.ptr(dl), bad.data_ptr(), L.cur_stream()),
                 "head_cross_entropy")
@@ -206,12 +213,12 @@ class NativeHead:
     def apply(self, x):
         return _HeadFn.apply(self, x, *self.params())
 
-    def loss_and_grad(self, x, target, ignore_index=-100, need_dx=True):
+    def loss_and_grad(self, x, target, ignore_index=-100, need_dx=True, meters=None):
         """Forward, loss and full backward of the head without autograd.  Parameter gradients are ACCUMULATED into
         ``p.grad`` (which must exist: Trainer points them into its flat gradient buffer).  -> (logits, loss, dx)"""
         seeds = self.next_seeds()
         us, logits = self.forward_layers(x, seeds)
-        loss, dl = self.cross_entropy(logits, target, ignore_index)
+        loss, dl = self.cross_entropy(logits, target, ignore_index, meters=meters)
         grads = []
         for l in self.layers:
             if l.lin.weight.grad is None or (l.lin.bias is not None and l.lin.bias.grad is None):

@@ -229,8 +229,9 @@ class Trainer:
 
     def __init__(self, model: nn.Module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  criterion: Optional[nn.Module] = None, distributed: bool = False, process_group=None,
-                 early_bucket_stage: int = 5, optimizer: str = "adam", **optimizer_kwargs):
+                 early_bucket_stage: int = 5, optimizer: str = "adam", meters=None, **optimizer_kwargs):
         self.model = model
+        self.meters = meters             # metrics.DeviceMeters or None: train.py:447,465-468 on the device (see forward_backward)
         self.native_step = True          # see _native_head()
         self.last_logits = None
         self.criterion = criterion if criterion is not None else nn.CrossEntropyLoss()   # train.py:277
@@ -326,6 +327,19 @@ class Trainer:
     def _native_head(self):
         """The model's NativeHead when the whole step can bypass autograd: FineTuneModelPool-like model in training mode
         (fused pool, Dropout/Linear/ReLU classifier) and a plain mean-reduced nn.CrossEntropyLoss (train.py:277)."""
+        m = self.model
+        head = self._native_eval_head()
+        if head is None or not (m.training and self.engine.root.training):
+            return None
+        if any(not p.requires_grad for p in self.head_params):
+            return None
+        if any(not p.requires_grad for p in self.engine.params):
+            return None            # frozen features (FineTuneModelPool.freeze()): the module path skips their backward
+        return head
+
+    def _native_eval_head(self):
+        """The part of _native_head() that does not concern training: what lets a validation batch run as engine forward (fused
+        pool) -> head -> fused loss."""
         m, c = self.model, self.criterion
         if not self.native_step or type(c) is not nn.CrossEntropyLoss:
             return None
@@ -333,12 +347,8 @@ class Trainer:
             return None
         if not (hasattr(m, "_native_head") and getattr(m, "native_head", False) and getattr(m, "fuse_pool", False)):
             return None
-        if not (m.training and self.engine.root.training and m._pool_is_global_average()):
+        if not m._pool_is_global_average() or self.engine.root is not m.features:
             return None
-        if self.engine.root is not m.features or any(not p.requires_grad for p in self.head_params):
-            return None
-        if any(not p.requires_grad for p in self.engine.params):
-            return None            # frozen features (FineTuneModelPool.freeze()): the module path skips their backward
         return m._native_head()
 
     @property
@@ -387,7 +397,9 @@ class Trainer:
             f = prog.run_forward(x, static_io=True)
             head.calls = self.optimizer.step_count           # dropout masks follow the CHECKPOINTED step count: a resumed run does
                                                              # not replay the masks of the first steps
-            self.last_logits, loss, df = head.loss_and_grad(f.view(f.size(0), -1), target, self.criterion.ignore_index)
+            # with meters: the loss kernels also rank every row's target and move the meters block -- no launch more
+            self.last_logits, loss, df = head.loss_and_grad(f.view(f.size(0), -1), target, self.criterion.ignore_index,
+                                                            meters=self.meters)
             accumulate = eng.prepare_grads()
             prog.run_backward(df, eng.on_stage_done, static_io=True)
             eng.finish_grads(accumulate)
@@ -395,4 +407,61 @@ class Trainer:
             out = self.model(x.float())
             loss = self.criterion(out, target)
             loss.backward()
+            if self.meters is not None and self._class_vector(out, target):
+                self.meters.update(out.detach(), target, loss.detach())
         return loss.detach()
+
+    @staticmethod
+    def _class_vector(out, target):
+        """single-label classification: (N, C) outputs and an int64 class index per row (what the meters count)"""
+        return (isinstance(target, torch.Tensor) and target.dtype == torch.int64 and out.dim() == 2 and target.shape == (out.shape[0],)
+                and target.device == out.device)
+
+    def validate(self, batches, meters=None, transform=None, max_batches=None, reduce=True):
+        """The reference's validate() (train.py:556-592) with its three host reads per batch replaced by ONE at the end.
+
+        ``model.eval()`` and ``torch.no_grad()``; for every ``(input, target)`` of ``batches``: ``transform(input)`` if given (a
+        transforms.DevicePipeline / DeviceTransform over an ImageBatch), the engine's eval-mode forward with the fused pool, the
+        native head without dropout, and the cross-entropy kernels that also move ``meters`` (default: a fresh DeviceMeters with
+        top-1 / top-5).  Any input shape works: the engine keeps one eval program per shape.  A model or criterion the native head
+        does not cover runs as ``model(x)`` / ``criterion`` / ``meters.update``.  Distributed trainers broadcast rank 0's
+        BatchNorm statistics first and sum the meters over the ranks at the end (``reduce=False``: neither).  The modules'
+        train/eval flags are restored on the way out, also when a batch raises.  Returns ``meters.read()``."""
+        from .metrics import DeviceMeters
+        if meters is None:
+            meters = DeviceMeters((1, 5), self.device)
+        model = self.model
+        modes = [(mod, mod.training) for mod in model.modules()]
+        if self.distributed and reduce:
+            self.sync_buffers()
+        try:
+            model.eval()                                                   # train.py:556
+            head = self._native_eval_head()
+            if head is not None and (model.features._forward_hooks or model.features._forward_pre_hooks
+                                     or model.pooling._forward_hooks or model.pooling._forward_pre_hooks):
+                head = None                                                # hooks on features / pooling must fire: model(x)
+            with torch.no_grad():                                          # train.py:560
+                for i, (x, target) in enumerate(batches):
+                    if max_batches is not None and i >= max_batches:
+                        break
+                    if transform is not None:
+                        x = transform(x)
+                    if not isinstance(target, torch.Tensor) or target.device != x.device:
+                        raise RuntimeError("target must be a tensor on the input's device (%s)" % (x.device,))
+                    if head is not None:
+                        model._sync_input_norm()
+                        f = self.engine.forward(x, pooled=True)
+                        _, logits = head.forward_layers(f.view(f.size(0), -1), [0] * len(head.layers))   # eval: the seeds are unused
+                        head.cross_entropy(logits, target, self.criterion.ignore_index, need_grad=False, meters=meters)
+                    else:
+                        out = model(x)                                     # the engine converts (train.py:562 input.float())
+                        loss = self.criterion(out, target)
+                        if not self._class_vector(out, target):
+                            raise ValueError("validate() counts single-label classification only: int64 targets of shape (N,)")
+                        meters.update(out, target, loss)
+        finally:
+            for mod, flag in modes:
+                mod.training = flag
+        if self.distributed and reduce:
+            meters.all_reduce(self.buckets.group)
+        return meters.read()
