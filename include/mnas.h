@@ -111,6 +111,20 @@ int mnas_conv_gemm_parts(int mode, int M, int Ci, int Co, int taps);
  * whole-image kernel (csrc/mnas_dimg.hip: 3x3, pad 1, output plane <= 256 pixels, N >= 32; mode 1: stride 1 and a
  * materialised dy), -1 otherwise.  mode 1 arguments as in MnasConvGemm (Hi,Wi,Ci = dy dims, Ho,Wo,Co = result dims). */
 int mnas_conv_img_parts(int mode, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int k, int stride, int pad);
+/* Which kernel family mnas_conv_gemm runs for a launch (host-side, no launch; additive within ABI 8).  The query and the launch
+ * share one dispatcher function, so the answer is what runs.  Returns MNAS_ROUTE_* or -MNAS_EINVAL for arguments mnas_conv_gemm
+ * refuses before it picks a kernel (refusals of a single k_igemm instance -- LDS size, a gate on a wide tile -- still come from the
+ * launch).  out (or NULL): int[4], for MNAS_ROUTE_IGEMM = {NT (16-cout tiles per workgroup), PT (64-pixel groups per tile), K
+ * elements per LDS chunk (32 / 64 / 128), 1 = parity-class form of the stride-2 3x3 input gradient}, zeros otherwise. */
+#define MNAS_ROUTE_PWX   0   /* csrc/mnas_pwx.hip: widening 1x1 forward, weight-stationary */
+#define MNAS_ROUTE_PWS   1   /* csrc/mnas_pws.hip: long-reduction 1x1, K split over the waves */
+#define MNAS_ROUTE_PWF   2   /* csrc/mnas_pwf.hip: DMA-pipelined 1x1 forward */
+#define MNAS_ROUTE_PWD   3   /* csrc/mnas_pwf.hip: DMA-pipelined 1x1 input gradient over a materialised dy */
+#define MNAS_ROUTE_C3R   4   /* csrc/mnas_c3r.hip: weight-heavy dense 3x3 on the 7x7 planes */
+#define MNAS_ROUTE_DIMG  5   /* csrc/mnas_dimg.hip: dense 3x3, whole image per workgroup */
+#define MNAS_ROUTE_C3X   6   /* csrc/mnas_c3x.hip: stride-2 3x3 forward on the large maps */
+#define MNAS_ROUTE_IGEMM 7   /* csrc/mnas_gemm.hip: k_igemm, every other shape */
+int mnas_conv_gemm_route(const MnasConvGemm* a, int* out);
 
 /* ---- input gradient of the stride-2 dense 3x3 convs as a transposed convolution (csrc/mnas_tconv.hip): one GEMM per 2x2
  * output block over the four dy pixels it depends on; no per-element gather.  dy: bf16 (N,Ho,Wo,Co), MATERIALISED
@@ -260,8 +274,10 @@ typedef struct MnasStemFwd {
     float* stats;            /* float[2][Co][nparts] */
     /* optional fused input pipeline (the normalisation the reference's dataset applies on the CPU: datasets.py:474-516
      * transforms.Normalize with the mean / std of classifiers.py:91-92): the conv reads in_affine[0][c] * x + in_affine[1][c];
-     * in_u8 != 0: x is a uint8 NCHW image (a quarter of the PCIe / HBM bytes).  Band-kernel shapes only (Co == 32,
-     * W % 4 == 0), otherwise MNAS_EINVAL. */
+     * in_u8 != 0: x is a uint8 NCHW image (a quarter of the PCIe / HBM bytes).  The two fields are independent: in_u8 without
+     * in_affine reads the byte values 0..255 themselves.  The staged value is bf16(fmaf(x, scale, shift)), and the zero padding
+     * pads the TRANSFORMED image.  Band-kernel shapes only (Co == 32, W % 4 == 0; the weight gradient also needs Wo % 8 == 0):
+     * on any other shape a launch with in_affine or in_u8 returns MNAS_EINVAL and writes nothing. */
     const float* in_affine;  /* float[2][3] (scale, shift per input plane) or NULL */
     int32_t in_u8, reserved;
 } MnasStemFwd;

@@ -124,6 +124,7 @@ OP_SE_FC_FWD, OP_SE_FC_BWD = 37, 38
 OP_STEM_DGRAD = 39
 PACK_FWD, PACK_DGRAD, PACK_DW, PACK_TCONV = 0, 1, 2, 3
 EINVAL = 10001      # MNAS_EINVAL
+ROUTE_PWX, ROUTE_PWS, ROUTE_PWF, ROUTE_PWD, ROUTE_C3R, ROUTE_DIMG, ROUTE_C3X, ROUTE_IGEMM = range(8)     # MNAS_ROUTE_*
 
 # every symbol include/mnas.h declares: (name, restype, argtypes)
 class MnasHeadLinear(C.Structure):
@@ -175,6 +176,7 @@ SYMBOLS = {
     "mnas_arch": (C.c_char_p, []),
     "mnas_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "mnas_conv_gemm": (c_int, [C.POINTER(MnasConvGemm), c_void_p]),
+    "mnas_conv_gemm_route": (c_int, [C.POINTER(MnasConvGemm), C.POINTER(c_int)]),
     "mnas_conv_gemm_tile_pixels": (c_int, [c_int, c_int, c_int]),
     "mnas_conv_gemm_parts": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "mnas_conv_wgrad": (c_int, [C.POINTER(MnasConvWgrad), c_void_p]),

@@ -207,6 +207,7 @@ int mnas_dw2_bwd(const MnasDwBwd* c, void* stream);
 int mnas_pws_enabled();
 int mnas_pws_parts(int mode, int M, int K, int N);
 int mnas_pws_run(const MnasConvGemm* c, void* stream);
+int mnas_pws_accepts(const MnasConvGemm* c);
 int mnas_pws_gate_ok(int M, int K, int N);
 int mnas_c3x_ok(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int kh, int kw, int stride, int pad);
 int mnas_c3x_run(const MnasConvGemm* c, void* stream);           // csrc/mnas_c3x.hip: stride-2 3x3 forward on the large maps, weight-stationary

@@ -609,10 +609,13 @@ extern "C" int mnas_conv_gemm_gate_ok(int N, int HW, int Ci, int Co) {
     return (nt <= 3 && nblocks == 1 && !(pt == 1 && Ci >= 256) && HW >= 64 * pt) ? 1 : 0;
 }
 
-extern "C" int mnas_conv_gemm(const MnasConvGemm* c, void* stream) {
-    if (!c || (c->mode != 0 && c->mode != 1)) return MNAS_EINVAL;
-    if ((c->Ci & 7) || (c->Co & 7) || c->nparts < 1 || c->nparts > 65535) return MNAS_EINVAL;
-    IgemmArgs a;
+// The dispatcher: argument checks, then the chain of kernel families in priority order.  One function for the launch path
+// (mnas_conv_gemm) and the host-side query (mnas_conv_gemm_route), so the answer of the query is what runs.  Returns a
+// MNAS_ROUTE_* value or -MNAS_EINVAL; fills the k_igemm arguments and, for MNAS_ROUTE_IGEMM, the instance (NT, cout blocks, PT).
+static int conv_gemm_plan(const MnasConvGemm* c, IgemmArgs* ap, int* nt_out, int* nblocks_out, int* pt_out) {
+    if (!c || (c->mode != 0 && c->mode != 1)) return -MNAS_EINVAL;
+    if ((c->Ci & 7) || (c->Co & 7) || c->nparts < 1 || c->nparts > 65535) return -MNAS_EINVAL;
+    IgemmArgs& a = *ap;
     a.M = c->N * c->Ho * c->Wo;
     a.Hi = c->Hi; a.Wi = c->Wi; a.Ci = c->Ci; a.Ho = c->Ho; a.Wo = c->Wo; a.Co = c->Co;
     a.kh = c->kh; a.kw = c->kw; a.stride = c->stride; a.pad = c->pad;
@@ -627,7 +630,7 @@ extern "C" int mnas_conv_gemm(const MnasConvGemm* c, void* stream) {
     a.red_y = (c->mode == 1) ? c->red_y : nullptr; a.red_bn = c->red_bn;
     a.nt = (mnas_nt_mask() & (c->mode == 1 ? MNAS_NT_IGEMM_DGRAD : MNAS_NT_IGEMM_FWD)) ? 1 : 0;
     a.gate = c->gate;
-    if (a.gate && (c->mode != 0 || !a.is_pw || !c->act.scale || c->resid)) return MNAS_EINVAL;
+    if (a.gate && (c->mode != 0 || !a.is_pw || !c->act.scale || c->resid)) return -MNAS_EINVAL;
     {   // the decode divides by the OUTPUT plane (half plane for the parity-class form); exact division beyond 2^24 pixels
         const int s2f = (c->mode == 1 && c->kh == 3 && c->kw == 3 && c->stride == 2 && c->pad == 1 && !(c->Ho & 1) && !(c->Wo & 1));
         const int wd = s2f ? c->Wo / 2 : c->Wo, hwd = s2f ? (c->Ho / 2) * wd : c->Ho * c->Wo;
@@ -640,39 +643,66 @@ extern "C" int mnas_conv_gemm(const MnasConvGemm* c, void* stream) {
     a.s2 = (c->mode == 1 && c->kh == 3 && c->kw == 3 && c->stride == 2 && c->pad == 1 && !(c->Ho & 1) && !(c->Wo & 1)) ? 1 : 0;
     a.Mc = c->N * (c->Ho / 2) * (c->Wo / 2);
     a.tpc = 0;
-    if (a.red_y && (!a.red_bn || !a.stats)) return MNAS_EINVAL;
-    if (a.taps != 1 && c->Ci > 1024) return MNAS_EINVAL;
-    if (a.taps == 1 && !a.is_pw) return MNAS_EINVAL;   // strided / padded 1x1 does not occur in this network
-    if (c->mode == 0 && !c->act.data) return MNAS_EINVAL;
-    if (c->mode == 1 && (!c->grad.g || (!c->grad.y) != (!c->grad.coef))) return MNAS_EINVAL;    // (y, coef) both or neither
+    if (a.red_y && (!a.red_bn || !a.stats)) return -MNAS_EINVAL;
+    if (a.taps != 1 && c->Ci > 1024) return -MNAS_EINVAL;
+    if (a.taps == 1 && !a.is_pw) return -MNAS_EINVAL;   // strided / padded 1x1 does not occur in this network
+    if (c->mode == 0 && !c->act.data) return -MNAS_EINVAL;
+    if (c->mode == 1 && (!c->grad.g || (!c->grad.y) != (!c->grad.coef))) return -MNAS_EINVAL;    // (y, coef) both or neither
     if (c->mode == 0 && a.is_pw && !c->resid && !c->gate && mnas_pwx_parts(a.M, c->Ci, c->Co) > 0)
-        return mnas_pwx_forward(c, stream);
-    if (a.is_pw && (c->mode == 1 || !c->resid) && mnas_pws_parts(c->mode, a.M, c->Ci, c->Co) > 0) {
-        const int rc = mnas_pws_run(c, stream);          // MNAS_EINVAL: not that kernel's case (a materialised dy): fall through
-        if (rc != MNAS_EINVAL) return rc;
-    }
+        return MNAS_ROUTE_PWX;
+    // (mnas_pws_accepts is false for what that kernel does not take, e.g. a materialised dy: the chain goes on)
+    if (a.is_pw && (c->mode == 1 || !c->resid) && mnas_pws_parts(c->mode, a.M, c->Ci, c->Co) > 0 && mnas_pws_accepts(c))
+        return MNAS_ROUTE_PWS;
     if (c->mode == 0 && a.is_pw && !c->resid && !c->gate && mnas_pwf_enabled() && mnas_pwf_parts(a.M, c->Ci, c->Co) > 0)
-        return mnas_pwf_forward(c, stream);
+        return MNAS_ROUTE_PWF;
     if (c->mode == 1 && a.is_pw && !c->resid && !c->bias && mnas_pwd_enabled() && mnas_pwd_parts(a.M, c->Ci, c->Co) > 0)
-        return mnas_pwd_dgrad(c, stream);
+        return MNAS_ROUTE_PWD;
 
     // weight-heavy dense 3x3 on the 7x7 planes: weight slices register-resident, images streamed (csrc/mnas_c3r.hip)
     if (a.taps == 9 && !c->resid && !(c->mode == 1 && c->grad.y) &&
         mnas_c3r_parts(c->mode, c->N, c->Hi, c->Wi, c->Ci, c->Ho, c->Wo, c->Co, c->kh, c->kw, c->stride, c->pad) > 0)
-        return mnas_c3r_run(c, stream);
+        return MNAS_ROUTE_C3R;
     // dense 3x3 on the 14x14 / 7x7 maps: whole image per workgroup (csrc/mnas_dimg.hip); MODE 1 there takes a materialised dy
     if (a.taps == 9 && !(c->mode == 0 && c->resid) && !(c->mode == 1 && (c->grad.y || c->resid)) &&
         mnas_dimg_parts(c->mode, c->N, c->Hi, c->Wi, c->Ci, c->Ho, c->Wo, c->Co, c->kh, c->kw, c->stride, c->pad) > 0)
-        return mnas_dimg_run(c, stream);
+        return MNAS_ROUTE_DIMG;
 
     // stride-2 3x3 forward on the large maps: every wave weight-stationary, fragments gathered from global memory (csrc/mnas_c3x.hip)
     if (c->mode == 0 && a.taps == 9 && !c->resid && !c->gate &&
         mnas_c3x_ok(c->N, c->Hi, c->Wi, c->Ci, c->Ho, c->Wo, c->Co, c->kh, c->kw, c->stride, c->pad))
-        return mnas_c3x_run(c, stream);
+        return MNAS_ROUTE_C3X;
 
-    int best_nt, nblocks, pt;
-    igemm_tiling(c->Co, a.Kpad, a.M, &best_nt, &nblocks, &pt);
+    igemm_tiling(c->Co, a.Kpad, a.M, nt_out, nblocks_out, pt_out);
+    const int best_nt = *nt_out, pt = *pt_out;
     if (pt == 1 && a.Kpad >= 256 && (best_nt == 2 || best_nt == 3 || best_nt == 6 || (best_nt == 4 && mnas_diag_env("MNAS_IG_K128_NT4", 1)))) a.kch = 128;
+    return MNAS_ROUTE_IGEMM;
+}
+
+extern "C" int mnas_conv_gemm_route(const MnasConvGemm* c, int* out) {
+    IgemmArgs a;
+    int nt = 0, nblocks = 0, pt = 0;
+    const int route = conv_gemm_plan(c, &a, &nt, &nblocks, &pt);
+    if (out) {
+        out[0] = out[1] = out[2] = out[3] = 0;
+        if (route == MNAS_ROUTE_IGEMM) { out[0] = nt; out[1] = pt; out[2] = a.kch; out[3] = a.s2; }
+    }
+    return route;
+}
+
+extern "C" int mnas_conv_gemm(const MnasConvGemm* c, void* stream) {
+    IgemmArgs a;
+    int best_nt = 0, nblocks = 0, pt = 0;
+    switch (conv_gemm_plan(c, &a, &best_nt, &nblocks, &pt)) {
+        case MNAS_ROUTE_PWX: return mnas_pwx_forward(c, stream);
+        case MNAS_ROUTE_PWS: return mnas_pws_run(c, stream);
+        case MNAS_ROUTE_PWF: return mnas_pwf_forward(c, stream);
+        case MNAS_ROUTE_PWD: return mnas_pwd_dgrad(c, stream);
+        case MNAS_ROUTE_C3R: return mnas_c3r_run(c, stream);
+        case MNAS_ROUTE_DIMG: return mnas_dimg_run(c, stream);
+        case MNAS_ROUTE_C3X: return mnas_c3x_run(c, stream);
+        case MNAS_ROUTE_IGEMM: break;
+        default: return MNAS_EINVAL;
+    }
     hipStream_t s = (hipStream_t)stream;
 #define MNAS_IG(MODE_, NT_) \
     if (c->mode == MODE_ && best_nt == NT_) return pt == 2 ? launch_igemm<MODE_, NT_, 2>(a, c->nparts, nblocks, s) \

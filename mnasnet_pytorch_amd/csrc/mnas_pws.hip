@@ -331,10 +331,19 @@ int mnas_pws_gate_ok(int M, int K, int N) {
 }
 
 // called by mnas_conv_gemm for 1x1 convs when mnas_pws_parts(...) > 0
+// 1 when mnas_pws_run takes this launch (host-side): a planned shape, dy-on-load operands in input-gradient mode (a materialised
+// dy goes to the kernels behind it in mnas_conv_gemm's chain), a gate only with short per-wave K slices
+int mnas_pws_accepts(const MnasConvGemm* c) {
+    const int M = c->N * c->Ho * c->Wo;
+    PwsPlan p;
+    if (!pws_plan(c->mode, M, c->Ci, c->Co, &p) || (c->mode == 1 && !c->grad.coef)) return 0;
+    if (c->mode == 0 && c->gate && (!c->act.scale || p.ksw > 3)) return 0;
+    return 1;
+}
 int mnas_pws_run(const MnasConvGemm* c, void* stream) {
     const int M = c->N * c->Ho * c->Wo;
     PwsPlan p;
-    if (!pws_plan(c->mode, M, c->Ci, c->Co, &p) || (c->mode == 1 && !c->grad.coef)) return MNAS_EINVAL;
+    if (!mnas_pws_accepts(c) || !pws_plan(c->mode, M, c->Ci, c->Co, &p)) return MNAS_EINVAL;
     PwsArgs a;
     a.M = M; a.K = c->Ci; a.N = c->Co;
     a.ksteps = (c->Ci + 31) / 32; a.Kpad = a.ksteps * 32;

@@ -9,7 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from cases import O
-from gpu_util import (L, act_in, bf16r, conv_gemm, dy_ref, from_nhwc, grad_in, nhwc, pack, rand_bn_coefs, relerr)
+from gpu_util import (L, act_in, bf16r, conv_gemm, dy_ref, from_nhwc, grad_in, guarded, nhwc, pack, rand_bn_coefs, relerr)
 
 pytestmark = pytest.mark.gpu
 TOL_BF16 = 6e-3
@@ -439,39 +439,45 @@ def test_stem(shape):
     xd = x.cuda()
     wp = pack(w.view(Co, 27, 1, 1), L.PACK_FWD)
     nparts = 9
-    out = torch.empty((N, Ho, Wo, Co), dtype=torch.bfloat16, device="cuda")
-    st = torch.full((2, Co, nparts), float("nan"), device="cuda")
+    out, out_chk = guarded((N, Ho, Wo, Co), torch.bfloat16)
+    st, st_chk = guarded((2, Co, nparts), torch.float32)
     a = L.MnasStemFwd()
     a.N, a.H, a.W, a.Ho, a.Wo, a.Co, a.nparts = N, H, W, Ho, Wo, Co, nparts
     db = bias.cuda()
     a.x, a.w, a.bias, a.out, a.stats = xd.data_ptr(), wp.data_ptr(), db.data_ptr(), out.data_ptr(), st.data_ptr()
     L.check(lib.mnas_stem_fwd(C.byref(a), L.cur_stream()), "stem_fwd")
+    out_chk("stem_fwd out")
+    st_chk("stem_fwd stats")
     assert relerr(from_nhwc(out), ref) < TOL_BF16
     st = st.cpu().double().sum(-1)
     assert relerr(st[0], ref.double().sum((0, 2, 3))) < TOL_F32
+    assert relerr(st[1], (ref.double() ** 2).sum((0, 2, 3))) < TOL_F32
     # wgrad
     g, y = _x((N, Co, Ho, Wo), 6), _x((N, Co, Ho, Wo), 7)
     b = rand_bn_coefs(Co, 9, O)
     dy = dy_ref(g, y, b)
     ref_dw = torch.nn.grad.conv2d_weight(bf16r(x), (Co, 3, 3, 3), dy, stride=2, padding=1)
     gd, yd, bd = nhwc(g), nhwc(y), b.cuda()
-    partial = torch.full((nparts, Co, 27), float("nan"), device="cuda")
+    partial, partial_chk = guarded((nparts, Co, 27), torch.float32)
     s = L.MnasStemWgrad()
     s.N, s.H, s.W, s.Ho, s.Wo, s.Co, s.nparts = N, H, W, Ho, Wo, Co, nparts
     s.x, s.dy, s.partial = xd.data_ptr(), grad_in(gd, yd, bd), partial.data_ptr()
     L.check(lib.mnas_stem_wgrad(C.byref(s), L.cur_stream()), "stem_wgrad")
-    grad = torch.full((Co, 3, 3, 3), float("nan"), device="cuda")
+    partial_chk("stem_wgrad partial")
+    grad, grad_chk = guarded((Co, 3, 3, 3), torch.float32)
     L.check(lib.mnas_wgrad_finalize(partial.data_ptr(), nparts, Co, 27, 1, grad.data_ptr(), 0, L.cur_stream()))
+    grad_chk("stem dW")
     assert relerr(grad.cpu(), ref_dw) < TOL_F32
     # input gradient (dL/d image, fp32 NCHW): bf16 dy and weights, fp32 accumulate; with the fused input normalisation's scale
     ref_dx = torch.nn.grad.conv2d_input((N, 3, H, W), w, bf16r(dy), stride=2, padding=1)
     w32 = w.cuda().contiguous()
     for aff in (None, torch.tensor([[2.0, 0.5, 1.25], [0.1, 0.2, 0.3]])):
-        dx = torch.full((N, 3, H, W), float("nan"), device="cuda")
+        dx, dx_chk = guarded((N, 3, H, W), torch.float32)
         affd = aff.cuda().contiguous() if aff is not None else None
         gi = grad_in(gd, yd, bd)
         L.check(lib.mnas_stem_dgrad(C.byref(gi), w32.data_ptr(), N, H, W, Ho, Wo, Co, affd.data_ptr() if aff is not None else None,
                                     dx.data_ptr(), L.cur_stream()), "stem_dgrad")
+        dx_chk("stem_dgrad dx")
         want = ref_dx if aff is None else ref_dx * aff[0].view(1, 3, 1, 1)
         assert relerr(dx.cpu(), want) < TOL_F32
     assert lib.mnas_stem_dgrad(C.byref(gi), w32.data_ptr(), N, H, W, Ho + 1, Wo, Co, None, dx.data_ptr(), L.cur_stream()) == L.EINVAL
