@@ -446,6 +446,83 @@ int mnas_head_cross_entropy_metrics(const void* logits, const void* target, int 
 int mnas_head_metrics(const void* logits, const void* target, int N, int C, const int* ks, int nk, const void* loss,
                       void* rank_rows, MnasMeters* meters, void* stream);
 
+/* ---- the multi-label branch of the step (csrc/mnas_mlabel.hip): MultiClassBCELoss (src/models/multi_class_loss.py), HardDice
+ * and the per-sample macro-F1 of batch_metrics (src/utils/metric.py) as train.py:274-279, 453-463, 577-587 use them, with the three
+ * AverageMeters of that branch in one MnasMultiLabelMeters block in device memory.  logits z, target t, weights w: fp32 [N][C].
+ *
+ * Arithmetic rule:
+ *   loss element  e = max(z,0) - z*t + log1p(exp(-|z|)), times w when weights are given;  b = sum(e) / (N*C)  (row sums in fp32 in
+ *                 a fixed order, the N row sums added in double, one rounding to fp32).
+ *   focal         pt = exp(-b), loss = balance * (1-pt)^gamma * b -- applied to the MEAN b, not per element, as the reference does
+ *                 (evaluated in double by one thread, rounded once); without focal loss = b.
+ *   gradient      dlogits = s * w * (sigma(z) - t) / (N*C);  s = 1 without focal, else
+ *                 s = balance * (1-pt)^(gamma-1) * ((1-pt) + gamma*pt*b)  (gamma >= 1);  sigma(z) = 1/(1+exp(-z)) for z >= 0 and
+ *                 exp(z)/(1+exp(z)) for z < 0.
+ *   F1            class c of a row is predicted iff z >= 0 and true iff t == 1 (batch_metrics: sigmoid < 0.5 -> 0, then > 0 -> 1, so
+ *                 0.5 counts as positive).  With tp/fp/fn/tn over the row's C classes: F1_1 = 2tp/(2tp+fp+fn) if tp+fp+fn > 0,
+ *                 F1_0 = 2tn/(2tn+fp+fn) if tn+fp+fn > 0; the row's F1 is the mean of those that exist (scikit-learn's macro average
+ *                 over the labels present), in double.  Batch value = (sum of the rows' F1, in row order, by one thread, one
+ *                 rounded double sum per row) / N: the reference's sum(list) / len(list).
+ *   HardDice      predicted iff z > threshold_logit (strict; 0 for the threshold 0.5); I = #(predicted and t == 1),
+ *                 U = #predicted + #(t == 1) (minus I with deduct_intersection); value = clamp(1 + log(2I/U), 0, 1) in fp32 and 0
+ *                 when I == 0.
+ *   A NaN logit is predicted negative under both rules (comparisons are false).  Targets other than exactly 1 are negatives for the
+ *   metrics; any t enters the loss (soft labels).
+ *   Deviation from the reference: both prediction rules are evaluated on the LOGIT, not on an fp32 sigmoid.  They differ only for
+ *   0 < |z| < 2^-23, where the fp32 sigmoid rounds to exactly 0.5 (sigmoid(1e-9) is not > 0.5; sigmoid(-1e-9) == 0.5 counts as
+ *   positive for F1).  At z == 0 both agree with the reference: F1 positive, Dice negative.
+ *
+ * The block follows MnasMeters: every field 8 bytes, all int64 first, then all double (an all-reduce is two tensors).  Each meter is
+ * an AverageMeter: sum += val * n as one rounded double product and one rounded double sum per update, no fused multiply-add. */
+#define MNAS_MLABEL_NUM_I64 16
+#define MNAS_MLABEL_NUM_F64 9
+typedef struct MnasMultiLabelMeters {
+    /* running */
+    int64_t steps;                               /* updates since the block was zeroed */
+    int64_t samples;                             /* sum of N over all updates */
+    int64_t nonfinite_steps;                     /* updates whose loss was NaN / Inf */
+    int64_t loss_n;                              /* AverageMeter.count of the loss meter (sum of n_loss over updates with a loss) */
+    int64_t dice_n;                              /* ... of the HardDice meter */
+    int64_t f1_n;                                /* ... of the F1 meter */
+    int64_t tp;                                  /* Dice rule: predicted and true */
+    int64_t fp;                                  /* Dice rule: predicted, not true */
+    int64_t fn;                                  /* Dice rule: true, not predicted */
+    /* last update */
+    int64_t last_n;
+    int64_t last_loss_n;                         /* n_loss of the last update that carried a loss */
+    int64_t last_dice_n;
+    int64_t last_f1_n;
+    int64_t last_tp;
+    int64_t last_fp;
+    int64_t last_fn;
+    double  loss_sum;                            /* running: sum of val * n */
+    double  dice_sum;
+    double  f1_sum;
+    double  last_loss;                           /* AverageMeter.val */
+    double  last_dice;
+    double  last_f1;
+    double  last_loss_sum;                       /* val * n of the last update (what an all-reduce sums: val over ranks = sum / n) */
+    double  last_dice_sum;
+    double  last_f1_sum;
+} MnasMultiLabelMeters;
+/* All calls: stream-ordered, no allocation, no host read of device memory, no float atomics (results do not depend on the run),
+ * capturable in a hipGraph.  scratch: mnas_mlabel_scratch_bytes(N) bytes of device memory, 16-byte aligned, owned by the call until
+ * it has run.  Zero the block (hipMemsetAsync) to reset it.  The meters' Dice threshold is 0.5 without deduct_intersection
+ * (train.py:279).  n_loss / n_dice / n_f1: the weights of the three meters (train.py:447-463: N, N and the number of classes).
+ *   mnas_mlabel_bce       : *loss (device fp32) and dlogits (NULL: forward only); weights NULL: none; focal != 0: the focal
+ *                           transform with focus_param (>= 1) and balance_param.  meters != NULL: the same launches also update the
+ *                           block (loss and dlogits are bit-identical either way).  Two launches, three with focal and dlogits.
+ *   mnas_mlabel_metrics   : logits from anywhere; loss = device fp32 scalar or NULL (then the loss meter does not move).  Two launches.
+ *   mnas_mlabel_hard_dice : *out (device fp32) = HardDice of one batch.  Two launches. */
+int64_t mnas_mlabel_scratch_bytes(int N);
+int mnas_mlabel_bce(const void* logits, const void* target, const void* weights, int N, int C, int focal, float focus_param,
+                    float balance_param, void* scratch, void* loss, void* dlogits, MnasMultiLabelMeters* meters, int64_t n_loss,
+                    int64_t n_dice, int64_t n_f1, void* stream);
+int mnas_mlabel_metrics(const void* logits, const void* target, int N, int C, const void* loss, void* scratch,
+                        MnasMultiLabelMeters* meters, int64_t n_loss, int64_t n_dice, int64_t n_f1, void* stream);
+int mnas_mlabel_hard_dice(const void* logits, const void* target, int N, int C, float threshold_logit, int deduct_intersection,
+                          void* scratch, void* out, void* stream);
+
 /* ---- squeeze-and-excitation of the SE variant of MBConv_block (BASELINE config 4; build-defined -- the reference has no SE
  * block; csrc/mnas_se.hip, restated in oracle.se_apply).  a = the activated depthwise output (act-on-load of y2), u = the
  * excite logits fp32 [N][C] (mnas_pool_act -> mnas_head_linear_fwd x2 produce them).

@@ -11,8 +11,10 @@ from .classifiers import FineTuneModelPool, load_model  # noqa: F401
 from .sampler import ClusterRandomSampler, DistributedClusterSampler  # noqa: F401
 from .transforms import (DeviceColorJitter, DevicePipeline, DeviceRandomGrayscale, DeviceTransform, ImageBatch,  # noqa: F401
                          collate_decoded)
-from .metrics import DeviceMeters, accuracy  # noqa: F401
+from .metrics import DeviceMeters, MultiLabelMeters, accuracy  # noqa: F401
+from .losses import HardDice, MultiClassBCELoss  # noqa: F401
 
 __all__ = ["Mnasnet", "ConvBlock", "SepConv", "MBConv_block", "MBConv", "load_model", "FineTuneModelPool",
            "ClusterRandomSampler", "DistributedClusterSampler", "DeviceTransform", "ImageBatch", "collate_decoded",
-           "DevicePipeline", "DeviceColorJitter", "DeviceRandomGrayscale", "DeviceMeters", "accuracy"]
+           "DevicePipeline", "DeviceColorJitter", "DeviceRandomGrayscale", "DeviceMeters", "accuracy",
+           "MultiLabelMeters", "MultiClassBCELoss", "HardDice"]

@@ -144,6 +144,17 @@ class MnasMeters(C.Structure):
                 ("loss_sum", c_double), ("last_loss", c_double), ("last_loss_sum", c_double)]
 
 
+MLABEL_NUM_I64, MLABEL_NUM_F64 = 16, 9                          # MNAS_MLABEL_*
+
+
+class MnasMultiLabelMeters(C.Structure):
+    """include/mnas.h: 16 int64 then 9 double, every field 8 bytes wide (the block is also viewed as two tensors)"""
+    _fields_ = [(n, c_int64) for n in ("steps", "samples", "nonfinite_steps", "loss_n", "dice_n", "f1_n", "tp", "fp", "fn", "last_n",
+                                       "last_loss_n", "last_dice_n", "last_f1_n", "last_tp", "last_fp", "last_fn")] + \
+               [(n, c_double) for n in ("loss_sum", "dice_sum", "f1_sum", "last_loss", "last_dice", "last_f1", "last_loss_sum",
+                                        "last_dice_sum", "last_f1_sum")]
+
+
 SYMBOLS = {
     "mnas_conv_img_parts": (c_int, [c_int] * 11),
     "mnas_stem_parts": (c_int, [c_int, c_int, c_int, c_int, c_int]),
@@ -157,6 +168,12 @@ SYMBOLS = {
                                                 C.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
     "mnas_head_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, C.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
                                   c_void_p]),
+    "mnas_mlabel_scratch_bytes": (c_int64, [c_int]),
+    "mnas_mlabel_bce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "mnas_mlabel_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                    c_void_p]),
+    "mnas_mlabel_hard_dice": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "mnas_se_scale": (c_int, [C.POINTER(MnasActIn), c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mnas_se_bwd_reduce": (c_int, [c_void_p, C.POINTER(MnasActIn), c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "mnas_se_scratch_bytes": (c_int64, [c_int, c_int, c_int]),

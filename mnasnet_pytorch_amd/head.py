@@ -6,7 +6,8 @@ Two entry points share the same kernels:
 * :class:`NativeHead` ``.apply(x)`` -- an autograd function, used by ``FineTuneModelPool.forward`` so that
   ``model(x)`` / ``criterion(out, target)`` / ``loss.backward()`` of train.py:434-439 work unchanged;
 * :meth:`NativeHead.loss_and_grad` -- logits, cross-entropy, and the whole backward of the head in 8 launches without
-  autograd; ``Trainer.step`` takes this path when the criterion is a plain ``nn.CrossEntropyLoss``.
+  autograd; ``Trainer.step`` takes this path when the criterion is a plain ``nn.CrossEntropyLoss`` or this package's
+  ``MultiClassBCELoss`` (the multi-label branch: :meth:`NativeHead.bce`, csrc/mnas_mlabel.hip).
 
 Dropout masks are a counter-based hash of (seed, element index) evaluated inside the GEMM kernels (never stored).  The seed
 of a call is derived from ``torch.initial_seed()``, the rank and a per-head call counter, so runs are reproducible under
@@ -200,6 +201,20 @@ class NativeHead:
                 "head_cross_entropy")
         return loss, dl
 
+    def bce(self, logits, target, criterion, weights=None, need_grad=True, meters=None, f1_n=None):
+        """-> (loss 0-d tensor, dlogits or None) of a losses.MultiClassBCELoss ``criterion`` (csrc/mnas_mlabel.hip).  target: (N, C),
+        converted with .float() as train.py:429 does.  ``meters`` (a metrics.MultiLabelMeters): the same launches also update its
+        loss / HardDice(0.5) / F1 block with the weights N, N and ``f1_n`` (default N)."""
+        from .losses import bce_with_logits
+        N = logits.shape[0]
+        if not isinstance(target, torch.Tensor) or target.shape != logits.shape:
+            raise ValueError("multi-label target must be of shape (N, C) = %s, got %s"
+                             % (tuple(logits.shape), tuple(getattr(target, "shape", ()))))
+        target, weights = criterion.prepare(logits, target, weights)
+        return bce_with_logits(logits, target, weights, bool(criterion.use_focal_weights), criterion.focus_param,
+                               criterion.balance_param, need_grad=need_grad, meters=meters,
+                               meter_weights=(N, N, N if f1_n is None else f1_n))
+
     def check_targets(self):
         """Host check of the device-side "target out of range" flag that mnas_head_cross_entropy raises (the loss is NaN from
         that step on; ATen asserts on the device instead).  Synchronises: call it next to a ``loss.item()``, not per step.
@@ -213,12 +228,17 @@ class NativeHead:
     def apply(self, x):
         return _HeadFn.apply(self, x, *self.params())
 
-    def loss_and_grad(self, x, target, ignore_index=-100, need_dx=True, meters=None):
+    def loss_and_grad(self, x, target, ignore_index=-100, need_dx=True, meters=None, criterion=None, f1_n=None):
         """Forward, loss and full backward of the head without autograd.  Parameter gradients are ACCUMULATED into
-        ``p.grad`` (which must exist: Trainer points them into its flat gradient buffer).  -> (logits, loss, dx)"""
+        ``p.grad`` (which must exist: Trainer points them into its flat gradient buffer).  -> (logits, loss, dx).
+        ``criterion``: None / an nn.CrossEntropyLoss -> cross-entropy with ``ignore_index``; a losses.MultiClassBCELoss -> :meth:`bce`."""
+        from .losses import MultiClassBCELoss
         seeds = self.next_seeds()
         us, logits = self.forward_layers(x, seeds)
-        loss, dl = self.cross_entropy(logits, target, ignore_index, meters=meters)
+        if type(criterion) is MultiClassBCELoss:             # the class itself, as Trainer routes it
+            loss, dl = self.bce(logits, target, criterion, meters=meters, f1_n=f1_n)
+        else:
+            loss, dl = self.cross_entropy(logits, target, ignore_index, meters=meters)
         grads = []
         for l in self.layers:
             if l.lin.weight.grad is None or (l.lin.bias is not None and l.lin.bias.grad is None):

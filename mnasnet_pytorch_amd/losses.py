@@ -1,0 +1,133 @@
+"""The criterion and the Dice metric of the reference's multi-label branch (``src/models/multi_class_loss.py``; train.py:274-279
+builds ``MultiClassBCELoss()`` and ``HardDice(threshold=0.5)`` when ``--multi_class`` is set, its default) on the HIP library
+(csrc/mnas_mlabel.hip; the arithmetic rule is stated in include/mnas.h).
+
+* :class:`MultiClassBCELoss` -- same constructor and ``forward(outputs, targets, weights=None)``.  BCE-with-logits, mean-reduced,
+  optional element weights, optional focal transform of the MEAN (as the reference applies it).  Differentiable with respect to
+  ``outputs``.  ``Trainer`` recognises this class and runs the whole step without autograd (head.NativeHead.bce).
+* :class:`HardDice` -- same constructor; returns a 0-d fp32 device tensor without a host sync.
+
+Deviations: the Dice prediction is ``outputs > logit(threshold)`` instead of ``sigmoid(outputs) > threshold`` (equal except where
+the fp32 sigmoid rounds onto the threshold), so the threshold must lie inside (0, 1); ``focus_param < 1`` is refused (the gradient
+holds ``(1 - pt) ** (focus_param - 1)``).  No CPU path: tensors must live on the MI355X."""
+from __future__ import annotations
+
+import math
+
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+
+
+def _scratch(lib, N, device):
+    return torch.empty(int(lib.mnas_mlabel_scratch_bytes(N)), dtype=torch.uint8, device=device)
+
+
+def _on_device(name, t, device=None):
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise RuntimeError("%s must be a tensor on the MI355X (no CPU path)" % name)
+    if device is not None and t.device != device:
+        raise RuntimeError("%s is on %s, outputs on %s (the kernels take raw device pointers)" % (name, t.device, device))
+
+
+def check_focus_param(focus_param):
+    if not float(focus_param) >= 1.0:
+        raise ValueError("focus_param must be >= 1 (the gradient holds (1 - pt) ** (focus_param - 1)), got %r" % (focus_param,))
+
+
+def bce_with_logits(logits, target, weights=None, focal=False, focus_param=2, balance_param=0.25, need_grad=True, meters=None,
+                    meter_weights=None):
+    """mnas_mlabel_bce on (N, C) fp32 contiguous device tensors -> (loss 0-d tensor, dlogits or None).  ``meters`` (a
+    metrics.MultiLabelMeters) with ``meter_weights = (n_loss, n_dice, n_f1)``: the same launches also move its block."""
+    lib = L.load()
+    N, Cn = logits.shape
+    dev = logits.device
+    if focal:
+        check_focus_param(focus_param)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dl = torch.empty_like(logits) if need_grad else None
+    scratch = _scratch(lib, N, dev)
+    blk, (n_loss, n_dice, n_f1) = 0, (0, 0, 0)
+    if meters is not None:
+        blk = meters.kernel_args(dev)
+        n_loss, n_dice, n_f1 = (int(v) for v in meter_weights)
+    L.check(lib.mnas_mlabel_bce(logits.data_ptr(), target.data_ptr(), L.ptr(weights), N, Cn, 1 if focal else 0, float(focus_param),
+                                float(balance_param), scratch.data_ptr(), loss.data_ptr(), L.ptr(dl), blk, n_loss, n_dice, n_f1,
+                                L.cur_stream()), "mlabel_bce")
+    return loss, dl
+
+
+class _BCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, outputs, targets, weights, focal, focus_param, balance_param):
+        loss, dl = bce_with_logits(outputs.detach().float().contiguous(), targets, weights, focal, focus_param, balance_param,
+                                   need_grad=ctx.needs_input_grad[0])
+        ctx.dl, ctx.dtype = dl, outputs.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return (ctx.dl * grad_output).to(ctx.dtype), None, None, None, None, None
+
+
+class MultiClassBCELoss(nn.Module):
+    def __init__(self, use_weight_mask=False, use_focal_weights=False, focus_param=2, balance_param=0.25):
+        super().__init__()
+        self.use_weight_mask = use_weight_mask
+        self.use_focal_weights = use_focal_weights
+        self.focus_param = focus_param
+        self.balance_param = balance_param
+        if use_focal_weights:
+            check_focus_param(focus_param)
+
+    def prepare(self, outputs, targets, weights=None):
+        """shape and device checks -> (targets, weights or None) as fp32 contiguous tensors.  A target whose rank, row count or
+        class count differs from the outputs' is an AssertionError, as it is for the reference's criterion; the weights are
+        dropped unless use_weight_mask is set, as there"""
+        if outputs.dim() != 2:
+            raise ValueError("outputs must be (N, C), got %s" % (tuple(outputs.shape),))
+        N, Cn = outputs.shape
+        assert targets.dim() == 2, "targets have %d dimensions, outputs 2" % targets.dim()
+        assert targets.shape[0] == N, "targets have %d rows, outputs %d" % (targets.shape[0], N)
+        assert targets.shape[1] == Cn, "targets have %d classes, outputs %d" % (targets.shape[1], Cn)
+        if weights is not None and weights.shape != outputs.shape:
+            raise ValueError("weights must be %s, got %s" % (tuple(outputs.shape), tuple(weights.shape)))
+        _on_device("outputs", outputs)
+        _on_device("targets", targets, outputs.device)
+        targets = targets.detach().float().contiguous()
+        if weights is not None and self.use_weight_mask:
+            _on_device("weights", weights, outputs.device)
+            weights = weights.detach().float().contiguous()
+        else:
+            weights = None
+        return targets, weights
+
+    def forward(self, outputs, targets, weights=None):
+        targets, weights = self.prepare(outputs, targets, weights)
+        return _BCEFn.apply(outputs, targets, weights, bool(self.use_focal_weights), self.focus_param, self.balance_param)
+
+
+class HardDice(nn.Module):
+    def __init__(self, threshold=0.5, deduct_intersection=False):
+        super().__init__()
+        if not 0.0 < float(threshold) < 1.0:
+            raise ValueError("threshold must lie inside (0, 1): the prediction is outputs > logit(threshold), got %r" % (threshold,))
+        self.threshold = threshold
+        self.deduct_intersection = deduct_intersection
+
+    def forward(self, outputs, targets):
+        _on_device("outputs", outputs)
+        _on_device("targets", targets, outputs.device)
+        if outputs.dim() != 2 or targets.shape != outputs.shape:
+            raise ValueError("outputs and targets must both be (N, C), got %s and %s" % (tuple(outputs.shape), tuple(targets.shape)))
+        lib = L.load()
+        N, Cn = outputs.shape
+        z = outputs.detach().float().contiguous()
+        t = targets.detach().float().contiguous()
+        th = float(self.threshold)
+        out = torch.empty((), dtype=torch.float32, device=z.device)
+        scratch = _scratch(lib, N, z.device)
+        L.check(lib.mnas_mlabel_hard_dice(z.data_ptr(), t.data_ptr(), N, Cn, math.log(th / (1.0 - th)), 1 if self.deduct_intersection else 0,
+                                          scratch.data_ptr(), out.data_ptr(), L.cur_stream()), "mlabel_hard_dice")
+        return out

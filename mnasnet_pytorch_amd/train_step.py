@@ -231,10 +231,11 @@ class Trainer:
                  criterion: Optional[nn.Module] = None, distributed: bool = False, process_group=None,
                  early_bucket_stage: int = 5, optimizer: str = "adam", meters=None, **optimizer_kwargs):
         self.model = model
-        self.meters = meters             # metrics.DeviceMeters or None: train.py:447,465-468 on the device (see forward_backward)
+        self.meters = meters             # metrics.DeviceMeters / MultiLabelMeters or None: train.py:447,453-468 on the device
         self.native_step = True          # see _native_head()
         self.last_logits = None
         self.criterion = criterion if criterion is not None else nn.CrossEntropyLoss()   # train.py:277
+        self._check_meters(meters)
         self.lib = L.load()
         dev = next(model.parameters()).device
         if dev.type != "cuda":
@@ -324,6 +325,23 @@ class Trainer:
     def load_state_dict(self, sd):
         self.optimizer.load_state_dict(sd["optimizer"])
 
+    def _multilabel(self):
+        """the criterion is this package's MultiClassBCELoss itself: the reference's multi-label branch (train.py:274-279).  A
+        subclass may override forward(), so it keeps the module path, as a subclass of nn.CrossEntropyLoss does"""
+        from .losses import MultiClassBCELoss
+        return type(self.criterion) is MultiClassBCELoss
+
+    def _check_meters(self, meters):
+        """the meters' kind against the criterion's, before anything is launched (the constructor, every forward_backward and
+        validate call it: ``criterion`` and ``meters`` are plain attributes)"""
+        from .losses import MultiClassBCELoss
+        from .metrics import MultiLabelMeters
+        if isinstance(meters, MultiLabelMeters) and isinstance(self.criterion, nn.CrossEntropyLoss):
+            raise ValueError("MultiLabelMeters count (N, C) multi-label targets; a cross-entropy criterion takes class indices "
+                             "(use DeviceMeters)")
+        if meters is not None and isinstance(self.criterion, MultiClassBCELoss) and not isinstance(meters, MultiLabelMeters):
+            raise ValueError("a MultiClassBCELoss step feeds MultiLabelMeters, not %s" % type(meters).__name__)
+
     def _native_head(self):
         """The model's NativeHead when the whole step can bypass autograd: FineTuneModelPool-like model in training mode
         (fused pool, Dropout/Linear/ReLU classifier) and a plain mean-reduced nn.CrossEntropyLoss (train.py:277)."""
@@ -341,9 +359,13 @@ class Trainer:
         """The part of _native_head() that does not concern training: what lets a validation batch run as engine forward (fused
         pool) -> head -> fused loss."""
         m, c = self.model, self.criterion
-        if not self.native_step or type(c) is not nn.CrossEntropyLoss:
+        if not self.native_step:
             return None
-        if c.weight is not None or c.reduction != "mean" or getattr(c, "label_smoothing", 0.0) != 0.0:
+        if self._multilabel():
+            pass                   # losses.MultiClassBCELoss: every setting of it is covered (head.NativeHead.bce)
+        elif type(c) is not nn.CrossEntropyLoss:
+            return None
+        elif c.weight is not None or c.reduction != "mean" or getattr(c, "label_smoothing", 0.0) != 0.0:
             return None
         if not (hasattr(m, "_native_head") and getattr(m, "native_head", False) and getattr(m, "fuse_pool", False)):
             return None
@@ -379,6 +401,7 @@ class Trainer:
         """train.py:427-439 without the optimizer: forward, loss, backward INTO the flat gradient buffer (accumulating into what is
         already there: two calls between ``optimizer.zero_grad()`` and ``optimizer.step()`` sum their gradients, which is what
         the world-2 test uses to emulate two data-parallel ranks in one process).  Fires the engine's stage-done callback."""
+        self._check_meters(self.meters)                      # before any launch, on either path
         head = self._native_head()
         if head is not None:
             # features -> pool -> head -> cross-entropy -> head backward -> features backward as plain launch lists: no
@@ -398,8 +421,14 @@ class Trainer:
             head.calls = self.optimizer.step_count           # dropout masks follow the CHECKPOINTED step count: a resumed run does
                                                              # not replay the masks of the first steps
             # with meters: the loss kernels also rank every row's target and move the meters block -- no launch more
-            self.last_logits, loss, df = head.loss_and_grad(f.view(f.size(0), -1), target, self.criterion.ignore_index,
-                                                            meters=self.meters)
+            if self._multilabel():
+                # train.py:429 target.float(); the meters' weights are the reference's: input.size(0) for the loss and Dice,
+                # input.size(1) for F1 (train.py:447, 454, 463)
+                self.last_logits, loss, df = head.loss_and_grad(f.view(f.size(0), -1), target, meters=self._ml_meters(),
+                                                                criterion=self.criterion, f1_n=x.shape[1])
+            else:
+                self.last_logits, loss, df = head.loss_and_grad(f.view(f.size(0), -1), target, self.criterion.ignore_index,
+                                                                meters=self.meters)
             accumulate = eng.prepare_grads()
             prog.run_backward(df, eng.on_stage_done, static_io=True)
             eng.finish_grads(accumulate)
@@ -407,9 +436,22 @@ class Trainer:
             out = self.model(x.float())
             loss = self.criterion(out, target)
             loss.backward()
-            if self.meters is not None and self._class_vector(out, target):
+            if self._ml_meters() is not None:
+                if self._label_matrix(out, target):
+                    self.meters.update(out.detach(), target, loss.detach(), f1_n=x.shape[1])
+            elif self.meters is not None and self._class_vector(out, target):
                 self.meters.update(out.detach(), target, loss.detach())
         return loss.detach()
+
+    def _ml_meters(self):
+        """self.meters when it is a MultiLabelMeters, else None (_check_meters has settled that the kind fits the criterion)"""
+        from .metrics import MultiLabelMeters
+        return self.meters if isinstance(self.meters, MultiLabelMeters) else None
+
+    @staticmethod
+    def _label_matrix(out, target):
+        """multi-label classification: (N, C) outputs and an (N, C) target on the same device"""
+        return isinstance(target, torch.Tensor) and out.dim() == 2 and target.shape == out.shape and target.device == out.device
 
     @staticmethod
     def _class_vector(out, target):
@@ -423,13 +465,16 @@ class Trainer:
         ``model.eval()`` and ``torch.no_grad()``; for every ``(input, target)`` of ``batches``: ``transform(input)`` if given (a
         transforms.DevicePipeline / DeviceTransform over an ImageBatch), the engine's eval-mode forward with the fused pool, the
         native head without dropout, and the cross-entropy kernels that also move ``meters`` (default: a fresh DeviceMeters with
-        top-1 / top-5).  Any input shape works: the engine keeps one eval program per shape.  A model or criterion the native head
+        top-1 / top-5).  With this package's MultiClassBCELoss as the criterion it is the multi-label pass (train.py:575-587): (N, C)
+        targets, the BCE kernels, and a MultiLabelMeters (loss, HardDice(0.5), macro-F1; the default is a fresh one).  Any input shape works: the engine keeps one eval program per shape.  A model or criterion the native head
         does not cover runs as ``model(x)`` / ``criterion`` / ``meters.update``.  Distributed trainers broadcast rank 0's
         BatchNorm statistics first and sum the meters over the ranks at the end (``reduce=False``: neither).  The modules'
         train/eval flags are restored on the way out, also when a batch raises.  Returns ``meters.read()``."""
-        from .metrics import DeviceMeters
+        from .metrics import DeviceMeters, MultiLabelMeters
+        multilabel = self._multilabel()
         if meters is None:
-            meters = DeviceMeters((1, 5), self.device)
+            meters = MultiLabelMeters(self.device) if multilabel else DeviceMeters((1, 5), self.device)
+        self._check_meters(meters)
         model = self.model
         modes = [(mod, mod.training) for mod in model.modules()]
         if self.distributed and reduce:
@@ -452,10 +497,18 @@ class Trainer:
                         model._sync_input_norm()
                         f = self.engine.forward(x, pooled=True)
                         _, logits = head.forward_layers(f.view(f.size(0), -1), [0] * len(head.layers))   # eval: the seeds are unused
-                        head.cross_entropy(logits, target, self.criterion.ignore_index, need_grad=False, meters=meters)
+                        if multilabel:                                     # train.py:575-587: weights N, N and input.size(1)
+                            head.bce(logits, target, self.criterion, need_grad=False, meters=meters, f1_n=x.shape[1])
+                        else:
+                            head.cross_entropy(logits, target, self.criterion.ignore_index, need_grad=False, meters=meters)
                     else:
                         out = model(x)                                     # the engine converts (train.py:562 input.float())
                         loss = self.criterion(out, target)
+                        if isinstance(meters, MultiLabelMeters):
+                            if not self._label_matrix(out, target):
+                                raise ValueError("MultiLabelMeters count multi-label classification: (N, C) targets")
+                            meters.update(out, target, loss, f1_n=x.shape[1])
+                            continue
                         if not self._class_vector(out, target):
                             raise ValueError("validate() counts single-label classification only: int64 targets of shape (N,)")
                         meters.update(out, target, loss)
