@@ -126,6 +126,124 @@ PACK_FWD, PACK_DGRAD, PACK_DW, PACK_TCONV = 0, 1, 2, 3
 EINVAL = 10001      # MNAS_EINVAL
 ROUTE_PWX, ROUTE_PWS, ROUTE_PWF, ROUTE_PWD, ROUTE_C3R, ROUTE_DIMG, ROUTE_C3X, ROUTE_IGEMM = range(8)     # MNAS_ROUTE_*
 
+
+def _act(n):
+    return (n + ".data", n + ".scale", n + ".shift")
+
+
+def _grad(n):
+    return (n + ".g", n + ".y", n + ".coef")
+
+
+def _post(n):
+    return tuple(n + "." + f for f in ("nsplit", "Co", "Ci", "taps", "dw", "level"))
+
+
+# What run_one() (csrc/mnas_abi.hip) reads of a MnasOp, per opcode: the names of the slots of i, d and p in order (None: a retired
+# slot).  THE description of the launch-list encoding: set_op() / op_field() address slots through it and nothing else spells an
+# index; tests/test_abi_cpu.py holds it to run_one()'s source.  i[14] is the stream of every op (mnas_run_ops_multi).
+OP_SLOTS = {
+    OP_CONV_GEMM: (("mode", "N", "Hi", "Wi", "Ci", "Ho", "Wo", "Co", "kh", "kw", "stride", "pad", "nparts"), (),
+                   _act("act") + _grad("grad") + ("w", "bias", "resid", "out", "stats", "red_y", "red_bn", "gate")),
+    OP_CONV_WGRAD: (("N", "Hi", "Wi", "Ci", "Ho", "Wo", "Co", "kh", "kw", "stride", "pad", "nsplit"), (),
+                    _act("x") + _grad("dy") + ("partial",)),
+    OP_WGRAD_FINALIZE: (("nsplit", "Co", "Ci", "taps", "accumulate"), (), ("partial", "grad")),
+    OP_DW_FWD: (("N", "H", "W", "C", "k", "nparts", "stride"), (), _act("in_") + ("w", "bias", "out", "stats")),
+    OP_DW_BWD: (("N", "H", "W", "C", "k", "nparts", "phase", "stride", "g_masked"), (),
+                _act("x") + _grad("dy") + ("w", "gin", "wpartial", "red_bn", "red_partial")),
+    OP_DW_WGRAD_FINALIZE: (("nparts", "C", "k", "accumulate"), (), ("wpartial", "grad")),
+    OP_STEM_FWD: (("N", "H", "W", "Ho", "Wo", "Co", "nparts", "in_u8"), (), ("x", "w", "bias", "out", "stats", "in_affine")),
+    OP_STEM_WGRAD: (("N", "H", "W", "Ho", "Wo", "Co", "nparts", "in_u8"), (), ("x",) + _grad("dy") + ("partial", "in_affine")),
+    OP_STEM_DGRAD: (("N", "H", "W", "Ho", "Wo", "Co"), (), _grad("dy") + ("w", "in_affine", "dx")),
+    OP_BN_FWD_FINALIZE: (("nparts", "C", "training"), ("count", "momentum", "eps"),
+                         ("partial", "gamma", "beta", "rmean", "rvar", "nbt", "bnbuf")),
+    OP_BN_BWD_REDUCE: (("C", "nparts"), ("rows",), ("g", "y", "bnbuf", "partial")),
+    OP_BN_BWD_FINALIZE: (("nparts", "C", "accumulate"), ("count",), ("partial", "bnbuf", "dgamma", "dbeta")),
+    OP_ADD_ACT: (("C", "HW"), ("rows",), _act("a") + _act("b") + ("out_bf16", "out_nchw")),
+    OP_NCHW_TO_NHWC: (("N", "C", "HW"), (), ("src", "dst")),
+    OP_PACK_WEIGHTS: (("kind", "Co", "Ci", "kh", "kw"), (), ("w", "dst")),
+    OP_PACK_BATCH: (("n",), (), ("descs",)),                   # descs: device array of MnasPackDesc
+    OP_EVENT_RECORD: ((), (), ("event", "gate")),              # gate: HOST int, 0 = skip this record
+    OP_EVENT_WAIT: ((), (), ("event",)),
+    OP_PW_BWD: (("M", "Ci", "Co", "nparts", "gin_masked", "seg_px"), (),
+                _act("x") + _grad("dy") + ("w", "resid", "gin", "wpartial", "red_partial", "red_y", "red_bn", None, "w_fwd", "b_fwd")),
+    OP_POOL_ACT: (("N", "HW", "C"), (), _act("a") + ("out",)),
+    OP_POOL_BWD: (("N", "HW", "C"), (), ("gpool", "g")),
+    OP_DY_MAT: (("C",), ("rows",), _grad("dy") + ("out",)),
+    OP_BWD_POST: (("bn_nparts", "bn_C") + _post("w1") + _post("w2"), ("count",),
+                  ("bn_partial", "bnbuf", "dgamma", "dbeta", "w1.partial", "w1.grad", "w2.partial", "w2.grad")),
+    OP_TCONV_DGRAD: (("N", "Ho", "Wo", "Co", "Ci", "nparts"), (), ("dy", "w", "out", "stats", "red_y", "red_bn")),
+    OP_HEAD_LINEAR: (("N", "I", "O", "relu", "accumulate", "which"), (),       # which: 0 forward, 1 bwd_w, 2 bwd_x; no dropout
+                     ("x", "w", "b", "y", "dz", "dw", "db", "dx", "relu_mask")),
+    OP_SE_SCALE: (("N", "HW", "C"), (), _act("a") + ("u", "out")),
+    OP_SE_BWD_REDUCE: (("N", "HW", "C"), (), ("gs",) + _act("a") + ("u", "du", "scratch")),
+    OP_SE_BWD_APPLY: (("N", "HW", "C"), (), ("gs", "u", "dz", "out", "red_y", "red_bn", "red_partial")),
+    OP_SE_GATE: (("N", "C"), (), ("u", "gate")),
+    OP_SE_PROJ_FIN: (("N", "kseg", "Co", "Ci", "accumulate"), (), ("wpartial", "u", "w", "grad", "du")),
+    OP_SE_FC_FWD: (("N", "E", "R"), (), ("z", "w1", "b1", "w2", "b2", "hb", "u", "gate")),
+    OP_SE_FC_BWD: (("N", "E", "R", "accumulate"), (), ("du", "z", "hb", "w1", "w2", "dh", "dz", "dw1", "db1", "dw2", "db2")),
+}
+OP_STREAM_SLOT = 14
+_SLOT = {}       # opcode -> {name: ("i" | "d" | "p", index)}
+_GROUP = {}      # opcode -> {prefix: [member names]}   ("x" -> x.data, x.scale, x.shift)
+for _opc, _kinds in OP_SLOTS.items():
+    _SLOT[_opc], _GROUP[_opc] = {}, {}
+    for _kind, _names in zip("idp", _kinds):
+        for _k, _name in enumerate(_names):
+            if _name is None:
+                continue
+            if _name in _SLOT[_opc] or (_kind == "i" and _k >= OP_STREAM_SLOT):
+                raise ValueError("OP_SLOTS[%d]: bad slot %s" % (_opc, _name))
+            _SLOT[_opc][_name] = (_kind, _k)
+            if "." in _name:
+                _GROUP[_opc].setdefault(_name.split(".")[0], []).append(_name)
+
+
+def slot(opcode, name):
+    """index of the named slot in its array (i, d or p)"""
+    return _SLOT[opcode][name][1]
+
+
+def set_op(o, opcode, stream=0, **fields):
+    """Fill a zeroed MnasOp by slot name (OP_SLOTS).  Pointer slots take a tensor, an address or None.  A group (x=, dy=, act=,
+    w1=, ...) takes an object with act_ptrs(), a NamedTuple whose fields are the group's members, or one value per member.
+    Unknown and doubly given names raise."""
+    slots, oi, od, op = _SLOT[opcode], o.i, o.d, o.p
+    o.opcode, oi[OP_STREAM_SLOT] = opcode, stream
+    for name, v in fields.items():
+        where = slots.get(name)
+        if where is None:
+            members = _GROUP[opcode].get(name)
+            if members is None:
+                raise TypeError("opcode %d: unknown slot %s" % (opcode, name))
+            if hasattr(v, "_asdict"):
+                v = [getattr(v, m.split(".")[1]) for m in members]
+            elif hasattr(v, "act_ptrs"):
+                v = v.act_ptrs()
+            if len(v) != len(members) or any(m in fields for m in members):
+                raise TypeError("opcode %d: group %s takes %d values, once" % (opcode, name, len(members)))
+            set_op(o, opcode, stream, **dict(zip(members, v)))
+            continue
+        kind, k = where
+        if kind == "i":
+            oi[k] = v           # (ctypes converts and range-checks)
+        elif kind == "d":
+            od[k] = v
+        else:
+            op[k] = (v if v is None or type(v) is int else v.data_ptr()) or None
+    return o
+
+
+def op_field(o, name):
+    kind, k = _SLOT[o.opcode][name]
+    return getattr(o, kind)[k]
+
+
+def op_ints(o):
+    """the op's named integers, in slot order"""
+    return tuple(int(v) for v in o.i[:len(OP_SLOTS[o.opcode][0])])
+
+
 # every symbol include/mnas.h declares: (name, restype, argtypes)
 class MnasHeadLinear(C.Structure):
     _fields_ = [("N", C.c_int32), ("I", C.c_int32), ("O", C.c_int32), ("relu", C.c_int32), ("accumulate", C.c_int32),

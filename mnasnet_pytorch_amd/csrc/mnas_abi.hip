@@ -48,34 +48,8 @@ extern "C" int64_t mnas_workspace_bytes(int kind, int n, int c, int k) {
     }
 }
 
-// Field use per opcode (i = op.i, d = op.d, p = op.p):
-//  CONV_GEMM        i: mode,N,Hi,Wi,Ci,Ho,Wo,Co,kh,kw,stride,pad,nparts
-//                   p: act.data,act.scale,act.shift, grad.g,grad.y,grad.coef, w,bias,resid,out,stats, red_y,red_bn
-//  CONV_WGRAD       i: N,Hi,Wi,Ci,Ho,Wo,Co,kh,kw,stride,pad,nsplit   p: x.data,x.scale,x.shift, dy.g,dy.y,dy.coef, partial
-//  WGRAD_FINALIZE   i: nsplit,Co,Ci,taps,accumulate                  p: partial,grad
-//  DW_FWD           i: N,H,W,C,k,nparts,stride  p: in.data,in.scale,in.shift, w,bias,out,stats
-//  DW_BWD           i: N,H,W,C,k,nparts,phase,stride,g_masked p: x.data,x.scale,x.shift, dy.g,dy.y,dy.coef, w,gin,wpartial, red_bn,red_partial
-//  DW_WGRAD_FINALIZE i: nparts,C,k,accumulate p: wpartial,grad
-//  STEM_FWD         i: N,H,W,Ho,Wo,Co,nparts,in_u8 p: x,w,bias,out,stats,in_affine
-//  STEM_WGRAD       i: N,H,W,Ho,Wo,Co,nparts,in_u8 p: x, dy.g,dy.y,dy.coef, partial,in_affine
-//  BN_FWD_FINALIZE  i: nparts,C,training  d: count,momentum,eps   p: partial,gamma,beta,rmean,rvar,nbt,bnbuf
-//  BN_BWD_REDUCE    i: C,nparts           d: rows                 p: g,y,bnbuf,partial
-//  BN_BWD_FINALIZE  i: nparts,C,accumulate d: count               p: partial,bnbuf,dgamma,dbeta
-//  ADD_ACT          i: C,HW               d: rows                 p: a.data,a.scale,a.shift, b.data,b.scale,b.shift, out_bf16,out_nchw
-//  NCHW_TO_NHWC     i: N,C,HW                                     p: src,dst
-//  PACK_WEIGHTS     i: kind,Co,Ci,kh,kw                           p: w,dst
-//  PACK_BATCH       i: n                                          p: descs (device array of MnasPackDesc)
-//  POOL_ACT         i: N,HW,C                                     p: a.data,a.scale,a.shift, out
-//  POOL_BWD         i: N,HW,C                                     p: gpool, g
-//  DY_MAT           i: C                  d: rows                 p: g,y,coef,out
-//  BWD_POST         i: bn_nparts,bn_C, w1{nsplit,Co,Ci,taps,dw,level}, w2{...}   d: count
-//                   p: bn_partial,bnbuf,dgamma,dbeta, w1.partial,w1.grad, w2.partial,w2.grad
-//  TCONV_DGRAD      i: N,Ho,Wo,Co,Ci,nparts                       p: dy,w,out,stats,red_y,red_bn
-//  HEAD_LINEAR      i: N,I,O,relu,accumulate,which   p: x,w,b,y,dz,dw,db,dx,relu_mask        (no dropout in launch lists)
-//  SE_SCALE         i: N,HW,C                      p: a.data,a.scale,a.shift, u, out
-//  SE_BWD_REDUCE    i: N,HW,C                      p: gs, a.data,a.scale,a.shift, u, du, scratch
-//  SE_BWD_APPLY     i: N,HW,C                      p: gs, u, dz, out, red_y, red_bn, red_partial
-//  PW_BWD           i: M,Ci,Co,nparts   p: x.data,x.scale,x.shift, dy.g,dy.y,dy.coef, w,resid,gin,wpartial, red_partial,red_y,red_bn
+// What each slot of op.i / op.d / op.p means per opcode: OP_SLOTS in mnasnet_pytorch_amd/_lib.py, the one table, which
+// tests/test_abi_cpu.py holds to the indices read below (i[14]: the stream, mnas_run_ops_multi).
 static int run_one(const MnasOp& o, void* stream) {
     const int32_t* i = o.i;
     void* const* p = o.p;

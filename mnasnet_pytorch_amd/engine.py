@@ -1,4 +1,4 @@
-"""Execution engine: compiles a subtree of the drop-in modules (mnasnet.py) into a static PROGRAM of HIP
+"""Execution engine: compiles (launch_plan.py) a subtree of the drop-in modules (mnasnet.py) into a static PROGRAM of HIP
 kernel launches (include/mnas.h) per (batch, height, width, mode) and runs it with ONE host->library call
 per forward / per backward segment (mnas_run_ops_multi: main stream + an OPTIONAL side stream for weight-gradient kernels,
 Engine.use_side_stream).
@@ -27,16 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-
-# igemm layers with fewer output pixels than this get one tile per workgroup (the 7x7 stage: 98 persistent workgroups of
-# two tiles leave most of the 256 CUs idle; measured -23..-35 % per launch there, +17..+37 % on the 14x14 stage)
-_SMALL_M = 20000
-_STATS_PARTS = 2048          # persistent pixel-workgroups for conv kernels / rows of the stats scratch
-_STEM_WGRAD_PARTS_MAX = 768  # upper bound of mnas_stem_parts(1, ...) (csrc/mnas_stem.hip): sizes the partial-slab scratch
-
-
-def _cdiv(a, b):
-    return (a + b - 1) // b
+from .launch_plan import LaunchPlan, _STATS_PARTS, _STEM_WGRAD_PARTS_MAX, _cdiv, se_segments_per_image  # noqa: F401  (re-exported)
 
 
 class _ConvInfo:
@@ -85,23 +76,6 @@ class _SEInfo:
         self.gslice = {}
 
 
-def se_segments_per_image(N, HW, tile, slices, max_slabs, resident=512):
-    """Workgroups per image (a divisor of HW, so that no segment straddles two images) for the segment-mode backward of a
-    squeeze-excite project conv: the divisor with the least (ragged-last-tile waste) x (idle share of the last round of `resident`
-    workgroups), ties to the smaller one; 0 if no divisor keeps the N*d weight-gradient slabs within `max_slabs` / 4096."""
-    best = None
-    for d in range(1, 65):
-        if HW % d or N * d > 4096 or N * d > max_slabs:
-            continue
-        seg = HW // d
-        waste = _cdiv(seg, tile) * tile / seg            # pixel slots per pixel (ragged last tile of a segment)
-        rounds = N * d * slices / float(resident)        # two resident workgroups per CU
-        cost = waste * _cdiv(N * d * slices, resident) / rounds
-        if best is None or cost < best[0] - 1e-9:
-            best = (cost, d)
-    return best[1] if best is not None else 0
-
-
 def _trace(root, se_map=None):
     """Flatten a module subtree into steps: ("conv", ConvBlock, stage) / ("block", [e,d,p], stage).  se_map (optional dict)
     receives id(expand ConvBlock) -> SqueezeExcite module for blocks that carry one."""
@@ -130,742 +104,15 @@ def _trace(root, se_map=None):
     return [(op, m, 0 if st is None else st) for op, m, st in steps]
 
 
-class _Act:
-    """A (possibly virtual) activation: value = relu(scale*data+shift) if bn is not None else data."""
-    __slots__ = ("data", "bn", "H", "W", "C", "gate")
-
-    def __init__(self, data, bn, H, W, C_, gate=None):
-        self.data, self.bn, self.H, self.W, self.C = data, bn, H, W, C_
-        self.gate = gate         # squeeze-excite applied on load: fp32 [N][C] multiplier on top of the virtual activation
-
-    def act_ptrs(self):
-        if self.bn is None:
-            return [self.data.data_ptr(), None, None]
-        return [self.data.data_ptr(), self.bn.data_ptr(), self.bn.data_ptr() + 4 * self.C]
-
-
-class _OpList:
-    def __init__(self, eng=None, tag=""):
-        self.items = []
-        self.eng, self.tag = eng, tag
-
-    def add(self, opcode, ints=(), dbls=(), ptrs=(), stream=0):
-        """stream: 0 = main (torch's current stream), 1 = the engine's side stream (weight-gradient work)"""
-        prof = (self.eng is not None and self.eng.profile_opcodes and opcode in self.eng.profile_opcodes
-                and (self.eng.profile_filter is None or self.eng.profile_filter(opcode, tuple(ints))))
-        if prof:
-            ev0, ev1 = self.eng.new_event(), self.eng.new_event()
-            gate = C.addressof(self.eng.profile_gate)          # host int: 0 = these two records are skipped (Engine.profile_gate)
-            self.items.append((L.OP_EVENT_RECORD, [], [], [ev0, gate], stream))
-        self.items.append((opcode, list(ints), list(dbls), list(ptrs), stream))
-        idx = len(self.items) - 1
-        if prof:
-            self.items.append((L.OP_EVENT_RECORD, [], [], [ev1, gate], stream))
-            self.eng.profile_events.append(((self.tag, opcode, tuple(ints)), ev0, ev1))
-        return idx
-
-    def fork(self):
-        """side stream may start from here: it waits for everything enqueued on main so far"""
-        ev = self.eng.new_event()
-        self.add(L.OP_EVENT_RECORD, [], [], [ev], 0)
-        self.add(L.OP_EVENT_WAIT, [], [], [ev], 1)
-
-    def join(self):
-        """main waits for everything enqueued on the side stream so far"""
-        ev = self.eng.new_event()
-        self.add(L.OP_EVENT_RECORD, [], [], [ev], 1)
-        self.add(L.OP_EVENT_WAIT, [], [], [ev], 0)
-
-    def build(self):
-        arr = (L.MnasOp * max(1, len(self.items)))()
-        for n, (opc, ints, dbls, ptrs, stream) in enumerate(self.items):
-            o = arr[n]
-            o.opcode = opc
-            o.i[14] = stream
-            for j, v in enumerate(ints):
-                o.i[j] = int(v)
-            for j, v in enumerate(dbls):
-                o.d[j] = float(v)
-            for j, v in enumerate(ptrs):
-                o.p[j] = v if v else None
-        return arr, len(self.items)
-
-
-class Program:
-    """All buffers + launch lists for one (N, H, W, training, need_dx) configuration."""
+class Program(LaunchPlan):
+    """launch_plan.LaunchPlan (all buffers + launch lists of one (N, H, W, training, need_dx) configuration) and its run-time half:
+    the run-time pointers are patched into the lists, which are launched per op or replayed as hipGraphs."""
 
     def __init__(self, eng: "Engine", N, H, W, training, need_dx, pooled=False, in_u8=False):
-        self.eng, self.N, self.H, self.W, self.training, self.need_dx = eng, N, H, W, training, need_dx
-        self.pooled = pooled
-        self.in_u8 = bool(in_u8)
-        # fused input pipeline of the stem (Engine.set_input_normalization): per-plane affine, uint8 images
-        aff = eng.input_affine(self.in_u8)
-        self._aff_ptr = aff.data_ptr() if aff is not None else None
-        if self.in_u8 and aff is None:
-            raise RuntimeError("uint8 images need Engine.set_input_normalization(mean, std)")
-        self.busy = False
-        dev = eng.device
-        self.keep = []                      # tensors owned by this program
-        lib = eng.lib
-
-
-
-        fwd = self._fwd = _OpList(eng, "fwd")
-        # dy plane (Ho, Wo) of every stride-2 dense conv in THIS program: the transposed-conv input gradient is picked per plane
-        # (rectangular clusters, 192-px inputs ... get the form whenever the library has it for their plane)
-        self._tconv_ok = {}
-        Ht, Wt = H, W
-        for op, m, stage in eng.steps:
-            for cb in ([m] if op == "conv" else m):
-                ci = eng.info[id(cb)]
-                Ho_, Wo_ = ci.out_hw(Ht, Wt)
-                if eng.use_tconv and eng.materialize_dy and getattr(ci, "w_tconv", None) is not None and Ht == 2 * Ho_ and Wt == 2 * Wo_:
-                    self._tconv_ok[id(ci)] = bool(lib.mnas_tconv_supported(Ho_, Wo_, ci.cout, ci.cin)) and \
-                        lib.mnas_tconv_parts(N, Ho_, Wo_, ci.cout, ci.cin) > 0
-                Ht, Wt = Ho_, Wo_
-        # ---- weight packing (once per forward; weights change every optimizer step): one batched launch
-        descs = []
-        for ci in eng.convs:
-            w = ci.mod.conv.weight
-            if ci.kind in ("pw", "dense"):
-                descs.append((w.data_ptr(), ci.w_fwd.data_ptr(), L.PACK_FWD, ci.cout, ci.cin, ci.k * ci.k))
-                if training:
-                    descs.append((w.data_ptr(), ci.w_dgrad.data_ptr(), L.PACK_DGRAD, ci.cout, ci.cin, ci.k * ci.k))
-                    if self._tconv_ok.get(id(ci)):
-                        descs.append((w.data_ptr(), ci.w_tconv.data_ptr(), L.PACK_TCONV, ci.cout, ci.cin, 9))
-            elif ci.kind == "dw":
-                descs.append((w.data_ptr(), ci.w_fwd.data_ptr(), L.PACK_DW, ci.cout, 1, ci.k * ci.k))
-            else:  # stem: [Co][27] viewed as a 1x1 conv over 27 "channels"
-                descs.append((w.data_ptr(), ci.w_fwd.data_ptr(), L.PACK_FWD, ci.cout, 27, 1))
-        host = (L.MnasPackDesc * len(descs))()
-        for n_, (wp, dp, kind, co, cin_, taps) in enumerate(descs):
-            host[n_].w, host[n_].dst, host[n_].kind, host[n_].Co, host[n_].Ci, host[n_].taps = wp, dp, kind, co, cin_, taps
-        raw = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(dev)
-        self.keep.append(raw)
-        fwd.add(L.OP_PACK_BATCH, [len(descs)], [], [raw.data_ptr()])
-
-        steps = eng.steps
-        first_kind = eng.info[id(steps[0][1] if steps[0][0] == "conv" else steps[0][1][0])].kind
-        self.x_is_image = first_kind == "stem"
-        self.patch_x = []       # (op index, pointer slot) receiving the input pointer
-        records = self._records = []   # forward applications, for the backward builder
-        Hc, Wc = H, W
-        if self.x_is_image:
-            cur = None          # the stem reads the fp32 NCHW input directly
-        else:
-            Cin = eng.info[id(steps[0][1] if steps[0][0] == "conv" else steps[0][1][0])].cin
-            xb = self._new((N, H, W, Cin))
-            j = fwd.add(L.OP_NCHW_TO_NHWC, [N, Cin, H * W], [], [None, xb.data_ptr()])
-            self.patch_x.append((j, 0))
-            cur = _Act(xb, None, H, W, Cin)
-        self.in_channels = 3 if self.x_is_image else cur.C
-
-
-
-
-
-        self._se_records = {}    # record index of a project conv -> its block's squeeze-excite tensors
-        step_records = []
-        for op, m, stage in steps:
-            start = len(records)
-            if op == "conv":
-                ci = eng.info[id(m)]
-                cur = self._conv_fwd(ci, cur, Hc, Wc)
-                Hc, Wc = cur.H, cur.W
-                step_records.append(("conv", stage, start, None, None))
-            else:
-                a_in = cur
-                cis = [eng.info[id(cb)] for cb in m]
-                se = eng.se_info.get(id(m[0]))
-                h = cur
-                for j_, ci_ in enumerate(cis):
-                    if j_ == 2 and se is not None:
-                        h = self._se_fwd(se, h, Hc, Wc, ci_)
-                    h = self._conv_fwd(ci_, h, Hc, Wc)
-                r = self._new((N, Hc, Wc, a_in.C))
-                fwd.add(L.OP_ADD_ACT, [a_in.C, Hc * Wc], [float(N * Hc * Wc)],
-                        a_in.act_ptrs() + h.act_ptrs() + [r.data_ptr(), None])
-                cur = _Act(r, None, Hc, Wc, a_in.C)
-                step_records.append(("block", stage, start, a_in, cur))
-        # ---- features output: fp32 NCHW (classifiers.py:109 consumes it), or, pooled, its global average [N][C]
-        # (AdaptiveAvgPool2d(1) fused with the last BatchNorm+ReLU: the feature map is never written)
-        if pooled:
-            self.out_shape = (N, cur.C)
-            j = fwd.add(L.OP_POOL_ACT, [N, cur.H * cur.W, cur.C], [], cur.act_ptrs() + [None])
-            self.patch_out = (j, 3)
-        else:
-            self.out_shape = (N, cur.C, cur.H, cur.W)
-            j = fwd.add(L.OP_ADD_ACT, [cur.C, cur.H * cur.W], [float(N * cur.H * cur.W)],
-                        cur.act_ptrs() + [None, None, None, None, None])
-            self.patch_out = (j, 7)
-        self.fwd_ops, self.fwd_n = fwd.build()
-        self.final = cur
-
-        # ---- backward ------------------------------------------------------------------------------
-        self.bwd_segments = []      # [(stage, ops, n)]
-        self.patch_gout = None
-        self.patch_dx = None
-        self.patch_x_bwd = None
         self._graphs = {}
-        # what the launch lists were BUILT with (the capture decision in _run must not follow later changes of the engine's
-        # switches: a list with stream-1 fork/join pairs or live event records cannot be captured whatever the switches say now)
-        self._built_side = bool(eng.use_side_stream)
-        self._built_prof = bool(eng.profile_opcodes)
-        self._out_buf = None
-        self._gout_buf = None
-        self._x_buf = None
-        self._x_direct = None
-        if training:
-            self._build_backward(step_records, cur)
-
-    def _build_backward(self, step_records, cur):
-        """The backward launch lists, one per features.<stage> segment, from the forward's records (reverse order)."""
-        eng, lib, N, H, W, need_dx, pooled, records = self.eng, self.eng.lib, self.N, self.H, self.W, self.need_dx, self.pooled, self._records
-        self._seg_ops: Dict[int, _OpList] = {}
-        self._order: List[int] = []
-        seg_ops, order = self._seg_ops, self._order
-
-
-        last_stage = step_records[-1][1]
-        g_final = self._new((N, cur.H, cur.W, cur.C))
-        if pooled:
-            j = self._seg(last_stage).add(L.OP_POOL_BWD, [N, cur.H * cur.W, cur.C], [], [None, g_final.data_ptr()])
-        else:
-            j = self._seg(last_stage).add(L.OP_NCHW_TO_NHWC, [N, cur.C, cur.H * cur.W], [], [None, g_final.data_ptr()])
-        self.patch_gout = (last_stage, j, 0)
-
-        # ---- merged bookkeeping launches (mnas_bwd_post): the weight-gradient reductions of the main-stream kernel that just
-        # ran ride in the SAME launch as the next layer's BatchNorm-backward finalize (and the second level of a two-level
-        # reduction in the one after that), instead of 2-3 tiny dependent launches in every gap of the main stream
-        merge = eng.merge_post
-        self._pend = {"w1": None, "w2": None, "ops": None}
-        self._rot = 0
-        self._rot_bufs = [eng.scratch_wgrad2, eng.scratch_wgrad3, eng.scratch_wgrad4]
-
-
-
-
-
-
-
-
-
-        self._masked_g = set()       # data_ptr of gradient tensors stored masked (dz) by their producer
-        g = g_final
-        g_red = 0            # number of fused-reduce partial columns already written for the layer g belongs to
-        self.patch_x_bwd = None
-        for si in range(len(step_records) - 1, -1, -1):
-            kind, stage, start, a_in, a_out = step_records[si]
-            ops = self._seg(stage)
-            first = si == 0
-            # what produced the step's INPUT: a ConvBlock (virtual act) or a block's residual sum / the network input
-            if kind == "conv":
-                rec = records[start]
-                need = (not first) or need_dx
-                if rec[2] is not None and rec[2].bn is None and si > 0 and step_records[si - 1][0] == "block":
-                    # input is the previous block's materialised sum r: its gradient G feeds that block's project conv
-                    prev_p = records[step_records[si - 1][2] + 2]
-                    tgt = (prev_p[3].data, prev_p[3].bn)
-                else:
-                    tgt = self._target_of(rec[2])
-                g, g_red = self._conv_bwd(ops, rec, g, None, need, g_red, tgt)
-            else:
-                re_, rd, rp = records[start], records[start + 1], records[start + 2]
-                G = g                                   # grad wrt the block output (materialised sum)
-                se_rec = self._se_records.get(start + 2)
-                if se_rec is not None and se_rec[5]:
-                    # excitation on load: the project conv's backward runs on the UNGATED activation in segment mode; its
-                    # weight-gradient slabs give du and (gated) dW3 without a pass over gs / a2 (csrc/mnas_se.hip)
-                    gs_, du_ = self._conv_bwd_se_proj(ops, rp, G, g_red, se_rec)
-                    g2, c2 = self._se_bwd(ops, start + 2, gs_, du_)
-                else:
-                    g2, c2 = self._conv_bwd(ops, rp, G, None, True, g_red, self._target_of(rp[2]))
-                    if se_rec is not None:
-                        g2, c2 = self._se_bwd(ops, start + 2, g2)         # g2 becomes dL/d(activated depthwise output)
-                g1, c1 = self._conv_bwd(ops, rd, g2, None, True, c2, self._target_of(rd[2]))
-                need = (not first) or need_dx
-                if need:
-                    # expand dgrad (+ skip gradient fused in its epilogue) produces the gradient of the block INPUT:
-                    # either a virtual activation (producer conv) or the previous block's sum (-> its project conv)
-                    if a_in.bn is not None:
-                        tgt = self._target_of(a_in)
-                    elif si > 0 and step_records[si - 1][0] == "block":
-                        prev_p = records[step_records[si - 1][2] + 2]
-                        tgt = (prev_p[3].data, prev_p[3].bn)
-                    else:
-                        tgt = None
-                    g, g_red = self._conv_bwd(ops, re_, g1, G, True, c1, tgt)
-                else:
-                    self._conv_bwd(ops, re_, g1, None, False, c1, None)
-                    g, g_red = None, 0
-        if need_dx and not self.x_is_image:
-            Cin = self.in_channels
-            j = self._seg(step_records[0][1]).add(L.OP_ADD_ACT, [Cin, H * W], [float(N * H * W)],
-                                            [g.data_ptr(), None, None, None, None, None, None, None])
-            self.patch_dx = (step_records[0][1], j, 7)
-        self._flush_post()
-        built = {}
-        for st in order:
-            # the main stream waits for the side stream's weight gradients at the end of backward, and at the end of the
-            # stages somebody consumes right away (Trainer: the stage that completes gradient bucket 0); joining after every
-            # stage cost 0.1 ms/step of main-stream waits with nobody looking at the gradients
-            if eng.join_stages is None:
-                need = st == order[-1] or eng.on_stage_done is not None
-            else:
-                need = st == order[-1] or st in eng.join_stages
-            if eng.use_side_stream and need:
-                seg_ops[st].join()
-            built[st] = seg_ops[st].build()
-        self.bwd_segments = [(st,) + built[st] for st in order]
-        self._seg_index = {st: n for n, st in enumerate(order)}
-        # all segments as ONE list (graph mode without a stage-done callback: one hipGraphLaunch per backward instead of one per
-        # stage -- every graph boundary is ~9 us of idle GPU)
-        n_all = sum(built[st][1] for st in order)
-        self.bwd_all = (L.MnasOp * max(1, n_all))()
-        self.bwd_all_n, self._seg_off, k = n_all, {}, 0
-        for st in order:
-            arr, n = built[st]
-            self._seg_off[st] = k
-            for j in range(n):
-                C.memmove(C.byref(self.bwd_all, k * C.sizeof(L.MnasOp)), C.byref(arr, j * C.sizeof(L.MnasOp)), C.sizeof(L.MnasOp))
-                k += 1
-        if self.patch_x_bwd is not None:
-            ops_obj, idx, slot = self.patch_x_bwd
-            st = [s for s in order if seg_ops[s] is ops_obj][0]
-            self.patch_x_bwd = (st, idx, slot)
-        if self.patch_dx is not None and not isinstance(self.patch_dx[0], int):
-            ops_obj, idx, slot = self.patch_dx
-            self.patch_dx = ([s for s in order if seg_ops[s] is ops_obj][0], idx, slot)
-
-    def _new(self, shape, dtype=torch.bfloat16):
-        t = torch.empty(shape, dtype=dtype, device=self.eng.device)
-        self.keep.append(t)
-        return t
-
-    def _bnbuf(self, C_):
-        t = torch.zeros((L_BN_ROWS, C_), dtype=torch.float32, device=self.eng.device)
-        self.keep.append(t)
-        return t
-
-    def _conv_fwd(self, ci: _ConvInfo, a_in: Optional[_Act], Hi, Wi):
-        eng, lib, dev, N, H, W, training = self.eng, self.eng.lib, self.eng.device, self.N, self.H, self.W, self.training
-        new, bnbuf, fwd, records = self._new, self._bnbuf, self._fwd, self._records
-        Ho, Wo = ci.out_hw(Hi, Wi)
-        M = N * Ho * Wo
-        y = new((N, Ho, Wo, ci.cout))
-        bn = bnbuf(ci.cout)
-        conv, bnm = ci.mod.conv, ci.mod.bn
-        bias = conv.bias.data_ptr() if conv.bias is not None else None
-        nparts = lib.mnas_conv_gemm_parts(0, M, ci.cin, ci.cout, ci.k * ci.k) if ci.kind in ("pw", "dense") else -1
-        if nparts < 1:
-            nparts = max(1, min(eng.igemm_fwd_parts, _cdiv(M, 128 if M >= _SMALL_M else lib.mnas_conv_gemm_tile_pixels(M, ci.cout, ci.k * ci.k * ci.cin))))
-        if ci.kind == "dense":       # small maps: one image per workgroup (csrc/mnas_dimg.hip)
-            ip = lib.mnas_conv_img_parts(0, N, Hi, Wi, ci.cin, Ho, Wo, ci.cout, ci.k, ci.stride, ci.pad)
-            nparts = ip if ip > 0 else nparts
-        stats = eng.scratch_stats.data_ptr() if training else None
-        if ci.kind == "stem":
-            sp = lib.mnas_stem_parts(0, N, Hi, Wi, ci.cout)
-            if self._aff_ptr is not None and (sp < 1 or (training and lib.mnas_stem_parts(1, N, Hi, Wi, ci.cout) < 1)):
-                # the fused Normalize / uint8 load exists only in the band kernels (csrc/mnas_stem.hip)
-                raise NotImplementedError(
-                    "fused input normalisation needs the stem band kernels: 32 output channels and an image width that is a "
-                    "multiple of 4 (16 in training); got %dx%d, %d channels.  Normalise on the host or call "
-                    "set_input_normalization(None, None)" % (Hi, Wi, ci.cout))
-            nparts = sp if sp > 0 else nparts
-            j = fwd.add(L.OP_STEM_FWD, [N, Hi, Wi, Ho, Wo, ci.cout, nparts, 1 if self.in_u8 else 0], [],
-                        [None, ci.w_fwd.data_ptr(), bias, y.data_ptr(), stats, self._aff_ptr])
-            self.patch_x.append((j, 0))
-        elif ci.kind == "dw":
-            nlaunch = max(64, min(_STATS_PARTS, _cdiv(M * ci.cout, 256 * 16 * 2)))
-            # stride 2 = SepConv(reduce=True)'s depthwise conv (mnasnet.py:73-81): plain direct kernels (csrc/mnas_dw2.hip)
-            fwd.add(L.OP_DW_FWD, [N, Hi, Wi, ci.cout, ci.k, nlaunch, ci.stride], [],
-                    a_in.act_ptrs() + [ci.w_fwd.data_ptr(), bias, y.data_ptr(), stats])
-            nparts = lib.mnas_dw_rows(N, Hi, Wi, ci.cout, ci.k, nlaunch, 0 if ci.stride == 1 else 4)      # columns of the stats table
-            if nparts < 1:
-                raise RuntimeError("unsupported depthwise shape %s" % ((N, Hi, Wi, ci.cout, ci.k),))
-        else:
-            gate = [None, None, a_in.gate.data_ptr()] if a_in.gate is not None else []
-            fwd.add(L.OP_CONV_GEMM, [0, N, Hi, Wi, ci.cin, Ho, Wo, ci.cout, ci.k, ci.k, ci.stride, ci.pad, nparts], [],
-                    a_in.act_ptrs() + [None, None, None, ci.w_fwd.data_ptr(), bias, None, y.data_ptr(), stats] + gate)
-        fwd.add(L.OP_BN_FWD_FINALIZE, [nparts, ci.cout, 1 if training else 0], [float(M), bnm.momentum, bnm.eps],
-                [stats, bnm.weight.data_ptr(), bnm.bias.data_ptr(), bnm.running_mean.data_ptr(),
-                 bnm.running_var.data_ptr(), bnm.num_batches_tracked.data_ptr(), bn.data_ptr()])
-        out = _Act(y, bn, Ho, Wo, ci.cout)
-        records.append(("conv", ci, a_in, out, Hi, Wi))
-        return out
-
-    def _se_onload_kseg(self, p_ci: _ConvInfo, h2: _Act, Hi, Wi):
-        """Workgroups per image of the project conv's segment-mode backward when the excitation can be applied ON LOAD for this
-        block (Engine.se_on_load): forward = MnasConvGemm.gate, backward = mnas_pw_bwd on the ungated activation with
-        per-image weight-gradient slabs + mnas_se_proj_finalize.  0: keep the materialised a*s (k_se_scale) path."""
-        eng, lib, N = self.eng, self.eng.lib, self.N
-        HW, M, Ci, Co = Hi * Wi, self.N * Hi * Wi, p_ci.cin, p_ci.cout
-        if not eng.se_on_load or h2.bn is None or p_ci.kind != "pw" or not lib.mnas_conv_gemm_gate_ok(N, HW, Ci, Co):
-            return 0
-        if not self.training:
-            return 1
-        if M < eng.pw_fused_min_pixels or not lib.mnas_pw_bwd_supported(Ci, Co):
-            return 0
-        tile, slices = lib.mnas_pw_bwd_tile_pixels(Ci, Co), lib.mnas_pw_bwd_slices(Ci, Co)
-        return se_segments_per_image(N, HW, tile, slices, eng.scratch_wgrad2.numel() // (Co * Ci))
-
-    def _se_fwd(self, se: _SEInfo, h2: _Act, Hi, Wi, p_ci: _ConvInfo):
-        """squeeze-excite on the activated depthwise output (csrc/mnas_se.hip): pooled mean -> fc1+ReLU -> fc2 -> a2 * sigmoid.
-        Returns what the project conv reads: the MATERIALISED scaled activation, or (Engine.se_on_load, supported shapes) the
-        virtual activation with the excitation as a per-(image, channel) gate applied on load."""
-        eng, lib, dev, N, H, W, training = self.eng, self.eng.lib, self.eng.device, self.N, self.H, self.W, self.training
-        new, bnbuf, fwd, records = self._new, self._bnbuf, self._fwd, self._records
-        E_, R_ = se.channels, se.reduced
-        z = new((N, E_), torch.float32)
-        hb = new((N, R_), torch.float32)
-        u = new((N, E_), torch.float32)
-        m_ = se.mod
-        fwd.add(L.OP_POOL_ACT, [N, Hi * Wi, E_], [], h2.act_ptrs() + [z.data_ptr()])
-        kseg = self._se_onload_kseg(p_ci, h2, Hi, Wi)
-        gate = new((N, E_), torch.float32) if kseg else None
-        if eng.se_fused_mlp and lib.mnas_se_fc_supported(E_, R_):
-            # the whole excitation MLP (+ the gate table) in one launch (csrc/mnas_se.hip k_se_fc_fwd)
-            fwd.add(L.OP_SE_FC_FWD, [N, E_, R_], [], [z.data_ptr(), m_.fc1.weight.data_ptr(), m_.fc1.bias.data_ptr(), m_.fc2.weight.data_ptr(),
-                                                      m_.fc2.bias.data_ptr(), hb.data_ptr(), u.data_ptr(), gate.data_ptr() if kseg else None])
-        else:
-            fwd.add(L.OP_HEAD_LINEAR, [N, E_, R_, 1, 0, 0], [], [z.data_ptr(), m_.fc1.weight.data_ptr(), m_.fc1.bias.data_ptr(), hb.data_ptr()])
-            fwd.add(L.OP_HEAD_LINEAR, [N, R_, E_, 0, 0, 0], [], [hb.data_ptr(), m_.fc2.weight.data_ptr(), m_.fc2.bias.data_ptr(), u.data_ptr()])
-            if kseg:
-                fwd.add(L.OP_SE_GATE, [N, E_], [], [u.data_ptr(), gate.data_ptr()])
-        self._se_records[len(records)] = (se, h2, z, hb, u, kseg, gate)    # keyed by the record index of the project conv that follows
-        if kseg:
-            return _Act(h2.data, h2.bn, Hi, Wi, E_, gate)
-        a2s = new((N, Hi, Wi, E_))
-        fwd.add(L.OP_SE_SCALE, [N, Hi * Wi, E_], [], h2.act_ptrs() + [u.data_ptr(), a2s.data_ptr()])
-        return _Act(a2s, None, Hi, Wi, E_)
-
-    def _seg(self, stage):
-        if stage not in self._seg_ops:
-            self._seg_ops[stage] = _OpList(self.eng, "bwd")
-            self._order.append(stage)
-        return self._seg_ops[stage]
-
-    def _next_scratch(self):
-        b = self._rot_bufs[self._rot % 3]
-        self._rot += 1
-        return b
-
-    def _emit_post(self, ops: _OpList, bn=None):
-        pend = self._pend
-        w1, w2 = pend["w1"], pend["w2"]
-        pend["w1"] = pend["w2"] = None
-        if w1 is not None and w1[7] == 2:
-            pend["w2"] = w1[:7] + (3,)
-        if bn is None and w1 is None and w2 is None:
-            return
-        none = (None, None, 0, 0, 0, 0, 0, 0)
-        w1 = w1 or none
-        w2 = w2 or none
-        bn = bn or (None, None, None, None, 0, 0, 0.0)
-        ops.add(L.OP_BWD_POST, [bn[4], bn[5]] + list(w1[2:]) + list(w2[2:]), [bn[6]],
-                list(bn[:4]) + [w1[0], w1[1], w2[0], w2[1]], 0)
-        pend["ops"] = ops
-
-    def _flush_post(self):
-        pend = self._pend
-        while pend["w1"] is not None or pend["w2"] is not None:
-            self._emit_post(pend["ops"])
-
-    def _queue_wgrad(self, ops, partial, nsplit, Co_, Ci_, taps, dw, grad_ptr):
-        pend = self._pend
-        pend["w1"] = (partial, grad_ptr, nsplit, Co_, Ci_, taps, 1 if dw else 0, 1 if nsplit <= 256 else 2)
-        pend["ops"] = ops
-
-    def _conv_bwd(self, ops: _OpList, rec, g, resid, need_gin, g_reduced=False, red_target=None):
-        """Backward of one ConvBlock application.  g: bf16 grad wrt its activated output.
-        g_reduced: the producer of g already wrote this layer's BN-backward partial sums into
-        eng.scratch_red (fused epilogue) with `g_reduced` columns.  red_target: (y, bn, C) of the ConvBlock
-        whose activated output is THIS layer's input -- the dgrad epilogue then does that reduce.
-        Returns (gin, ncols) : bf16 grad wrt the (activated) input or None, and the number of partial
-        columns written for red_target (0 if not fused)."""
-        eng, lib, N, merge, pend, records = self.eng, self.eng.lib, self.N, self.eng.merge_post, self._pend, self._records
-        new = self._new
-        _, ci, a_in, out, Hi, Wi = rec
-        Ho, Wo, Co = out.H, out.W, ci.cout
-        M = N * Ho * Wo
-        gy = [g.data_ptr(), out.data.data_ptr(), out.bn.data_ptr()]
-        if g_reduced:
-            nred = g_reduced
-            red_buf = eng.scratch_red
-        else:
-            nred = max(1, min(1024, _cdiv(M * Co, 256 * 8 * 8)))
-            red_buf = eng.scratch_stats
-            ops.add(L.OP_BN_BWD_REDUCE, [Co, nred], [float(M)], gy[:2] + [out.bn.data_ptr(), red_buf.data_ptr()])
-        if merge:
-            if pend["ops"] is not None and pend["ops"] is not ops:
-                self._flush_post()               # a stage's gradients are complete inside its own launch list
-            self._emit_post(ops, (red_buf.data_ptr(), out.bn.data_ptr(), eng.gptr(ci, 2), eng.gptr(ci, 3), nred, Co, float(M)))
-        else:
-            ops.add(L.OP_BN_BWD_FINALIZE, [nred, Co, 1], [float(M)],
-                    [red_buf.data_ptr(), out.bn.data_ptr(), eng.gptr(ci, 2), eng.gptr(ci, 3)])
-        # the weight-gradient kernels only share READ-ONLY inputs (g, y, the dy coefficients just finalised, the
-        # forward activations) with the input-gradient chain: with Engine.use_side_stream they go to the side stream
-        gyd = gy
-        if ci.kind == "dense" and eng.materialize_dy:
-            # dense 3x3: every dy element is gathered 2.25-10 times by the input/weight-gradient kernels; form it once
-            dyb = new((N, Ho, Wo, Co))
-            ops.add(L.OP_DY_MAT, [Co], [float(M)], gy + [dyb.data_ptr()], 0)
-            gyd = [dyb.data_ptr(), None, None]
-        WS = 1 if (eng.use_side_stream and M <= eng.side_stream_max_pixels) else 0
-        if WS:
-            ops.fork()
-        gin, ncols = None, 0
-        rt = red_target if (red_target is not None and need_gin) else None
-        if ci.kind == "stem":
-            nsp = max(1, min(512, _cdiv(M, 1024)))
-            sp = lib.mnas_stem_parts(1, N, Hi, Wi, Co)
-            nsp = min(sp if sp > 0 else nsp, _STEM_WGRAD_PARTS_MAX)
-            if nsp * Co * 27 > eng.scratch_wgrad.numel():
-                raise RuntimeError("stem weight-gradient scratch too small (%d splits)" % nsp)
-            jx = ops.add(L.OP_STEM_WGRAD, [N, Hi, Wi, Ho, Wo, Co, nsp, 1 if self.in_u8 else 0], [],
-                         [None] + gy + [eng.scratch_wgrad.data_ptr(), self._aff_ptr], WS)
-            self.patch_x_bwd = (ops, jx, 0)
-            ops.add(L.OP_WGRAD_FINALIZE, [nsp, Co, 27, 1, 1], [], [eng.scratch_wgrad.data_ptr(), eng.gptr(ci, 0)], WS)
-            if need_gin:
-                # dL/d image (fp32 NCHW; csrc/mnas_stem.hip k_stem_dgrad): not on the training path, autograd completeness only
-                if self.in_u8:
-                    raise RuntimeError("a uint8 image has no gradient")
-                jd = ops.add(L.OP_STEM_DGRAD, [N, Hi, Wi, Ho, Wo, Co], [], gy + [ci.mod.conv.weight.data_ptr(), self._aff_ptr, None], 0)
-                self.patch_dx = (ops, jd, 5)
-        elif ci.kind == "dw" and ci.stride == 2:
-            # SepConv(reduce=True): two plain launches, no fused reduce (the producer of x runs its own mnas_bn_bwd_reduce)
-            nparts = max(64, min(eng.dw_bwd_parts, _cdiv(M * Co, 256 * 16 * 2)))
-            if g.data_ptr() in self._masked_g:
-                raise AssertionError("masked gradient handed to the stride-2 depthwise backward")
-            wrows = lib.mnas_dw_rows(N, Hi, Wi, Co, ci.k, nparts, 7)
-            if wrows < 1 or wrows * ci.k * ci.k * Co > eng.scratch_wgrad.numel():
-                raise RuntimeError("unsupported stride-2 depthwise shape %s" % ((N, Hi, Wi, Co, ci.k),))
-            dwp = a_in.act_ptrs() + gy + [ci.w_fwd.data_ptr(), None, eng.scratch_wgrad.data_ptr(), None, None]
-            ops.add(L.OP_DW_BWD, [N, Hi, Wi, Co, ci.k, nparts, 2, 2, 0], [], dwp, WS)              # weight gradient
-            ops.add(L.OP_DW_WGRAD_FINALIZE, [wrows, Co, ci.k, 1], [], [eng.scratch_wgrad.data_ptr(), eng.gptr(ci, 0)], WS)
-            if need_gin:
-                gin = new((N, Hi, Wi, ci.cin))
-                dwp = a_in.act_ptrs() + gy + [ci.w_fwd.data_ptr(), gin.data_ptr(), None, None, None]
-                ops.add(L.OP_DW_BWD, [N, Hi, Wi, Co, ci.k, nparts, 1, 2, 0], [], dwp, 0)           # input gradient
-        elif ci.kind == "dw":
-            nparts = max(64, min(eng.dw_bwd_parts, _cdiv(M * Co, 256 * 16 * 2)))
-            gin = new((N, Hi, Wi, ci.cin))
-            red = [None, None]
-            if rt is not None:
-                red = [rt[1].data_ptr(), eng.scratch_red.data_ptr()]
-                ncols = lib.mnas_dw_rows(N, Hi, Wi, Co, ci.k, nparts, 1 if ci.k in eng.dw_fused_k else 2)
-            wsc = (self._next_scratch() if merge else eng.scratch_wgrad2) if ci.k in eng.dw_fused_k else eng.scratch_wgrad     # fused: main stream
-            dwp = a_in.act_ptrs() + gy + [ci.w_fwd.data_ptr(), gin.data_ptr(), wsc.data_ptr()] + red
-            wrows = lib.mnas_dw_rows(N, Hi, Wi, Co, ci.k, nparts, 1 if ci.k in eng.dw_fused_k else 3)
-            if wrows < 1 or (rt is not None and ncols < 1):
-                raise RuntimeError("unsupported depthwise shape %s" % ((N, Hi, Wi, Co, ci.k),))
-            if ci.k in eng.dw_fused_k:
-                # one sweep: dgrad + wgrad (+ fused reduce); both partial tables have `wrows` rows
-                if rt is not None:
-                    ncols = wrows
-                # g written by a project conv's out-stage backward as dz = g*[s*y+t>0] (see below): dy-on-read skips the mask
-                gm = 1 if g.data_ptr() in self._masked_g else 0
-                if gm and rt is None:
-                    raise AssertionError("masked gradient handed to a depthwise backward without the fused reduce")
-                ops.add(L.OP_DW_BWD, [N, Hi, Wi, Co, ci.k, nparts, 0, 0, gm], [], dwp, 0)
-                if merge:
-                    self._queue_wgrad(ops, wsc.data_ptr(), wrows, Co, 1, ci.k * ci.k, True, eng.gptr(ci, 0))
-                else:
-                    ops.add(L.OP_DW_WGRAD_FINALIZE, [wrows, Co, ci.k, 1], [], [eng.scratch_wgrad2.data_ptr(), eng.gptr(ci, 0)], 0)
-            else:
-                if g.data_ptr() in self._masked_g:
-                    raise AssertionError("masked gradient handed to the two-launch depthwise backward")
-                ops.add(L.OP_DW_BWD, [N, Hi, Wi, Co, ci.k, nparts, 2], [], dwp, WS)          # weight gradient
-                ops.add(L.OP_DW_WGRAD_FINALIZE, [wrows, Co, ci.k, 1], [], [eng.scratch_wgrad.data_ptr(), eng.gptr(ci, 0)], WS)
-                ops.add(L.OP_DW_BWD, [N, Hi, Wi, Co, ci.k, nparts, 1], [], dwp, 0)           # input gradient
-        elif (ci.kind == "pw" and need_gin and M >= eng.pw_fused_min_pixels and lib.mnas_pw_bwd_supported(ci.cin, Co)
-              and not (M < eng.pw_split_max_pixels and resid is None and Co < ci.cin and Co <= 128
-                       and lib.mnas_conv_gemm_parts(1, M, Co, ci.cin, 1) > 0)):
-            # large-pixel-count 1x1 conv: ONE sweep produces the input gradient, the weight-gradient partials and the
-            # fused reduce (both former kernels stream the same g, y; see csrc/mnas_pwbwd.hip).  Main stream.
-            gin = new((N, Hi, Wi, ci.cin))
-            nparts = max(1, min(eng.pw_bwd_parts_large if M >= 800000 else (eng.pw_bwd_parts_mid if M >= 100000 else eng.pw_bwd_parts_small),
-                                _cdiv(M, 128 if max(ci.cin, Co) <= 80 else 64)))
-            red = [None, None, None]
-            if rt is not None:
-                red = [eng.scratch_red.data_ptr(), rt[0].data_ptr(), rt[1].data_ptr()]
-                ncols = nparts
-            wsc = self._next_scratch() if merge else eng.scratch_wgrad2
-            gyp, extra = gy, [None, None, None]
-            if eng.pw_recompute_y and (lib.mnas_pw_bwd_forms(ci.cin, Co) & 2):
-                # widening (expand) conv: dy-on-load's raw forward output is recomputed from the staged x tile on the matrix
-                # cores (bit-identical to the stored tensor) instead of being read: a third of the launch's reads
-                conv = ci.mod.conv
-                gyp = [gy[0], None, gy[2]]
-                extra = [None, ci.w_fwd.data_ptr(), conv.bias.data_ptr() if conv.bias is not None else None]
-            # project conv in front of a depthwise conv: the out-stage form stores the input gradient already masked with the
-            # depthwise conv's ReLU (the mask its fused reduce computes anyway); mnas_dw_bwd then skips re-deriving it per window column
-            masked = 0
-            if (eng.dw_masked_g and rt is not None and resid is None and a_in.bn is not None and rt[0] is a_in.data
-                    and (lib.mnas_pw_bwd_forms(ci.cin, Co) & 4) and self._feeds_fused_dw(a_in)):
-                masked = 1
-                self._masked_g.add(gin.data_ptr())
-            seg = 0
-            if eng.pw_bwd_segments and M >= 800000 and (lib.mnas_pw_bwd_forms(ci.cin, Co) & 4):
-                # the out-stage (project) convs of the 112x112 / 56x56 stages: contiguous pixel range per workgroup (segment mode of
-                # csrc/mnas_pwbwd.hip) and one resident round of workgroups instead of tiles strided over a 1024-wide grid:
-                # 48 -> 16 at 112x112 200 -> 189 us, 72 -> 24 at 56x56 87 -> 83 us (same call); the expand forms (3-4 resident
-                # workgroups per CU) and 240 -> 40 at 28x28 lose with it (16 -> 48: 155 -> 220 us at 512 segments)
-                tile = lib.mnas_pw_bwd_tile_pixels(ci.cin, Co)
-                nparts = max(1, min(nparts, eng.pw_bwd_segments))
-                seg = _cdiv(_cdiv(M, nparts), tile) * tile
-                nparts = _cdiv(M, seg)
-                if rt is not None:
-                    ncols = nparts
-            ops.add(L.OP_PW_BWD, [M, ci.cin, Co, nparts, masked, seg], [],
-                    a_in.act_ptrs() + gyp + [ci.w_dgrad.data_ptr(), resid.data_ptr() if resid is not None else None,
-                                             gin.data_ptr(), wsc.data_ptr()] + red + extra, 0)
-            if merge:
-                self._queue_wgrad(ops, wsc.data_ptr(), nparts, Co, ci.cin, 1, False, eng.gptr(ci, 0))
-            else:
-                ops.add(L.OP_WGRAD_FINALIZE, [nparts, Co, ci.cin, 1, 1], [], [eng.scratch_wgrad2.data_ptr(), eng.gptr(ci, 0)], 0)
-        else:
-            # pixel splits: as many as keep slabs x splits within the workgroup budget (rounding UP put 513-540 workgroups on the
-            # 512 resident slots of most launches: a second, nearly empty round)
-            slabs = lib.mnas_conv_wgrad_slabs(Co, ci.cin, ci.k * ci.k)
-            nsp = max(1, min(eng.wgrad_wgs // slabs, _cdiv(M, 256)))
-            # partial[nsp][Co][K] must fit the scratch _setup sized for 1024 workgroups (Engine.wgrad_wgs is public)
-            nsp = max(1, min(nsp, eng.scratch_wgrad.numel() // (Co * ci.cin * ci.k * ci.k)))
-            ops.add(L.OP_CONV_WGRAD, [N, Hi, Wi, ci.cin, Ho, Wo, Co, ci.k, ci.k, ci.stride, ci.pad, nsp], [],
-                    a_in.act_ptrs() + gyd + [eng.scratch_wgrad.data_ptr()], WS)
-            ops.add(L.OP_WGRAD_FINALIZE, [nsp, Co, ci.cin, ci.k * ci.k, 1], [], [eng.scratch_wgrad.data_ptr(), eng.gptr(ci, 0)], WS)
-            if need_gin:
-                gin = new((N, Hi, Wi, ci.cin))
-                Min = N * Hi * Wi
-                nparts = lib.mnas_conv_gemm_parts(1, Min, Co, ci.cin, ci.k * ci.k)
-                if nparts < 1:
-                    nparts = max(1, min(eng.igemm_dgrad_parts, _cdiv(Min, 128 if Min >= _SMALL_M else lib.mnas_conv_gemm_tile_pixels(Min, ci.cin, ci.k * ci.k * Co))))
-                tconv = (eng.use_tconv and ci.kind == "dense" and self._tconv_ok.get(id(ci), False) and gyd is not gy and resid is None
-                         and Hi == 2 * Ho and Wi == 2 * Wo)
-                if tconv:
-                    tp = lib.mnas_tconv_parts(N, Ho, Wo, Co, ci.cin)       # (-1: a form that needs a larger batch)
-                    tconv = tp > 0
-                    nparts = tp if tconv else nparts
-                if tconv:
-                    pass
-                elif ci.kind == "dense" and gyd is not gy and resid is None:
-                    ip = lib.mnas_conv_img_parts(1, N, Ho, Wo, Co, Hi, Wi, ci.cin, ci.k, ci.stride, ci.pad)
-                    nparts = ip if ip > 0 else nparts
-                red = [None, None, None]
-                if rt is not None:
-                    red = [eng.scratch_red.data_ptr(), rt[0].data_ptr(), rt[1].data_ptr()]
-                    ncols = nparts
-                if tconv:
-                    # stride-2 3x3: transposed convolution over the materialised dy (csrc/mnas_tconv.hip)
-                    ops.add(L.OP_TCONV_DGRAD, [N, Ho, Wo, Co, ci.cin, nparts], [],
-                            [gyd[0], ci.w_tconv.data_ptr(), gin.data_ptr(), red[0], red[1], red[2]])
-                else:
-                    ops.add(L.OP_CONV_GEMM, [1, N, Ho, Wo, Co, Hi, Wi, ci.cin, ci.k, ci.k, ci.stride, ci.pad, nparts], [],
-                            [None, None, None] + gyd + [ci.w_dgrad.data_ptr(), None,
-                                                       resid.data_ptr() if resid is not None else None,
-                                                       gin.data_ptr(), red[0], red[1], red[2]])
-        if ci.kind == "dw" and resid is not None:
-            raise AssertionError("residual add into a depthwise dgrad does not occur")
-        return gin, ncols
-
-    def _feeds_fused_dw(self, act: _Act):
-        """True if the ConvBlock that produced the virtual activation `act` is a depthwise conv whose backward runs as the fused
-        sweep (the only mnas_dw_bwd form that takes a masked gradient)."""
-        for rec in self._records:
-            if rec[3] is act or (rec[3].data is act.data and rec[3].bn is act.bn):
-                ci = rec[1]
-                # ... and carries the fused reduce (its own input is a virtual activation), the form g_masked exists for
-                return ci.kind == "dw" and ci.stride == 1 and ci.k in self.eng.dw_fused_k and rec[2] is not None and rec[2].bn is not None
-        return False
-
-    def _conv_bwd_se_proj(self, ops: _OpList, rec, g, g_reduced, se_rec):
-        """Backward of the project conv of a squeeze-excite block whose excitation is applied on load.  Returns (gs, du): the input
-        gradient wrt the GATED activation and dL/du (fp32 [N][E])."""
-        eng, lib, N, merge = self.eng, self.eng.lib, self.N, self.eng.merge_post
-        new = self._new
-        _, ci, a_in, out, Hi, Wi = rec
-        se, h2, z, hb, u, kseg = se_rec[:6]
-        Co, M, HW = ci.cout, N * Hi * Wi, Hi * Wi
-        gy = [g.data_ptr(), out.data.data_ptr(), out.bn.data_ptr()]
-        if g_reduced:
-            nred, red_buf = g_reduced, eng.scratch_red
-        else:
-            nred = max(1, min(1024, _cdiv(M * Co, 256 * 8 * 8)))
-            red_buf = eng.scratch_stats
-            ops.add(L.OP_BN_BWD_REDUCE, [Co, nred], [float(M)], gy[:2] + [out.bn.data_ptr(), red_buf.data_ptr()])
-        if merge:
-            if self._pend["ops"] is not None and self._pend["ops"] is not ops:
-                self._flush_post()
-            self._emit_post(ops, (red_buf.data_ptr(), out.bn.data_ptr(), eng.gptr(ci, 2), eng.gptr(ci, 3), nred, Co, float(M)))
-        else:
-            ops.add(L.OP_BN_BWD_FINALIZE, [nred, Co, 1], [float(M)],
-                    [red_buf.data_ptr(), out.bn.data_ptr(), eng.gptr(ci, 2), eng.gptr(ci, 3)])
-        gs = new((N, Hi, Wi, ci.cin))
-        du = new((N, ci.cin), torch.float32)
-        wsc = self._next_scratch() if merge else eng.scratch_wgrad2
-        ops.add(L.OP_PW_BWD, [M, ci.cin, Co, N * kseg, 0, HW // kseg], [],
-                h2.act_ptrs() + gy + [ci.w_dgrad.data_ptr(), None, gs.data_ptr(), wsc.data_ptr()] + [None] * 6, 0)
-        ops.add(L.OP_SE_PROJ_FIN, [N, kseg, Co, ci.cin, 1], [],
-                [wsc.data_ptr(), u.data_ptr(), ci.mod.conv.weight.data_ptr(), eng.gptr(ci, 0), du.data_ptr()], 0)
-        return gs, du
-
-    def _se_bwd(self, ops: _OpList, rec_index, gs, du=None):
-        """Backward of the squeeze-excite stage: gs = dL/d(a2 * s) from the project conv's input gradient -> dL/d a2, and the
-        SE parameters' gradients (accumulated into the flat buffer; shared blocks sum their applications).  du: dL/du when the
-        project conv's backward already produced it (excitation on load), else it is reduced here from (gs, a2)."""
-        eng, lib, N, merge, pend, records = self.eng, self.eng.lib, self.N, self.eng.merge_post, self._pend, self._records
-        new = self._new
-        se, h2, z, hb, u = self._se_records[rec_index][:5]
-        E_, R_ = se.channels, se.reduced
-        HWl = h2.H * h2.W
-        m_ = se.mod
-        dh = new((N, R_), torch.float32)
-        dzp = new((N, E_), torch.float32)
-        ga = new((N, h2.H, h2.W, E_))
-        if du is None:
-            du = new((N, E_), torch.float32)
-            sb = lib.mnas_se_scratch_bytes(N, HWl, E_)
-            if sb < 0:
-                raise RuntimeError("unsupported squeeze-excite shape %s" % ((N, HWl, E_),))
-            dup = new((sb // 4,), torch.float32)
-            ops.add(L.OP_SE_BWD_REDUCE, [N, HWl, E_], [], [gs.data_ptr()] + h2.act_ptrs() + [u.data_ptr(), du.data_ptr(), dup.data_ptr()], 0)
-        if eng.se_fused_mlp and lib.mnas_se_fc_supported(E_, R_):
-            # the MLP backward in one op (two kernels: per-image dh / dz, then the parameter gradients; csrc/mnas_se.hip)
-            ops.add(L.OP_SE_FC_BWD, [N, E_, R_, 1], [], [du.data_ptr(), z.data_ptr(), hb.data_ptr(), m_.fc1.weight.data_ptr(),
-                                                         m_.fc2.weight.data_ptr(), dh.data_ptr(), dzp.data_ptr(), eng.gptr(se, 0),
-                                                         eng.gptr(se, 1), eng.gptr(se, 2), eng.gptr(se, 3)], 0)
-        else:
-            self._se_mlp_bwd_unfused(ops, se, z, hb, du, dh, dzp)
-        # the BatchNorm2-backward reduce of the depthwise conv rides in the same pass (ga is its g; h2 = its raw output + bnbuf)
-        ncols = lib.mnas_se_bwd_apply_cols(N, HWl, E_)
-        fused = h2.bn is not None and 0 < ncols <= _STATS_PARTS
-        ops.add(L.OP_SE_BWD_APPLY, [N, HWl, E_], [],
-                [gs.data_ptr(), u.data_ptr(), dzp.data_ptr(), ga.data_ptr()] +
-                ([h2.data.data_ptr(), h2.bn.data_ptr(), eng.scratch_red.data_ptr()] if fused else [None, None, None]), 0)
-        return ga, (ncols if fused else 0)
-
-    def _se_mlp_bwd_unfused(self, ops, se, z, hb, du, dh, dzp):
-        """The excitation MLP's backward as four mnas_head_linear_* launches (Engine.se_fused_mlp = False: the A/B baseline)."""
-        eng, N, m_ = self.eng, self.N, se.mod
-        E_, R_ = se.channels, se.reduced
-        # fc2: dW2 += du^T hb, db2 += sum du ; dh = (du W2) * [hb > 0]
-        ops.add(L.OP_HEAD_LINEAR, [N, R_, E_, 0, 1, 1], [], [hb.data_ptr(), m_.fc2.weight.data_ptr(), None, None, du.data_ptr(),
-                                                            eng.gptr(se, 2), eng.gptr(se, 3)], 0)
-        ops.add(L.OP_HEAD_LINEAR, [N, R_, E_, 0, 0, 2], [], [hb.data_ptr(), m_.fc2.weight.data_ptr(), None, None, du.data_ptr(),
-                                                            None, None, dh.data_ptr(), hb.data_ptr()], 0)
-        # fc1: dW1 += dh^T z, db1 += sum dh ; dz = dh W1
-        ops.add(L.OP_HEAD_LINEAR, [N, E_, R_, 1, 1, 1], [], [z.data_ptr(), m_.fc1.weight.data_ptr(), None, None, dh.data_ptr(),
-                                                            eng.gptr(se, 0), eng.gptr(se, 1)], 0)
-        ops.add(L.OP_HEAD_LINEAR, [N, E_, R_, 1, 0, 2], [], [z.data_ptr(), m_.fc1.weight.data_ptr(), None, None, dh.data_ptr(),
-                                                            None, None, dzp.data_ptr(), None], 0)
-
-    @staticmethod
-    def _target_of(act: Optional[_Act]):
-        """(raw y tensor, bnbuf) of the ConvBlock that produced a VIRTUAL activation, else None."""
-        if act is None or act.bn is None:
-            return None
-        return (act.data, act.bn)
-
+        self.busy = False
+        self._out_buf = self._gout_buf = self._x_buf = self._x_direct = None
+        super().__init__(eng, N, H, W, training, need_dx, pooled, in_u8)
 
     # ------------------------------------------------------------------------------------------
     def _run(self, arr, n, what):
@@ -907,7 +154,7 @@ class Program:
 
     def destroy_graphs(self):
         """Destroy the captured graph executables -- after a device sync: one of them may still be executing."""
-        slots = [s for s in getattr(self, "_graphs", {}).values() if s["exec"] is not None]
+        slots = [s for s in self._graphs.values() if s["exec"] is not None]
         if not slots:
             return
         torch.cuda.synchronize(self.eng.device)
@@ -979,8 +226,6 @@ class Program:
         self.x_ref = None
         return dx
 
-
-L_BN_ROWS = 8
 _MAX_PROGRAMS_PER_SHAPE = 4     # forwards kept alive simultaneously per (N,H,W,mode): beyond this the caller is leaking graphs
 
 
@@ -1146,9 +391,9 @@ class Engine:
         self.profile_gate = C.c_int(1)   # 0: the bracketing event records of the compiled programs are skipped (read at run time by
                                          # mnas_run_ops: bench.py switches them on for the last step of a timed window only)
         self._events = []                # every HIP event handle the compiled programs own (destroyed with them)
-        first = self.steps[0][1] if self.steps[0][0] == "conv" else self.steps[0][1][0]
-        self.in_channels_hint = self.info[id(first)].cin
-        self.starts_with_stem = self.info[id(first)].kind == "stem"
+        self.first_conv = self.convs[0]      # (unique ConvBlocks are in first-use order)
+        self.in_channels_hint = self.first_conv.cin
+        self.starts_with_stem = self.first_conv.kind == "stem"
 
     # ---- device state ---------------------------------------------------------------------------
     def _signature(self):
@@ -1324,7 +569,7 @@ class Engine:
 
     def input_affine(self, u8: bool):
         """device float[2][3] (scale, shift) of the stem's fused input transform for float / uint8 images, or None"""
-        if getattr(self, "_in_norm", None) is None:
+        if self._in_norm is None:
             return None
         t = self._in_aff.get((u8, self.device))
         if t is None:
@@ -1399,7 +644,7 @@ class Engine:
         """pooled=True returns the global average of the features, [N, C] fp32 (AdaptiveAvgPool2d(1) + flatten fused in)."""
         self.check_input(x)
         track = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.params))
-        if x.dtype == torch.uint8 and self.starts_with_stem and getattr(self, "_in_norm", None) is not None:
+        if x.dtype == torch.uint8 and self.starts_with_stem and self._in_norm is not None:
             x = x.contiguous()              # uint8 images stay uint8: the stem converts and normalises on load
         else:
             x = x.float().contiguous()      # train.py:427 input.float()

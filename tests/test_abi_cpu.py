@@ -77,3 +77,32 @@ def test_finetune_pool_surface():
     assert all(p.requires_grad for p in m.features.parameters())
     with pytest.raises(ValueError):
         FineTuneModelPool(base, "mnasnet", 10, "nope")
+
+
+def test_slot_table_matches_run_one():
+    """_lib.OP_SLOTS names exactly the slots run_one() (csrc/mnas_abi.hip) reads, opcode by opcode; where run_one() fills a struct
+    member from a slot, the member's name is the slot's name.  i[14] is the stream of every op."""
+    from mnasnet_pytorch_amd import _lib
+    src = open(os.path.join(ROOT, "mnasnet_pytorch_amd", "csrc", "mnas_abi.hip")).read()
+    body = src[src.index("static int run_one("):]
+    body = body[:body.index("default:")]
+    body = re.sub(r"//[^\n]*|/\*.*?\*/", "", body, flags=re.S)
+    blocks = re.split(r"case MNAS_OP_([A-Z0-9_]+):", body)[1:]
+    seen = {}
+    for name, text in zip(blocks[0::2], blocks[1::2]):
+        opc = getattr(_lib, "OP_" + name)
+        assert opc not in seen, name
+        seen[opc] = name
+        i_names, d_names, p_names = _lib.OP_SLOTS[opc]
+        used = {"i": set(map(int, re.findall(r"\bi\[(\d+)\]", text))), "d": set(map(int, re.findall(r"\bo\.d\[(\d+)\]", text))),
+                "p": set(map(int, re.findall(r"\bp\[(\d+)\]", text)))}
+        for kind, names in (("i", i_names), ("d", d_names), ("p", p_names)):
+            assert used[kind] == {k for k, n in enumerate(names) if n is not None}, (name, kind)
+        assert _lib.OP_STREAM_SLOT == 14 and len(i_names) <= 14 and len(d_names) <= 4 and len(p_names) <= 16
+        # a.<member> = (cast)p[k];   (the C member `in` is `in_` in Python, as in the ctypes mirrors)
+        members = re.findall(r"\ba\.([\w.]+) = (?:\([^()]*\))?([ip])\[(\d+)\];", text)
+        for member, kind, k in members:
+            member = re.sub(r"^in\b", "in_", member)
+            assert {"i": i_names, "p": p_names}[kind][int(k)] == member, (name, kind, k)
+    assert set(seen) == set(_lib.OP_SLOTS), set(seen) ^ set(_lib.OP_SLOTS)
+    assert "i[14]" in src[src.index("mnas_run_ops_multi("):]          # ... which mnas_run_ops_multi reads as the stream

@@ -618,7 +618,11 @@ def test_dw_bwd_g_masked(shape):
 # 2.  the launches of the bench configuration's training step, replayed standalone with the production integers
 # =====================================================================================================================================
 _CENSUS_OPS = {L.OP_PW_BWD: "pw_bwd", L.OP_DW_BWD: "dw_bwd", L.OP_TCONV_DGRAD: "tconv_dgrad", L.OP_DY_MAT: "dy_mat"}
-_NINTS = {L.OP_PW_BWD: 6, L.OP_DW_BWD: 9, L.OP_TCONV_DGRAD: 6, L.OP_DY_MAT: 1}
+_FORM_SLOTS = {   # pointer slots (by their names in _lib.OP_SLOTS) whose presence selects a form
+    L.OP_PW_BWD: {"virt": "x.scale", "red": "red_partial", "resid": "resid", "w_fwd": "w_fwd", "dy.y": "dy.y", "b_fwd": "b_fwd"},
+    L.OP_DW_BWD: {"virt": "x.scale", "red": "red_partial", "gin": "gin", "wpartial": "wpartial", "dy.y": "dy.y"},
+    L.OP_TCONV_DGRAD: {"red": "stats"}, L.OP_DY_MAT: {"dy.y": "dy.y"},
+}
 
 
 def _census(prog):
@@ -629,19 +633,10 @@ def _census(prog):
             o = arr[j]
             if o.opcode not in _CENSUS_OPS:
                 continue
-            ints = tuple(int(v) for v in o.i[:_NINTS[o.opcode]])
+            ints = L.op_ints(o)
             if o.opcode == L.OP_DY_MAT:
-                ints = ints + (int(o.d[0]),)
-            p = o.p
-            if o.opcode == L.OP_PW_BWD:
-                flags = {"virt": bool(p[1]), "red": bool(p[10]), "resid": bool(p[7]), "w_fwd": bool(p[14]), "dy.y": bool(p[4]),
-                         "b_fwd": bool(p[15])}
-            elif o.opcode == L.OP_DW_BWD:
-                flags = {"virt": bool(p[1]), "red": bool(p[10]), "gin": bool(p[7]), "wpartial": bool(p[8]), "dy.y": bool(p[4])}
-            elif o.opcode == L.OP_TCONV_DGRAD:
-                flags = {"red": bool(p[3])}
-            else:
-                flags = {"dy.y": bool(p[1])}
+                ints = ints + (int(L.op_field(o, "rows")),)
+            flags = {k: bool(L.op_field(o, s)) for k, s in _FORM_SLOTS[o.opcode].items()}
             key = (o.opcode, ints, tuple(sorted(flags.items())))
             seen[key] = seen.get(key, 0) + 1
     return seen
@@ -747,7 +742,7 @@ def test_bench_config_backward_launches():
     distinct backward launches of the Trainer's Program, each replayed on its own with the production integers (N, shape, nparts,
     phase, flags, seg_px) on device-generated inputs, against fp64 references on the device and bit-identical to a second grid.
 
-    Expected from the engine code (engine.py Program._conv_bwd) and asserted: RECOMP (16->48 at 112^2, 24->72 at 56^2), gin_masked
+    Expected from the engine code (launch_plan.py LaunchPlan._conv_bwd) and asserted: RECOMP (16->48 at 112^2, 24->72 at 56^2), gin_masked
     + segment mode (48->16, 72->24: the project convs in front of fused depthwise sweeps at >= 800 k pixels), gin_masked without
     segments (240->40 at 28^2), g_masked fused depthwise sweeps with k = 3 and k = 5, k_tcx shapes (16->24 at 112^2, 24->40 at
     56^2: the 2x2-block GEMM over dy 56^2 / 28^2), k_tcr (96->192 at 14^2: dy 7x7x192), dy materialised for every dense 3x3."""

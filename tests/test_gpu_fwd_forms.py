@@ -696,14 +696,16 @@ def test_igemm_16m_pixels_split_vs_whole():
 # =====================================================================================================================================
 # 2.  the forward, weight-gradient, stem and glue launches of the bench configuration's training step, replayed standalone
 # =====================================================================================================================================
-_CENSUS = {L.OP_CONV_GEMM: ("conv_gemm", 13), L.OP_CONV_WGRAD: ("conv_wgrad", 12), L.OP_DW_FWD: ("dw_fwd", 7), L.OP_STEM_FWD: ("stem_fwd", 8),
-           L.OP_STEM_WGRAD: ("stem_wgrad", 8), L.OP_BN_BWD_REDUCE: ("bn_bwd_reduce", 2), L.OP_ADD_ACT: ("add_act", 2),
-           L.OP_POOL_ACT: ("pool_act", 3), L.OP_POOL_BWD: ("pool_bwd", 3)}
-_FLAGS = {   # pointer slots of mnas_run_ops (csrc/mnas_abi.hip) whose presence selects a form
-    L.OP_CONV_GEMM: {"virt": 1, "dy.y": 4, "bias": 7, "resid": 8, "stats": 10, "red": 11, "gate": 13},
-    L.OP_CONV_WGRAD: {"virt": 1, "dy.y": 4}, L.OP_DW_FWD: {"virt": 1, "bias": 4, "stats": 6},
-    L.OP_STEM_FWD: {"bias": 2, "stats": 4, "affine": 5}, L.OP_STEM_WGRAD: {"dy.y": 2, "affine": 5}, L.OP_BN_BWD_REDUCE: {},
-    L.OP_ADD_ACT: {"a.virt": 1, "b": 3, "b.virt": 4, "out": 6, "nchw": 7}, L.OP_POOL_ACT: {"virt": 1}, L.OP_POOL_BWD: {},
+_CENSUS = {L.OP_CONV_GEMM: "conv_gemm", L.OP_CONV_WGRAD: "conv_wgrad", L.OP_DW_FWD: "dw_fwd", L.OP_STEM_FWD: "stem_fwd",
+           L.OP_STEM_WGRAD: "stem_wgrad", L.OP_BN_BWD_REDUCE: "bn_bwd_reduce", L.OP_ADD_ACT: "add_act", L.OP_POOL_ACT: "pool_act",
+           L.OP_POOL_BWD: "pool_bwd"}
+_FORM_SLOTS = {   # pointer slots (by their names in _lib.OP_SLOTS) whose presence selects a form
+    L.OP_CONV_GEMM: {"virt": "act.scale", "dy.y": "grad.y", "bias": "bias", "resid": "resid", "stats": "stats", "red": "red_y",
+                     "gate": "gate"},
+    L.OP_CONV_WGRAD: {"virt": "x.scale", "dy.y": "dy.y"}, L.OP_DW_FWD: {"virt": "in_.scale", "bias": "bias", "stats": "stats"},
+    L.OP_STEM_FWD: {"bias": "bias", "stats": "stats", "affine": "in_affine"}, L.OP_STEM_WGRAD: {"dy.y": "dy.y", "affine": "in_affine"},
+    L.OP_BN_BWD_REDUCE: {}, L.OP_ADD_ACT: {"a.virt": "a.scale", "b": "b.data", "b.virt": "b.scale", "out": "out_bf16", "nchw": "out_nchw"},
+    L.OP_POOL_ACT: {"virt": "a.scale"}, L.OP_POOL_BWD: {},
 }
 
 
@@ -715,17 +717,17 @@ def _census(prog, seen, finalize):
         for j in range(n):
             o = arr[j]
             if o.opcode == L.OP_WGRAD_FINALIZE:
-                finalize.add(tuple(int(v) for v in o.i[:4]))
+                finalize.add(tuple(int(L.op_field(o, n)) for n in ("nsplit", "Co", "Ci", "taps")))
             if o.opcode == L.OP_BWD_POST:
-                for base in (2, 8):
-                    if o.i[base + 5] and not o.i[base + 4]:
-                        finalize.add((int(o.i[base]), int(o.i[base + 1]), int(o.i[base + 2]), int(o.i[base + 3])))
+                for w in ("w1.", "w2."):
+                    if L.op_field(o, w + "level") and not L.op_field(o, w + "dw"):
+                        finalize.add(tuple(int(L.op_field(o, w + n)) for n in ("nsplit", "Co", "Ci", "taps")))
             if o.opcode not in _CENSUS:
                 continue
-            ints = tuple(int(v) for v in o.i[:_CENSUS[o.opcode][1]])
+            ints = L.op_ints(o)
             if o.opcode in (L.OP_BN_BWD_REDUCE, L.OP_ADD_ACT):
-                ints = ints + (int(o.d[0]),)
-            flags = tuple(sorted((k, bool(o.p[s])) for k, s in _FLAGS[o.opcode].items()))
+                ints = ints + (int(L.op_field(o, "rows")),)
+            flags = tuple(sorted((k, bool(L.op_field(o, s))) for k, s in _FORM_SLOTS[o.opcode].items()))
             key = (o.opcode, ints, flags)
             seen[key] = seen.get(key, 0) + 1
 
@@ -1000,7 +1002,7 @@ def test_bench_config_forward_wgrad_stem_launches():
         opc, ints, flags = k[0], k[1], dict(k[2])
         if opc in (L.OP_STEM_FWD, L.OP_STEM_WGRAD):
             continue
-        form = _CENSUS[opc][0] + "".join(" " + n for n, v in sorted(flags.items()) if v)
+        form = _CENSUS[opc] + "".join(" " + n for n, v in sorted(flags.items()) if v)
         torch.cuda.synchronize()
         if opc == L.OP_CONV_GEMM:
             r, inst, info = _replay_gemm(ints, flags, gen)

@@ -576,18 +576,11 @@ def test_run_ops_batch():
     rm, rv = torch.zeros(Co, device="cuda"), torch.ones(Co, device="cuda")
     bn = torch.zeros(8, Co, device="cuda")
     ops = (L.MnasOp * 3)()
-    ops[0].opcode = L.OP_PACK_WEIGHTS
-    ops[0].i[0:5] = [L.PACK_FWD, Co, Ci, 1, 1]
-    ops[0].p[0], ops[0].p[1] = wd.data_ptr(), wp.data_ptr()
-    ops[1].opcode = L.OP_CONV_GEMM
-    ops[1].i[0:13] = [0, N, H, W, Ci, H, W, Co, 1, 1, 1, 0, nparts]
-    ops[1].p[0], ops[1].p[6], ops[1].p[9], ops[1].p[10] = xd.data_ptr(), wp.data_ptr(), out.data_ptr(), st.data_ptr()
-    ops[2].opcode = L.OP_BN_FWD_FINALIZE
-    ops[2].i[0:3] = [nparts, Co, 1]
-    ops[2].d[0], ops[2].d[1], ops[2].d[2] = float(N * H * W), 0.1, 1e-5
-    for j, t in enumerate((st, gamma, beta, rm, rv)):
-        ops[2].p[j] = t.data_ptr()
-    ops[2].p[5], ops[2].p[6] = None, bn.data_ptr()
+    L.set_op(ops[0], L.OP_PACK_WEIGHTS, kind=L.PACK_FWD, Co=Co, Ci=Ci, kh=1, kw=1, w=wd, dst=wp)
+    L.set_op(ops[1], L.OP_CONV_GEMM, mode=0, N=N, Hi=H, Wi=W, Ci=Ci, Ho=H, Wo=W, Co=Co, kh=1, kw=1, stride=1, pad=0, nparts=nparts,
+             act=(xd, None, None), w=wp, out=out, stats=st)
+    L.set_op(ops[2], L.OP_BN_FWD_FINALIZE, nparts=nparts, C=Co, training=1, count=float(N * H * W), momentum=0.1, eps=1e-5,
+             partial=st, gamma=gamma, beta=beta, rmean=rm, rvar=rv, nbt=None, bnbuf=bn)
     failed = C.c_int(-1)
     L.check(lib.mnas_run_ops(ops, 3, L.cur_stream(), C.byref(failed)), "run_ops")
     ref = F.conv2d(x, w)

@@ -806,3 +806,14 @@ def test_net_odd_sizes_and_batch_one(hw, n):
         coss.append(float((a @ b) / (a.norm() * b.norm() + 1e-30)))
     print(hw, n, "grad cosine vs mirror: min %.4f median %.4f" % (min(coss), float(np.median(coss))))
     assert np.median(coss) > 0.9
+
+
+def test_launch_plan_on_gpu_equals_cpu_fixture():
+    """The (2, 32, 32) training program of the default model, built on the GPU, is the plan tests/golden/launch_plans.txt.gz pins on
+    the CPU (tests/test_launch_plan_cpu.py): what the CPU test proves unchanged is what runs here."""
+    import make_launch_plan_golden as G
+    name = "ccf1_se0_train_2x32x32"
+    cfg = [c for n, _, c in G.configs() if n == name][0]
+    ops, sha, _ = G.read_fixture()[name]
+    lines = G.dump_config(cfg, torch.device("cuda:0"))
+    assert (G.count_ops(lines), G.digest(lines)) == (ops, sha)

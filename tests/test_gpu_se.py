@@ -265,7 +265,7 @@ def test_se_stage_vs_mirror(name):
     y = m(x)
     cot = C.cotangent(tuple(y.shape))
     (y * cot.cuda()).sum().backward()
-    on_load = [bool(r_[5]) for lst in m._engine().programs.values() for prog_ in lst for r_ in prog_._se_records.values()]
+    on_load = [bool(r_.kseg) for lst in m._engine().programs.values() for prog_ in lst for r_ in prog_._se_records.values()]
     assert on_load and all(v == on_load[0] for v in on_load)
     assert on_load[0] == name.endswith(("_n16", "_n64")), "the stage did not take the expected squeeze-excite path"
     r = M.run(prog, st, x0, True, cot, need_dx=True, se_on_load=(lambda *a: True) if on_load[0] else None)
@@ -304,7 +304,7 @@ def test_se_on_load_matches_materialised(name):
         (y * C.cotangent(tuple(y.shape)).cuda()).sum().backward()
         res[on] = (y.detach().cpu(), x.grad.cpu(), {k: v.grad.cpu() for k, v in m.named_parameters()})
         used = [r for lst in m._engine().programs.values() for prog_ in lst for r in prog_._se_records.values()]
-        assert used and all(bool(r[5]) == bool(on) for r in used), "the stage did not take the expected squeeze-excite path"
+        assert used and all(bool(r.kseg) == bool(on) for r in used), "the stage did not take the expected squeeze-excite path"
     assert torch.equal(res[True][0], res[False][0])
     assert rl2(res[True][1], res[False][1]) < 5e-2
     for k in res[True][2]:
