@@ -28,6 +28,7 @@
  *   row 1 shift  t = beta - mean*s        row 5 batch mean
  *   row 2 c1                              row 6 invstd
  *   row 3 c2                              row 7 (reserved)
+ *   Frozen statistics (mnas_bn_frozen_tables): rows 5, 6 hold the running mean and 1/sqrt(running_var+eps), c1 = s, c2 = c3 = 0.
  */
 #ifndef MNAS_H
 #define MNAS_H
@@ -345,6 +346,45 @@ typedef struct MnasBwdPost {
 } MnasBwdPost;
 int mnas_bwd_post(const MnasBwdPost* p, void* stream);
 
+/* ---- frozen BatchNorm statistics: training with the RUNNING buffers (model.train(); features.eval(): the fine-tuning recipe).
+ * y is normalised with (running_mean, running_var), which are constants of the step, so
+ *     dy = s*dz             bnbuf rows 2..4 = (s, +0, +0): the conv backward kernels run unchanged
+ *     dgamma += S2, dbeta += S1, dbias += s*S1      with S1 = sum dz, S2 = sum dz*(y*invstd - running_mean*invstd)
+ * (conv.bias has a gradient here: batch statistics cancel the bias, running statistics do not).  S1 / S2 are the partial tables the
+ * fused reduces and mnas_bn_bwd_reduce already produce from rows 0, 1, 5, 6.
+ *
+ * mnas_bn_frozen_tables: the whole coefficient block of `n` ConvBlock applications in ONE launch (`descs`: DEVICE array); they
+ * depend on parameters and buffers only, not on the batch.  Per channel, fp32, in the arithmetic of mnas_bn_fwd_finalize(training=0):
+ *     invstd = 1/sqrtf(running_var + eps), s = gamma*invstd, t = beta - running_mean*s
+ *     rows 0..6 = s, t, s, +0, +0, running_mean, invstd     (row 7 and the running buffers are not written) */
+typedef struct MnasBnFrozenDesc {
+    const float* gamma;
+    const float* beta;
+    const float* running_mean;
+    const float* running_var;
+    float*  bnbuf;           /* float[8][C] */
+    int32_t C;
+    float   eps;
+} MnasBnFrozenDesc;
+int mnas_bn_frozen_tables(const MnasBnFrozenDesc* descs, int n, void* stream);
+/* mnas_bn_bwd_finalize under frozen statistics: dgamma (+)= S2, dbeta (+)= S1, dbias (+)= s*S1 (formed in double from the double
+ * partial sums, rounded once); bnbuf (row 0 = s) is only read.  Any of the three gradient pointers may be NULL. */
+int mnas_bn_bwd_finalize_frozen(const float* partial, int nparts, int C, const float* bnbuf, float* dgamma, float* dbeta,
+                                float* dbias, int accumulate, void* stream);
+/* mnas_bwd_post under frozen statistics: the fields of MnasBwdPost (count is not used) + dbias.  The BatchNorm blocks do the three
+ * accumulations above and leave bnbuf alone; the weight-gradient tasks are those of mnas_bwd_post. */
+typedef struct MnasBwdPostFrozen {
+    const float* bn_partial; /* float[2][C][nparts] */
+    const float* bnbuf;
+    float* dgamma;
+    float* dbeta;
+    double count;
+    int32_t bn_nparts, bn_C;
+    MnasPostWgrad w1, w2;
+    float* dbias;
+} MnasBwdPostFrozen;
+int mnas_bwd_post_frozen(const MnasBwdPostFrozen* p, void* stream);
+
 /* ---- element-wise glue ------------------------------------------------------------------------------ */
 /* out = act(a) + act(b)   (b.data may be NULL -> out = act(a)); rows x C bf16.  The MBConv_block residual
  * (mnasnet.py:133).  If out_nchw_f32 != NULL the result is ALSO/INSTEAD written as fp32 NCHW (N,C,H,W)
@@ -631,6 +671,10 @@ int mnas_sgd_step(float* p, const float* g, float* momentum_buf, int64_t n, floa
 #define MNAS_OP_SE_FC_FWD 37        /* ABI 7: i = {N, E, R}; p = {z, W1, b1, W2, b2, hb, u, gate or NULL} */
 #define MNAS_OP_STEM_DGRAD 39       /* ABI 7: i = {N, H, W, Ho, Wo, Co}; p = {g, y, coef, w fp32, in_affine or NULL, dx} */
 #define MNAS_OP_SE_FC_BWD 38        /* ABI 7: i = {N, E, R, accumulate}; p = {du, z, hb, W1, W2, dh, dz, dW1, db1, dW2, db2} */
+/* frozen BatchNorm statistics (ABI 8, additive) */
+#define MNAS_OP_BN_FROZEN_BATCH 40          /* i = {n}; p = {descs: device array of MnasBnFrozenDesc} */
+#define MNAS_OP_BWD_POST_FROZEN 41          /* the slots of MNAS_OP_BWD_POST; p[8] = dbias */
+#define MNAS_OP_BN_BWD_FINALIZE_FROZEN 42   /* i = {nparts, C, accumulate}; p = {partial, bnbuf, dgamma, dbeta, dbias} */
 typedef struct MnasOp {
     int32_t opcode;
     int32_t i[15];

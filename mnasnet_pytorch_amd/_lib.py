@@ -66,6 +66,15 @@ class MnasBwdPost(C.Structure):
                 ("bn_nparts", C.c_int32), ("bn_C", C.c_int32), ("w1", MnasPostWgrad), ("w2", MnasPostWgrad)]
 
 
+class MnasBwdPostFrozen(C.Structure):
+    _fields_ = MnasBwdPost._fields_ + [("dbias", c_void_p)]
+
+
+class MnasBnFrozenDesc(C.Structure):
+    _fields_ = [("gamma", c_void_p), ("beta", c_void_p), ("running_mean", c_void_p), ("running_var", c_void_p), ("bnbuf", c_void_p),
+                ("C", C.c_int32), ("eps", c_float)]
+
+
 class MnasTconvDgrad(C.Structure):
     _fields_ = [("N", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32), ("Co", C.c_int32), ("Ci", C.c_int32),
                 ("nparts", C.c_int32), ("dy", c_void_p), ("w", c_void_p), ("out", c_void_p), ("stats", c_void_p),
@@ -122,6 +131,7 @@ OP_HEAD_LINEAR, OP_SE_SCALE, OP_SE_BWD_REDUCE, OP_SE_BWD_APPLY = 30, 31, 32, 33
 OP_SE_GATE, OP_SE_PROJ_FIN = 34, 35
 OP_SE_FC_FWD, OP_SE_FC_BWD = 37, 38
 OP_STEM_DGRAD = 39
+OP_BN_FROZEN_BATCH, OP_BWD_POST_FROZEN, OP_BN_BWD_FINALIZE_FROZEN = 40, 41, 42      # frozen BatchNorm statistics (include/mnas.h)
 PACK_FWD, PACK_DGRAD, PACK_DW, PACK_TCONV = 0, 1, 2, 3
 EINVAL = 10001      # MNAS_EINVAL
 ROUTE_PWX, ROUTE_PWS, ROUTE_PWF, ROUTE_PWD, ROUTE_C3R, ROUTE_DIMG, ROUTE_C3X, ROUTE_IGEMM = range(8)     # MNAS_ROUTE_*
@@ -172,6 +182,10 @@ OP_SLOTS = {
     OP_DY_MAT: (("C",), ("rows",), _grad("dy") + ("out",)),
     OP_BWD_POST: (("bn_nparts", "bn_C") + _post("w1") + _post("w2"), ("count",),
                   ("bn_partial", "bnbuf", "dgamma", "dbeta", "w1.partial", "w1.grad", "w2.partial", "w2.grad")),
+    OP_BWD_POST_FROZEN: (("bn_nparts", "bn_C") + _post("w1") + _post("w2"), ("count",),
+                         ("bn_partial", "bnbuf", "dgamma", "dbeta", "w1.partial", "w1.grad", "w2.partial", "w2.grad", "dbias")),
+    OP_BN_BWD_FINALIZE_FROZEN: (("nparts", "C", "accumulate"), (), ("partial", "bnbuf", "dgamma", "dbeta", "dbias")),
+    OP_BN_FROZEN_BATCH: (("n",), (), ("descs",)),              # descs: device array of MnasBnFrozenDesc
     OP_TCONV_DGRAD: (("N", "Ho", "Wo", "Co", "Ci", "nparts"), (), ("dy", "w", "out", "stats", "red_y", "red_bn")),
     OP_HEAD_LINEAR: (("N", "I", "O", "relu", "accumulate", "which"), (),       # which: 0 forward, 1 bwd_w, 2 bwd_x; no dropout
                      ("x", "w", "b", "y", "dz", "dw", "db", "dx", "relu_mask")),
@@ -336,6 +350,9 @@ SYMBOLS = {
     "mnas_tconv_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "mnas_tconv_parts": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "mnas_bwd_post": (c_int, [C.POINTER(MnasBwdPost), c_void_p]),
+    "mnas_bwd_post_frozen": (c_int, [C.POINTER(MnasBwdPostFrozen), c_void_p]),
+    "mnas_bn_bwd_finalize_frozen": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "mnas_bn_frozen_tables": (c_int, [c_void_p, c_int, c_void_p]),
     "mnas_dy_materialize": (c_int, [C.POINTER(MnasGradIn), c_int64, c_int, c_void_p, c_void_p]),
     "mnas_bn_bwd_finalize": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "mnas_add_act": (c_int, [C.POINTER(MnasActIn), C.POINTER(MnasActIn), c_int64, c_int, c_void_p, c_void_p, c_int,

@@ -46,6 +46,7 @@ class FineTuneModelPool(nn.Module):
         else:
             raise ValueError("Finetuning not supported on this architecture yet")
         self.input_norm_on_device = False     # see normalize_on_device()
+        self.bn_frozen = False                # see freeze_bn()
         self.fuse_pool = True        # see forward()
         self.native_head = True      # classifier on csrc/mnas_head.hip when it is a Dropout/Linear/ReLU chain
         self._head = None
@@ -80,6 +81,22 @@ class FineTuneModelPool(nn.Module):
             else:
                 eng.set_input_normalization(*want)
             eng._in_norm_key = want
+
+    def freeze_bn(self, enable=True):
+        """Train on frozen BatchNorm statistics: ``features`` stays in eval mode (BatchNorm normalises with its running buffers and
+        does not update them) while its weights -- and the classifier -- still train; the engine runs its frozen-statistics program
+        (engine.py).  What fine-tuning at small batch sizes needs (train.py:307-317 divides the batch by 4 at every growth step of
+        progressive resizing).  Module state like ``input_norm_on_device``: off by default, survives pickling / deepcopy and
+        ``model.train()`` (train.py:419 calls it every epoch).  Independent of freeze() / unfreeze(), which stop the weights."""
+        self.bn_frozen = bool(enable)
+        self.features.train(self.training and not self.bn_frozen)
+        return self
+
+    def train(self, mode=True):
+        super().train(mode)
+        if getattr(self, "bn_frozen", False):
+            self.features.eval()
+        return self
 
     def freeze(self):
         print("Features frozen")

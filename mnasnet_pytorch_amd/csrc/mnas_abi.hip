@@ -162,6 +162,20 @@ static int run_one(const MnasOp& o, void* stream) {
             a.w2 = {(float*)p[6], (float*)p[7], i[8], i[9], i[10], i[11], i[12], i[13]};
             return mnas_bwd_post(&a, stream);
         }
+        case MNAS_OP_BWD_POST_FROZEN: {
+            MnasBwdPostFrozen a = {};
+            a.bn_partial = (const float*)p[0]; a.bnbuf = (const float*)p[1]; a.dgamma = (float*)p[2]; a.dbeta = (float*)p[3];
+            a.count = o.d[0]; a.bn_nparts = i[0]; a.bn_C = i[1];
+            a.w1 = {(float*)p[4], (float*)p[5], i[2], i[3], i[4], i[5], i[6], i[7]};
+            a.w2 = {(float*)p[6], (float*)p[7], i[8], i[9], i[10], i[11], i[12], i[13]};
+            a.dbias = (float*)p[8];
+            return mnas_bwd_post_frozen(&a, stream);
+        }
+        case MNAS_OP_BN_BWD_FINALIZE_FROZEN:
+            return mnas_bn_bwd_finalize_frozen((const float*)p[0], i[0], i[1], (const float*)p[1], (float*)p[2], (float*)p[3],
+                                               (float*)p[4], i[2], stream);
+        case MNAS_OP_BN_FROZEN_BATCH:
+            return mnas_bn_frozen_tables((const MnasBnFrozenDesc*)p[0], i[0], stream);
         case MNAS_OP_TCONV_DGRAD: {
             MnasTconvDgrad a = {};
             a.N = i[0]; a.Ho = i[1]; a.Wo = i[2]; a.Co = i[3]; a.Ci = i[4]; a.nparts = i[5];

@@ -217,9 +217,11 @@ extern "C" int mnas_dy_materialize(const MnasGradIn* d, int64_t rows, int C, voi
 
 // dgamma, dbeta and the dy-on-load coefficients:
 //   dy = gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat)) = c1*dz + c2*y + c3
-template <int TPC>
+// FROZEN (running statistics, mnas_bn_frozen_tables wrote rows 0..6 in forward): dy = s*dz, so rows 2..4 stay as they are and
+// bnbuf is only read; the conv bias gets a gradient, dbias (+)= s*S1 -- in double from the double sum, rounded once like the other two.
+template <int TPC, bool FROZEN = false>
 __device__ __forceinline__ void bn_bwd_finalize_body(const float* __restrict__ partial, int nparts, int C, double count, float* bnbuf,
-                                                     float* dgamma, float* dbeta, int accumulate, int blk) {
+                                                     float* dgamma, float* dbeta, int accumulate, int blk, float* dbias = nullptr) {
     const int lane = threadIdx.x % TPC;
     const int c = (TPC == 256) ? blk : blk * 4 + (threadIdx.x >> 6);
     if (c >= C) return;
@@ -227,6 +229,7 @@ __device__ __forceinline__ void bn_bwd_finalize_body(const float* __restrict__ p
     // (loaded ahead of the partial sums: see k_bn_fwd_finalize)
     const float fs = bnbuf[0 * C + c], fmean = bnbuf[5 * C + c], finv = bnbuf[6 * C + c];
     const float dg0 = (dgamma && accumulate) ? dgamma[c] : 0.f, db0 = (dbeta && accumulate) ? dbeta[c] : 0.f;
+    const float dc0 = (FROZEN && dbias && accumulate) ? dbias[c] : 0.f;
 #endif
     double s1, s2;
     bn_partial_sums<TPC>(partial, nparts, C, c, s1, s2);
@@ -234,12 +237,17 @@ __device__ __forceinline__ void bn_bwd_finalize_body(const float* __restrict__ p
 #if !MNAS_FIN_HOIST
         const float fs = bnbuf[0 * C + c], fmean = bnbuf[5 * C + c], finv = bnbuf[6 * C + c];
         const float dg0 = (dgamma && accumulate) ? dgamma[c] : 0.f, db0 = (dbeta && accumulate) ? dbeta[c] : 0.f;
+        const float dc0 = (FROZEN && dbias && accumulate) ? dbias[c] : 0.f;
 #endif
         const double s = fs, mean = fmean, invstd = finv;
-        const double md = s1 / count, mx = s2 / count;
-        bnbuf[2 * C + c] = (float)s;
-        bnbuf[3 * C + c] = (float)(-s * invstd * mx);
-        bnbuf[4 * C + c] = (float)(s * (mean * invstd * mx - md));
+        if (FROZEN) {
+            if (dbias) dbias[c] = dc0 + (float)(s * s1);
+        } else {
+            const double md = s1 / count, mx = s2 / count;
+            bnbuf[2 * C + c] = (float)s;
+            bnbuf[3 * C + c] = (float)(-s * invstd * mx);
+            bnbuf[4 * C + c] = (float)(s * (mean * invstd * mx - md));
+        }
         if (dgamma) dgamma[c] = dg0 + (float)s2;
         if (dbeta) dbeta[c] = db0 + (float)s1;
     }
@@ -260,6 +268,57 @@ extern "C" int mnas_bn_bwd_finalize(const float* partial, int nparts, int C, dou
     else
         hipLaunchKernelGGL(k_bn_bwd_finalize<64>, dim3((C + 3) / 4), dim3(256), 0, (hipStream_t)stream, partial, nparts, C,
                            count, bnbuf, dgamma, dbeta, accumulate);
+    MNAS_CHECK_LAUNCH();
+    return MNAS_OK;
+}
+
+template <int TPC>
+__global__ __launch_bounds__(256) void k_bn_bwd_finalize_frozen(const float* __restrict__ partial, int nparts, int C,
+                                                                const float* bnbuf, float* dgamma, float* dbeta, float* dbias,
+                                                                int accumulate) {
+    bn_bwd_finalize_body<TPC, true>(partial, nparts, C, 1.0, const_cast<float*>(bnbuf), dgamma, dbeta, accumulate, blockIdx.x, dbias);
+}
+
+extern "C" int mnas_bn_bwd_finalize_frozen(const float* partial, int nparts, int C, const float* bnbuf, float* dgamma,
+                                           float* dbeta, float* dbias, int accumulate, void* stream) {
+    if (C <= 0 || nparts <= 0 || !partial || !bnbuf) return MNAS_EINVAL;
+    if (nparts > 256)
+        hipLaunchKernelGGL(k_bn_bwd_finalize_frozen<256>, dim3(C), dim3(256), 0, (hipStream_t)stream, partial, nparts, C,
+                           bnbuf, dgamma, dbeta, dbias, accumulate);
+    else
+        hipLaunchKernelGGL(k_bn_bwd_finalize_frozen<64>, dim3((C + 3) / 4), dim3(256), 0, (hipStream_t)stream, partial, nparts, C,
+                           bnbuf, dgamma, dbeta, dbias, accumulate);
+    MNAS_CHECK_LAUNCH();
+    return MNAS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Frozen BatchNorm statistics: the coefficient blocks of ALL ConvBlock applications of a forward in one launch (they depend on
+// parameters and buffers only).  blockIdx.y selects the descriptor (device array, like k_pack_batch), blockIdx.x a chunk of 256
+// channels.  Rows 0, 1 in the arithmetic of k_bn_fwd_finalize's eval branch (bit-equal); rows 2..6 = s, +0, +0, running mean, invstd.
+// ------------------------------------------------------------------------------------------------
+#define FROZEN_CHUNKS 8
+__global__ __launch_bounds__(256) void k_bn_frozen_batch(const MnasBnFrozenDesc* __restrict__ descs) {
+    const MnasBnFrozenDesc d = descs[blockIdx.y];
+    const int C = d.C;
+    for (int c = blockIdx.x * 256 + threadIdx.x; c < C; c += gridDim.x * 256) {
+        const float rm = d.running_mean[c];
+        const float invstd = 1.0f / sqrtf(d.running_var[c] + d.eps);
+        const float s = d.gamma[c] * invstd;
+        const float t = d.beta[c] - rm * s;
+        float* b = d.bnbuf;
+        b[0 * C + c] = s;
+        b[1 * C + c] = t;
+        b[2 * C + c] = s;
+        b[3 * C + c] = 0.f;
+        b[4 * C + c] = 0.f;
+        b[5 * C + c] = rm;
+        b[6 * C + c] = invstd;
+    }
+}
+extern "C" int mnas_bn_frozen_tables(const MnasBnFrozenDesc* descs_device, int n, void* stream) {
+    if (!descs_device || n < 1 || n > 65535) return MNAS_EINVAL;
+    hipLaunchKernelGGL(k_bn_frozen_batch, dim3(FROZEN_CHUNKS, n), dim3(256), 0, (hipStream_t)stream, descs_device);
     MNAS_CHECK_LAUNCH();
     return MNAS_OK;
 }
@@ -688,6 +747,21 @@ __global__ __launch_bounds__(256) void k_bwd_post(PostArgs a) {
     if (b < n1) { post_wg(a.w1, b); return; }
     post_wg(a.w2, b - n1);
 }
+// The same launch under frozen BatchNorm statistics: the BatchNorm blocks accumulate dgamma, dbeta and dbias and leave bnbuf alone
+// (bn_bwd_finalize_body<.., true>); the weight-gradient blocks are post_wg unchanged.  (Its own ten lines, not a template shared
+// with k_bwd_post: through a shared body the compiler schedules k_bwd_post's stores differently, and that kernel's code is kept.)
+__global__ __launch_bounds__(256) void k_bwd_post_frozen(PostArgs a, float* dbias) {
+    int b = blockIdx.x;
+    if (b < a.bn_nblk) {
+        if (a.bn_wide) bn_bwd_finalize_body<256, true>(a.bn_partial, a.bn_nparts, a.bn_C, a.count, a.bnbuf, a.dgamma, a.dbeta, 1, b, dbias);
+        else bn_bwd_finalize_body<64, true>(a.bn_partial, a.bn_nparts, a.bn_C, a.count, a.bnbuf, a.dgamma, a.dbeta, 1, b, dbias);
+        return;
+    }
+    b -= a.bn_nblk;
+    const int n1 = a.w1.level ? a.w1.nx * a.w1.ny : 0;
+    if (b < n1) { post_wg(a.w1, b); return; }
+    post_wg(a.w2, b - n1);
+}
 static bool post_fill(PostWg* w, const MnasPostWgrad& t) {
     w->level = t.level;
     if (!t.level) { w->nx = w->ny = 0; return true; }
@@ -699,20 +773,37 @@ static bool post_fill(PostWg* w, const MnasPostWgrad& t) {
     w->ny = t.level == 2 ? (t.nsplit + FIN_SPLITS - 1) / FIN_SPLITS : 1;
     return true;
 }
+// PostArgs and the grid of one merged launch, from the fields MnasBwdPost and MnasBwdPostFrozen share: the number of blocks
+// (0: nothing to launch), or -1 for arguments that are refused.
+static int post_args(PostArgs* a, const float* bn_partial, const float* bnbuf, float* dgamma, float* dbeta, double count, int bn_nparts,
+                     int bn_C, const MnasPostWgrad& w1, const MnasPostWgrad& w2) {
+    if (bn_C > 0) {
+        if (!bn_partial || !bnbuf || bn_nparts < 1) return -1;
+        a->bn_partial = bn_partial; a->bnbuf = const_cast<float*>(bnbuf); a->dgamma = dgamma; a->dbeta = dbeta; a->count = count;
+        a->bn_nparts = bn_nparts; a->bn_C = bn_C;
+        a->bn_wide = bn_nparts > 256 ? 1 : 0;
+        a->bn_nblk = a->bn_wide ? bn_C : (bn_C + 3) / 4;
+    }
+    if (!post_fill(&a->w1, w1) || !post_fill(&a->w2, w2)) return -1;
+    return a->bn_nblk + a->w1.nx * a->w1.ny + a->w2.nx * a->w2.ny;
+}
 extern "C" int mnas_bwd_post(const MnasBwdPost* p, void* stream) {
     if (!p) return MNAS_EINVAL;
     PostArgs a = {};
-    if (p->bn_C > 0) {
-        if (!p->bn_partial || !p->bnbuf || p->bn_nparts < 1) return MNAS_EINVAL;
-        a.bn_partial = p->bn_partial; a.bnbuf = p->bnbuf; a.dgamma = p->dgamma; a.dbeta = p->dbeta; a.count = p->count;
-        a.bn_nparts = p->bn_nparts; a.bn_C = p->bn_C;
-        a.bn_wide = p->bn_nparts > 256 ? 1 : 0;
-        a.bn_nblk = a.bn_wide ? p->bn_C : (p->bn_C + 3) / 4;
-    }
-    if (!post_fill(&a.w1, p->w1) || !post_fill(&a.w2, p->w2)) return MNAS_EINVAL;
-    const int blocks = a.bn_nblk + a.w1.nx * a.w1.ny + a.w2.nx * a.w2.ny;
+    const int blocks = post_args(&a, p->bn_partial, p->bnbuf, p->dgamma, p->dbeta, p->count, p->bn_nparts, p->bn_C, p->w1, p->w2);
+    if (blocks < 0) return MNAS_EINVAL;
     if (blocks < 1) return MNAS_OK;
     hipLaunchKernelGGL(k_bwd_post, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    MNAS_CHECK_LAUNCH();
+    return MNAS_OK;
+}
+extern "C" int mnas_bwd_post_frozen(const MnasBwdPostFrozen* p, void* stream) {
+    if (!p) return MNAS_EINVAL;
+    PostArgs a = {};
+    const int blocks = post_args(&a, p->bn_partial, p->bnbuf, p->dgamma, p->dbeta, p->count, p->bn_nparts, p->bn_C, p->w1, p->w2);
+    if (blocks < 0) return MNAS_EINVAL;
+    if (blocks < 1) return MNAS_OK;
+    hipLaunchKernelGGL(k_bwd_post_frozen, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, p->dbias);
     MNAS_CHECK_LAUNCH();
     return MNAS_OK;
 }

@@ -15,8 +15,18 @@ us (tensor hooks registered on parameters -- register_hook / post-accumulate-gra
 bypass AccumulateGrad; DDP-style hook-driven reducers must use train_step.Trainer's stage-done callback instead); weight/BN gradients are written by the kernels straight into a flat fp32 buffer whose slices ARE the
 parameters' ``.grad`` (None -> attached, already ours -> accumulated, foreign tensor -> added into it), the
 same observable behaviour as autograd's AccumulateGrad, without ~110 tiny copy kernels.  Shared blocks
-accumulate their ``layers`` contributions; ``conv.bias.grad`` is exactly zero (train-mode BatchNorm cancels
-the bias; the reference gets ~1e-5 rounding noise there).
+accumulate their ``layers`` contributions; in train mode ``conv.bias.grad`` is exactly zero (batch-statistics
+BatchNorm cancels the bias; the reference gets ~1e-5 rounding noise there).
+
+Frozen BatchNorm statistics: a TRACKED forward of a subtree that is entirely in eval mode (``model.train();
+model.features.eval()``, classifiers.FineTuneModelPool.freeze_bn) runs the frozen program (launch_plan.LaunchPlan,
+frozen_bn): the eval forward, bit for bit, with its activations kept (the same launches without squeeze-excite; with
+it, a block whose project conv has no gate-on-load backward at that size reads the materialised a*s where plain
+inference gates on load -- the same values by another launch, LaunchPlan._se_onload_kseg), and a backward that gives
+every parameter its gradient while the running buffers stay untouched.  There ``conv.bias.grad`` is NOT zero (s * sum dz).  A no-grad eval forward stays the
+plain eval program; a subtree in mixed modes still raises.  The frozen program holds every backward buffer and a lease
+until its output dies, so inference belongs under ``torch.no_grad()``: more than _MAX_PROGRAMS_PER_SHAPE tracked
+eval-mode outputs alive at once raise.
 """
 from __future__ import annotations
 
@@ -108,11 +118,11 @@ class Program(LaunchPlan):
     """launch_plan.LaunchPlan (all buffers + launch lists of one (N, H, W, training, need_dx) configuration) and its run-time half:
     the run-time pointers are patched into the lists, which are launched per op or replayed as hipGraphs."""
 
-    def __init__(self, eng: "Engine", N, H, W, training, need_dx, pooled=False, in_u8=False):
+    def __init__(self, eng: "Engine", N, H, W, training, need_dx, pooled=False, in_u8=False, *, frozen_bn=False):
         self._graphs = {}
         self.busy = False
         self._out_buf = self._gout_buf = self._x_buf = self._x_direct = None
-        super().__init__(eng, N, H, W, training, need_dx, pooled, in_u8)
+        super().__init__(eng, N, H, W, training, need_dx, pooled, in_u8, frozen_bn=frozen_bn)
 
     # ------------------------------------------------------------------------------------------
     def _run(self, arr, n, what):
@@ -253,17 +263,20 @@ class _EngineFn(torch.autograd.Function):
     def forward(ctx, eng, track, pooled, x, *params):
         need_dx = track and x.requires_grad
         training = eng.root.training
-        prog = eng.program(x.shape[0], x.shape[2], x.shape[3], training, need_dx, pooled, x.dtype == torch.uint8)
+        # a tracked forward in eval mode trains on the running statistics (frozen program); without tracking it is plain inference
+        frozen = track and not training
+        prog = eng.program(x.shape[0], x.shape[2], x.shape[3], training or frozen, need_dx, pooled, x.dtype == torch.uint8,
+                           frozen_bn=frozen)
         out = prog.run_forward(x)
         ctx.eng = eng
-        ctx.lease = _Lease(prog) if (training and track) else None
+        ctx.lease = _Lease(prog) if track else None
         return out
 
     @staticmethod
     def backward(ctx, gout):
         lease, eng = ctx.lease, ctx.eng
         if lease is None:
-            raise RuntimeError("backward through an eval-mode / no-grad engine forward")
+            raise RuntimeError("backward through a no-grad engine forward")
         if lease.consumed or lease.prog is None:
             # the activation buffers belong to a per-shape program that later forwards reuse: a second backward
             # (retain_graph=True) would read overwritten activations
@@ -475,8 +488,8 @@ class Engine:
                     raise TypeError("mnasnet_pytorch_amd: SqueezeExcite parameters must be contiguous float32")
 
     def _check_modes(self):
-        """One mode per call: the launch list is compiled for root.training.  A submodule in a different mode (frozen-BN
-        fine-tuning: ``bn.eval()`` under a training root) is not silently ignored."""
+        """One mode per call: the launch list is compiled for root.training.  A submodule in a different mode (``bn.eval()`` under a
+        training root) is not silently ignored; frozen-BN fine-tuning puts the WHOLE subtree in eval mode (module docstring)."""
         mode = self.root.training
         for m in self.root.modules():
             if m.training != mode:
@@ -579,8 +592,8 @@ class Engine:
             self._in_aff[(u8, self.device)] = t
         return t
 
-    def program(self, N, H, W, training, need_dx, pooled=False, in_u8=False) -> Program:
-        key = (N, H, W, training, need_dx, pooled, bool(in_u8))
+    def program(self, N, H, W, training, need_dx, pooled=False, in_u8=False, *, frozen_bn=False) -> Program:
+        key = (N, H, W, training, need_dx, pooled, bool(in_u8), bool(frozen_bn))
         lst = self.programs.setdefault(key, [])
         for p in lst:
             if not p.busy:
@@ -590,7 +603,7 @@ class Engine:
                 "%d forwards of shape %s are alive at once (their autograd graphs are still referenced and no backward "
                 "has run): each holds a full set of activation buffers.  Drop the old outputs / call backward, or run "
                 "under torch.no_grad()." % (len(lst), (N, self.in_channels_hint, H, W)))
-        p = Program(self, N, H, W, training, need_dx, pooled, in_u8)
+        p = Program(self, N, H, W, training, need_dx, pooled, in_u8, frozen_bn=frozen_bn)
         lst.append(p)
         return p
 

@@ -112,10 +112,21 @@ class _OpList:
 
 
 class LaunchPlan:
-    """All buffers + launch lists for one (N, H, W, training, need_dx) configuration."""
+    """All buffers + launch lists for one (N, H, W, training, need_dx) configuration.
 
-    def __init__(self, eng, N, H, W, training, need_dx, pooled=False, in_u8=False):
+    frozen_bn (with training): BatchNorm normalises with its RUNNING statistics and leaves them alone while every parameter still
+    gets its gradient (model.train(); features.eval()).  The forward is the eval forward that keeps its activations (squeeze-excite
+    blocks take the TRAINING criteria of _se_onload_kseg, since their backward has to exist: below pw_fused_min_pixels the project
+    conv reads the materialised a*s where the plain eval program gates on load: the same values), with one
+    mnas_bn_frozen_tables launch at its head filling every application's whole coefficient block (dy = s*dz: rows 2..4 = s, 0, 0;
+    rows 5, 6 = running mean, invstd for the reduces); the backward is the train-mode list with the BatchNorm finalizes replaced by
+    their frozen twins, which also accumulate the conv bias gradient s*S1 and do not write the block."""
+
+    def __init__(self, eng, N, H, W, training, need_dx, pooled=False, in_u8=False, *, frozen_bn=False):
         self.eng, self.N, self.H, self.W, self.training, self.need_dx = eng, N, H, W, training, need_dx
+        self.frozen_bn = bool(frozen_bn)
+        if self.frozen_bn and not training:
+            raise ValueError("frozen_bn is a training mode: the plain eval program is training=False")
         self.pooled = pooled
         self.in_u8 = bool(in_u8)
         # fused input pipeline of the stem (Engine.set_input_normalization): per-plane affine, uint8 images
@@ -169,6 +180,9 @@ class LaunchPlan:
         raw = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(eng.device)
         self.keep.append(raw)
         fwd.add(L.OP_PACK_BATCH, n=len(descs), descs=raw)
+        # frozen statistics: every application's coefficient block in one launch; its descriptor table is filled in below, once the
+        # blocks exist
+        j_frozen = fwd.add(L.OP_BN_FROZEN_BATCH, n=0) if self.frozen_bn else None
 
         self.x_is_image = eng.first_conv.kind == "stem"
         self.patch_x = []       # (op index, pointer slot) receiving the input pointer
@@ -214,6 +228,16 @@ class LaunchPlan:
             self.out_shape = (N, cur.C, cur.H, cur.W)
             j = fwd.add(L.OP_ADD_ACT, C=cur.C, HW=cur.H * cur.W, rows=N * cur.H * cur.W, a=cur)
             self.patch_out = (j, L.slot(L.OP_ADD_ACT, "out_nchw"))
+        if self.frozen_bn:
+            fdescs = []
+            for rec in self._records:
+                bnm = rec.ci.mod.bn
+                fdescs.append((bnm.weight.data_ptr(), bnm.bias.data_ptr(), bnm.running_mean.data_ptr(), bnm.running_var.data_ptr(),
+                               rec.out.bn.data_ptr(), rec.ci.cout, bnm.eps))
+            host = (L.MnasBnFrozenDesc * len(fdescs))(*fdescs)
+            raw = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(eng.device)
+            self.keep.append(raw)
+            L.set_op(fwd.items[j_frozen], L.OP_BN_FROZEN_BATCH, 0, n=len(fdescs), descs=raw)
         self.fwd_ops, self.fwd_n = fwd.build()
         self.final = cur
         return steps
@@ -248,7 +272,7 @@ class LaunchPlan:
         y = self._new((N, Ho, Wo, ci.cout))
         bn = self._bnbuf(ci.cout)
         conv, bnm = ci.mod.conv, ci.mod.bn
-        stats = eng.scratch_stats if training else None
+        stats = eng.scratch_stats if (training and not self.frozen_bn) else None      # no statistics partials from running buffers
         if ci.kind == "stem":
             nparts = lib.mnas_stem_parts(0, N, Hi, Wi, ci.cout)
             if self._aff is not None and (nparts < 1 or (training and lib.mnas_stem_parts(1, N, Hi, Wi, ci.cout) < 1)):
@@ -278,9 +302,10 @@ class LaunchPlan:
             fwd.add(L.OP_CONV_GEMM, mode=0, N=N, Hi=Hi, Wi=Wi, Ci=ci.cin, Ho=Ho, Wo=Wo, Co=ci.cout, kh=ci.k, kw=ci.k,
                     stride=ci.stride, pad=ci.pad, nparts=nparts, act=a_in, w=ci.w_fwd, bias=conv.bias, out=y, stats=stats,
                     gate=a_in.gate)
-        fwd.add(L.OP_BN_FWD_FINALIZE, nparts=nparts, C=ci.cout, training=training, count=M, momentum=bnm.momentum, eps=bnm.eps,
-                partial=stats, gamma=bnm.weight, beta=bnm.bias, rmean=bnm.running_mean, rvar=bnm.running_var,
-                nbt=bnm.num_batches_tracked, bnbuf=bn)
+        if not self.frozen_bn:       # (frozen: OP_BN_FROZEN_BATCH at the head of the list wrote the block)
+            fwd.add(L.OP_BN_FWD_FINALIZE, nparts=nparts, C=ci.cout, training=training, count=M, momentum=bnm.momentum, eps=bnm.eps,
+                    partial=stats, gamma=bnm.weight, beta=bnm.bias, rmean=bnm.running_mean, rvar=bnm.running_var,
+                    nbt=bnm.num_batches_tracked, bnbuf=bn)
         out = _Act(y, bn, Ho, Wo, ci.cout)
         self._records.append(_ConvApp(ci, a_in, out, Hi, Wi))
         return out
@@ -295,6 +320,8 @@ class LaunchPlan:
             return 0
         if not self.training:
             return 1
+        # (a frozen_bn program is a training program: where these criteria fail its forward materialises a*s while the plain eval
+        # forward gates on load; the values are the same either way)
         if M < eng.pw_fused_min_pixels or not lib.mnas_pw_bwd_supported(Ci, Co):
             return 0
         tile, slices = lib.mnas_pw_bwd_tile_pixels(Ci, Co), lib.mnas_pw_bwd_slices(Ci, Co)
@@ -435,20 +462,24 @@ class LaunchPlan:
         self._rot += 1
         return b
 
-    def _emit_post(self, ops: _OpList, bn=None):
+    def _emit_post(self, ops: _OpList, bn=None, dbias=None):
+        """dbias (frozen statistics only): the conv bias gradient slice of the ConvBlock `bn` belongs to"""
         pend = self._pend
         w1, w2 = pend.w1, pend.w2
         pend.w1 = pend.w2 = None
         if w1 is not None and w1.level == 2:
             pend.w2 = w1._replace(level=3)
         fields = {} if bn is None else bn._asdict()
+        if bn is not None and self.frozen_bn:
+            fields["dbias"] = dbias
         if w1 is not None:
             fields["w1"] = w1
         if w2 is not None:
             fields["w2"] = w2
         if not fields:
             return
-        ops.add(L.OP_BWD_POST, **fields)
+        # frozen statistics: the twin that leaves bnbuf alone (a launch without a BatchNorm part stays mnas_bwd_post)
+        ops.add(L.OP_BWD_POST_FROZEN if (bn is not None and self.frozen_bn) else L.OP_BWD_POST, **fields)
         pend.ops = ops
 
     def _flush_post(self):
@@ -475,7 +506,10 @@ class LaunchPlan:
         if eng.merge_post:
             if self._pend.ops is not None and self._pend.ops is not ops:
                 self._flush_post()               # a stage's gradients are complete inside its own launch list
-            self._emit_post(ops, _BnPost(red_buf, out.bn, eng.gptr(ci, 2), eng.gptr(ci, 3), nred, Co, float(M)))
+            self._emit_post(ops, _BnPost(red_buf, out.bn, eng.gptr(ci, 2), eng.gptr(ci, 3), nred, Co, float(M)), eng.gptr(ci, 1))
+        elif self.frozen_bn:
+            ops.add(L.OP_BN_BWD_FINALIZE_FROZEN, nparts=nred, C=Co, accumulate=1,
+                    partial=red_buf, bnbuf=out.bn, dgamma=eng.gptr(ci, 2), dbeta=eng.gptr(ci, 3), dbias=eng.gptr(ci, 1))
         else:
             ops.add(L.OP_BN_BWD_FINALIZE, nparts=nred, C=Co, accumulate=1, count=M,
                     partial=red_buf, bnbuf=out.bn, dgamma=eng.gptr(ci, 2), dbeta=eng.gptr(ci, 3))

@@ -344,10 +344,12 @@ class Trainer:
 
     def _native_head(self):
         """The model's NativeHead when the whole step can bypass autograd: FineTuneModelPool-like model in training mode
-        (fused pool, Dropout/Linear/ReLU classifier) and a plain mean-reduced nn.CrossEntropyLoss (train.py:277)."""
+        (fused pool, Dropout/Linear/ReLU classifier) and a plain mean-reduced nn.CrossEntropyLoss (train.py:277).  The features may
+        be entirely in eval mode under a training model (FineTuneModelPool.freeze_bn): forward_backward then runs the engine's
+        frozen-statistics program; a subtree in mixed modes is refused by Engine._check_modes."""
         m = self.model
         head = self._native_eval_head()
-        if head is None or not (m.training and self.engine.root.training):
+        if head is None or not m.training:
             return None
         if any(not p.requires_grad for p in self.head_params):
             return None
@@ -416,7 +418,7 @@ class Trainer:
             x = x.contiguous() if u8 else x.float().contiguous()
             eng.ensure_setup(x.device)
             eng._check_modes()
-            prog = eng.program(x.shape[0], x.shape[2], x.shape[3], True, False, True, u8)
+            prog = eng.program(x.shape[0], x.shape[2], x.shape[3], True, False, True, u8, frozen_bn=not eng.root.training)
             f = prog.run_forward(x, static_io=True)
             head.calls = self.optimizer.step_count           # dropout masks follow the CHECKPOINTED step count: a resumed run does
                                                              # not replay the masks of the first steps
