@@ -98,10 +98,24 @@ class FineTuneModelPool(nn.Module):
             self.features.eval()
         return self
 
-    def freeze(self):
-        print("Features frozen")
-        for p in self.features.parameters():
-            p.requires_grad = False
+    def freeze(self, upto=None):
+        """classifiers.py:95-99 without an argument: every feature parameter stops training.  ``upto`` = k (an extension for
+        gradual unfreezing, 0 <= k <= len(self.features)) freezes ``features[:k]`` and makes ``features[k:]`` trainable: the
+        engine's backward then ends at the first layer of ``features[k]`` (engine.Engine.first_trainable_step) and the stages in
+        front of it cost no backward launch and no backward buffer.  Only ``requires_grad`` changes: with train-mode BatchNorm the
+        frozen stages keep normalising with batch statistics and updating their running buffers, as under the reference's
+        freeze(); freeze_bn() is the independent switch for those."""
+        if upto is None:
+            print("Features frozen")
+            for p in self.features.parameters():
+                p.requires_grad = False
+            return
+        n = len(self.features)
+        if isinstance(upto, bool) or not isinstance(upto, int) or not 0 <= upto <= n:
+            raise ValueError("freeze(upto=...) takes an integer in [0, %d], got %r" % (n, upto))
+        for i, child in enumerate(self.features):
+            for p in child.parameters():
+                p.requires_grad = i >= upto
 
     def unfreeze(self):
         print("Features unfrozen")

@@ -27,6 +27,11 @@ every parameter its gradient while the running buffers stay untouched.  There ``
 plain eval program; a subtree in mixed modes still raises.  The frozen program holds every backward buffer and a lease
 until its output dies, so inference belongs under ``torch.no_grad()``: more than _MAX_PROGRAMS_PER_SHAPE tracked
 eval-mode outputs alive at once raise.
+
+Frozen stage prefix: the backward of a tracked forward ends at Engine.first_trainable_step(), the first step that owns a parameter
+with ``requires_grad`` (classifiers.FineTuneModelPool.freeze(upto=k)); the steps in front of it get no backward launch and no
+backward buffer (launch_plan.LaunchPlan, first_trainable).  The boundary is read at every forward and is part of the program key,
+so changing ``requires_grad`` between two steps selects another program; ``x.requires_grad`` needs the whole backward.
 """
 from __future__ import annotations
 
@@ -118,11 +123,11 @@ class Program(LaunchPlan):
     """launch_plan.LaunchPlan (all buffers + launch lists of one (N, H, W, training, need_dx) configuration) and its run-time half:
     the run-time pointers are patched into the lists, which are launched per op or replayed as hipGraphs."""
 
-    def __init__(self, eng: "Engine", N, H, W, training, need_dx, pooled=False, in_u8=False, *, frozen_bn=False):
+    def __init__(self, eng: "Engine", N, H, W, training, need_dx, pooled=False, in_u8=False, *, frozen_bn=False, first_trainable=0):
         self._graphs = {}
         self.busy = False
         self._out_buf = self._gout_buf = self._x_buf = self._x_direct = None
-        super().__init__(eng, N, H, W, training, need_dx, pooled, in_u8, frozen_bn=frozen_bn)
+        super().__init__(eng, N, H, W, training, need_dx, pooled, in_u8, frozen_bn=frozen_bn, first_trainable=first_trainable)
 
     # ------------------------------------------------------------------------------------------
     def _run(self, arr, n, what):
@@ -206,6 +211,8 @@ class Program(LaunchPlan):
         return out
 
     def run_backward(self, gout, on_stage_done: Optional[Callable[[int], None]] = None, static_io=False):
+        if not self.bwd_segments:
+            raise RuntimeError("this program has no backward: it was built for inference or with every step frozen")
         if static_io and self.eng.use_graphs:
             if self._gout_buf is None or self._gout_buf.shape != gout.shape or self._gout_buf.device != gout.device:
                 self._gout_buf = torch.empty_like(gout)
@@ -265,8 +272,10 @@ class _EngineFn(torch.autograd.Function):
         training = eng.root.training
         # a tracked forward in eval mode trains on the running statistics (frozen program); without tracking it is plain inference
         frozen = track and not training
+        # the backward ends at the first step that owns a trainable parameter; an input gradient needs all of it
+        first = 0 if (need_dx or not track) else eng.first_trainable_step()
         prog = eng.program(x.shape[0], x.shape[2], x.shape[3], training or frozen, need_dx, pooled, x.dtype == torch.uint8,
-                           frozen_bn=frozen)
+                           frozen_bn=frozen, first_trainable=first)
         out = prog.run_forward(x)
         ctx.eng = eng
         ctx.lease = _Lease(prog) if track else None
@@ -592,8 +601,31 @@ class Engine:
             self._in_aff[(u8, self.device)] = t
         return t
 
-    def program(self, N, H, W, training, need_dx, pooled=False, in_u8=False, *, frozen_bn=False) -> Program:
-        key = (N, H, W, training, need_dx, pooled, bool(in_u8), bool(frozen_bn))
+    def step_params(self, i: int) -> List[nn.Parameter]:
+        """The parameters step ``i`` owns: its ConvBlocks' conv.weight, conv.bias, bn.weight, bn.bias and, for a block with
+        squeeze-excite, the se.fc* parameters."""
+        op, m, _ = self.steps[i]
+        owners = [self.info[id(cb)] for cb in ([m] if op == "conv" else m)]
+        if op == "block" and id(m[0]) in self.se_info:
+            owners.append(self.se_info[id(m[0])])
+        return [p for o in owners for p in o.params]
+
+    def first_trainable_step(self) -> int:
+        """The smallest index i such that step i owns a parameter with requires_grad, len(self.steps) if there is none: where the
+        backward may end (LaunchPlan first_trainable).  Read from the modules at every call: freeze() / unfreeze() or a manual
+        ``p.requires_grad = ...`` between two forwards selects another program.  The applications of a list-multiplied block share
+        one module and flip together."""
+        for i in range(len(self.steps)):
+            if any(p.requires_grad for p in self.step_params(i)):
+                return i
+        return len(self.steps)
+
+    def step_stage(self, i: int) -> int:
+        """features.<stage> of step i; one past the last stage for i == len(self.steps)"""
+        return self.steps[i][2] if i < len(self.steps) else self.steps[-1][2] + 1
+
+    def program(self, N, H, W, training, need_dx, pooled=False, in_u8=False, *, frozen_bn=False, first_trainable=0) -> Program:
+        key = (N, H, W, training, need_dx, pooled, bool(in_u8), bool(frozen_bn), int(first_trainable))
         lst = self.programs.setdefault(key, [])
         for p in lst:
             if not p.busy:
@@ -603,7 +635,7 @@ class Engine:
                 "%d forwards of shape %s are alive at once (their autograd graphs are still referenced and no backward "
                 "has run): each holds a full set of activation buffers.  Drop the old outputs / call backward, or run "
                 "under torch.no_grad()." % (len(lst), (N, self.in_channels_hint, H, W)))
-        p = Program(self, N, H, W, training, need_dx, pooled, in_u8, frozen_bn=frozen_bn)
+        p = Program(self, N, H, W, training, need_dx, pooled, in_u8, frozen_bn=frozen_bn, first_trainable=first_trainable)
         lst.append(p)
         return p
 

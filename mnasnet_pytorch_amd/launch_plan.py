@@ -120,13 +120,24 @@ class LaunchPlan:
     conv reads the materialised a*s where the plain eval program gates on load: the same values), with one
     mnas_bn_frozen_tables launch at its head filling every application's whole coefficient block (dy = s*dz: rows 2..4 = s, 0, 0;
     rows 5, 6 = running mean, invstd for the reduces); the backward is the train-mode list with the BatchNorm finalizes replaced by
-    their frozen twins, which also accumulate the conv bias gradient s*S1 and do not write the block."""
+    their frozen twins, which also accumulate the conv bias gradient s*S1 and do not write the block.
 
-    def __init__(self, eng, N, H, W, training, need_dx, pooled=False, in_u8=False, *, frozen_bn=False):
+    first_trainable (with training): index into Engine.steps of the first step that owns a trainable parameter
+    (Engine.first_trainable_step).  The backward ends there: the boundary step runs without its input gradient, the steps in
+    front of it get no launch, the stages wholly in front of it no segment, and no buffer that only their backward needs exists.
+    The forward is the same list whatever the boundary; len(steps) leaves a program without backward lists.  An input gradient
+    (need_dx) needs the boundary at 0."""
+
+    def __init__(self, eng, N, H, W, training, need_dx, pooled=False, in_u8=False, *, frozen_bn=False, first_trainable=0):
         self.eng, self.N, self.H, self.W, self.training, self.need_dx = eng, N, H, W, training, need_dx
         self.frozen_bn = bool(frozen_bn)
         if self.frozen_bn and not training:
             raise ValueError("frozen_bn is a training mode: the plain eval program is training=False")
+        self.first_trainable = int(first_trainable)
+        if not 0 <= self.first_trainable <= len(eng.steps):
+            raise ValueError("first_trainable must be a step index in [0, %d], got %d" % (len(eng.steps), self.first_trainable))
+        if self.first_trainable and (need_dx or not training):
+            raise ValueError("a frozen prefix belongs to a training program without an input gradient")
         self.pooled = pooled
         self.in_u8 = bool(in_u8)
         # fused input pipeline of the stem (Engine.set_input_normalization): per-plane affine, uint8 images
@@ -143,7 +154,7 @@ class LaunchPlan:
         self.patch_gout = None      # patch_*: (stage, op index, pointer slot) receiving a run-time pointer
         self.patch_dx = None
         self.patch_x_bwd = None
-        if training:
+        if training and self.first_trainable < len(steps):
             self._plan_backward(steps)
 
     # ---- forward -----------------------------------------------------------------------------------
@@ -357,8 +368,10 @@ class LaunchPlan:
 
     # ---- backward ----------------------------------------------------------------------------------
     def _plan_backward(self, steps: List[_Step]):
-        """The backward launch lists, one per features.<stage> segment, from the forward's records (reverse order)."""
+        """The backward launch lists, one per features.<stage> segment, from the forward's records (reverse order), down to the
+        boundary step self.first_trainable."""
         eng, N, H, W, need_dx, records, cur = self.eng, self.N, self.H, self.W, self.need_dx, self._records, self.final
+        first = self.first_trainable
         self._seg_ops: Dict[int, _OpList] = {}
         self._order: List[int] = []
         last = self._seg(steps[-1].stage)
@@ -377,12 +390,15 @@ class LaunchPlan:
         self._rot = 0
         self._rot_bufs = [eng.scratch_wgrad2, eng.scratch_wgrad3, eng.scratch_wgrad4]
         self._masked_g = set()       # data_ptr of gradient tensors stored masked (dz) by their producer
+        # the record of a conv step that ends the backward: its depthwise sweep runs without the fused reduce, the one form that
+        # takes no masked gradient (_feeds_fused_dw)
+        self._end_rec = records[steps[first].start] if not (first == 0 and need_dx) else None
         g = g_final
         g_red = 0            # number of fused-reduce partial columns already written for the layer g belongs to
-        for si in range(len(steps) - 1, -1, -1):
+        for si in range(len(steps) - 1, first - 1, -1):
             step = steps[si]
             ops = self._seg(step.stage)
-            need = si > 0 or need_dx          # does anybody want the gradient of the step's input
+            need = si > first or (need_dx and first == 0)     # does anybody want the gradient of the step's input
             if step.kind == "conv":
                 rec = records[step.start]
                 g, g_red = self._conv_bwd(ops, rec, g, None, need, g_red, self._input_target(steps, si, rec.a_in))
@@ -408,9 +424,9 @@ class LaunchPlan:
                     self._conv_bwd(ops, re_, g1, None, False, c1, None)
                     g, g_red = None, 0
         if need_dx and not self.x_is_image:
-            first = self._seg(steps[0].stage)
-            j = first.add(L.OP_ADD_ACT, C=self.in_channels, HW=H * W, rows=N * H * W, a=(g, None, None))
-            self.patch_dx = (first.stage, j, L.slot(L.OP_ADD_ACT, "out_nchw"))
+            seg0 = self._seg(steps[0].stage)
+            j = seg0.add(L.OP_ADD_ACT, C=self.in_channels, HW=H * W, rows=N * H * W, a=(g, None, None))
+            self.patch_dx = (seg0.stage, j, L.slot(L.OP_ADD_ACT, "out_nchw"))
         self._flush_post()
         order, built = self._order, {}
         for st in order:
@@ -708,7 +724,8 @@ class LaunchPlan:
             if rec.out is act or (rec.out.data is act.data and rec.out.bn is act.bn):
                 ci = rec.ci
                 # ... and carries the fused reduce (its own input is a virtual activation), the form g_masked exists for
-                return ci.kind == "dw" and ci.stride == 1 and ci.k in self.eng.dw_fused_k and rec.a_in is not None and rec.a_in.bn is not None
+                return (ci.kind == "dw" and ci.stride == 1 and ci.k in self.eng.dw_fused_k and rec.a_in is not None and rec.a_in.bn is not None
+                        and rec is not self._end_rec)
         return False
 
     def _conv_bwd_se_proj(self, ops: _OpList, rec, g, g_reduced, se_rec):

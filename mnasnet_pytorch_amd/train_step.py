@@ -65,14 +65,22 @@ class BucketSchedule:
         early = [s for s in stage_ranges if s >= early_bucket_stage]
         split = n_head + (max(stage_ranges[s][1] for s in early) if early else 0)
         self.buckets = FlatBuckets(flat_g, [0, split, n], group)
+        self._n_head, self._stage_ranges, self._bounds = n_head, {s: tuple(r) for s, r in stage_ranges.items()}, [0, split, n]
         self.early_stage = min(early) if early else None
         self.join_stages = {self.early_stage} if self.early_stage is not None else set()
         self.launched0 = False
         self.log = []                     # ("stage", s) / ("launch", bucket): the order things happened in (tests)
 
-    def begin_step(self):
+    def begin_step(self, first_trainable_stage: int = 0):
+        """first_trainable_stage: the stage the engine's backward ends in this step (a frozen stage prefix, Engine.first_trainable_step).
+        The stages wholly in front of it have no gradient and are left out of the all-reduce: the flat layout is later stages
+        first, so the trainable stages are a leading range and both buckets are clipped to it (an empty bucket launches nothing).
+        Every rank must pass the same value: the collectives pair up by size."""
         self.launched0 = False
         self.log = []
+        live = [s for s in self._stage_ranges if s >= first_trainable_stage]
+        end = self._n_head + (max(self._stage_ranges[s][1] for s in live) if live else 0)
+        self.buckets.bounds = [min(b, end) for b in self._bounds]
 
     def on_stage_done(self, stage: int):
         """engine callback: the backward of features.<stage> (and everything after it) has been enqueued"""
@@ -353,9 +361,22 @@ class Trainer:
             return None
         if any(not p.requires_grad for p in self.head_params):
             return None
-        if any(not p.requires_grad for p in self.engine.params):
-            return None            # frozen features (FineTuneModelPool.freeze()): the module path skips their backward
+        if self._frozen_prefix() is None:
+            return None            # all features frozen (FineTuneModelPool.freeze()) or a pattern that is no stage prefix: module path
         return head
+
+    def _frozen_prefix(self):
+        """The engine step the native step's backward ends at: 0 with every engine parameter trainable, b when the frozen ones are
+        exactly those of the steps in front of step b (FineTuneModelPool.freeze(upto=k)), 0 < b < len(steps).  None for anything
+        else -- a frozen parameter behind the boundary, or nothing trainable at all: those keep the module path, which runs the
+        truncated program too (engine._EngineFn)."""
+        eng = self.engine
+        b = eng.first_trainable_step()
+        if b >= len(eng.steps):
+            return None
+        if any(not p.requires_grad for i in range(b, len(eng.steps)) for p in eng.step_params(i)):
+            return None
+        return b
 
     def _native_eval_head(self):
         """The part of _native_head() that does not concern training: what lets a validation batch run as engine forward (fused
@@ -392,7 +413,8 @@ class Trainer:
         """One iteration of train.py:427-440.  Returns the loss tensor (no host sync)."""
         self.optimizer.zero_grad()                           # train.py:438
         if self.schedule is not None:
-            self.schedule.begin_step()
+            eng = self.engine
+            self.schedule.begin_step(eng.step_stage(eng.first_trainable_step()))
         loss = self.forward_backward(x, target)
         if self.schedule is not None:
             self.schedule.finish()
@@ -418,7 +440,8 @@ class Trainer:
             x = x.contiguous() if u8 else x.float().contiguous()
             eng.ensure_setup(x.device)
             eng._check_modes()
-            prog = eng.program(x.shape[0], x.shape[2], x.shape[3], True, False, True, u8, frozen_bn=not eng.root.training)
+            prog = eng.program(x.shape[0], x.shape[2], x.shape[3], True, False, True, u8, frozen_bn=not eng.root.training,
+                               first_trainable=self._frozen_prefix())
             f = prog.run_forward(x, static_io=True)
             head.calls = self.optimizer.step_count           # dropout masks follow the CHECKPOINTED step count: a resumed run does
                                                              # not replay the masks of the first steps
