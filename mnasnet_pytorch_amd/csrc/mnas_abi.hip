@@ -3,36 +3,12 @@
 #include "mnas_common.h"
 
 #define MNAS_NT_DEFAULT MNAS_NT_PWF
-int mnas_nt_mask() {
-    static int mask = -1;
-    if (mask < 0) {
-        mask = mnas_diag_env("MNAS_NT", MNAS_NT_DEFAULT);
-    }
-    return mask;
-}
+MNAS_SWITCH(mnas_nt_mask, mnas_diag_env("MNAS_NT", MNAS_NT_DEFAULT))
 
-int mnas_pwf_enabled() {
-    static int on = -1;
-    if (on < 0) {
-        on = mnas_diag_env("MNAS_PWF", 1);
-    }
-    return on;
-}
-int mnas_pwd_enabled() {
-    static int on = -1;
-    if (on < 0) {
-        on = mnas_diag_env("MNAS_PWD", 1) && mnas_pwf_enabled();
-    }
-    return on;
-}
+MNAS_SWITCH(mnas_pwf_enabled, mnas_diag_env("MNAS_PWF", 1))
+MNAS_SWITCH(mnas_pwd_enabled, mnas_diag_env("MNAS_PWD", 1) && mnas_pwf_enabled())
 
-int mnas_pws_enabled() {
-    static int on = -1;
-    if (on < 0) {
-        on = mnas_diag_env("MNAS_PWS", 2);      // 0: off, 1: forward only, 2: forward + input gradient
-    }
-    return on;
-}
+MNAS_SWITCH(mnas_pws_enabled, mnas_diag_env("MNAS_PWS", 2))  // 0: off, 1: forward only, 2: forward + input gradient
 
 extern "C" int mnas_version(void) { return 8; }
 extern "C" const char* mnas_arch(void) { return "gfx950"; }

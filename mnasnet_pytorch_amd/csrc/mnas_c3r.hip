@@ -64,18 +64,7 @@ __global__ __launch_bounds__(512) void k_c3r(C3rArgs a) {
     for (int i = tid; i < 2 * a.Ci; i += 512)
         lds_coef[i] = has_coef ? (i < a.Ci ? a.act.scale[i] : a.act.shift[i - a.Ci]) : 0.f;
     for (int i = tid; i < (NIMG * img_elems) >> 3; i += 512) ((uint4*)img)[i] = make_uint4(0, 0, 0, 0);  // zero borders (and interiors)
-    if (do_red)
-        for (int i = tid; i < 4 * NB; i += 512) {
-            const int r = i / NB, cc = co0 + i % NB;
-            float v = 0.f;
-            if (cc < a.Co) {
-                if (r == 0) v = a.red_bn[cc];
-                else if (r == 1) v = a.red_bn[a.Co + cc];
-                else if (r == 2) v = a.red_bn[6 * a.Co + cc];
-                else v = -a.red_bn[5 * a.Co + cc] * a.red_bn[6 * a.Co + cc];
-            }
-            lds_rc[i] = v;
-        }
+    if (do_red) mnas_fill_red_table(lds_rc, NB, a.Co - co0, a.red_bn, a.Co, co0, tid, 512);
     // ---- this wave's quarter of the weight slice: A fragments [cout l15][k = ks*32 + lg*8 ..], k-steps ks = kq + 4j
     bf16x8_t wf[NT][KSW];
 #pragma unroll
@@ -261,11 +250,7 @@ __global__ __launch_bounds__(512) void k_c3r(C3rArgs a) {
 // ---- host side ---------------------------------------------------------------------------------------------------------
 struct C3rPlan { int nt, ksw, ptw, kq, slices, parts; size_t lds; };
 
-int mnas_c3r_enabled() {
-    static int on = -1;
-    if (on < 0) on = mnas_diag_env("MNAS_C3R", 1);
-    return on;
-}
+MNAS_SWITCH(mnas_c3r_enabled, mnas_diag_env("MNAS_C3R", 1))
 static bool c3r_plan(int mode, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int kh, int kw, int stride, int pad, C3rPlan* p) {
     if (!mnas_c3r_enabled() || kh != 3 || kw != 3 || pad != 1 || (stride != 1 && !(stride == 2 && mode == 0))) return false;
     if ((Ci & 7) || (Co & 7) || Ci < 64 || N < 32 || Ho != (Hi - 1) / stride + 1 || Wo != (Wi - 1) / stride + 1) return false;

@@ -29,15 +29,6 @@ struct C3xArgs {
     float* stats;            // [2][Co][gridDim.x] or NULL
 };
 
-__device__ __forceinline__ int c3x_fdiv(int n, int d, float rcp) {
-    if (rcp == 0.f) return n / d;
-    int q = (int)((float)n * rcp);
-    const int r = n - q * d;
-    q += (r >= d) ? 1 : 0;
-    q -= (r < 0) ? 1 : 0;
-    return q;
-}
-
 template <int TPW, int KS>
 __global__ __launch_bounds__(256) void k_c3x(C3xArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -93,8 +84,8 @@ __global__ __launch_bounds__(256) void k_c3x(C3xArgs a) {
     auto issue = [&](int g) {
         const int m = g * 16 + l15;
         const bool mok = m < a.M;
-        const int n = mok ? c3x_fdiv(m, hw, a.rcp_hw) : 0, rem = m - n * hw;
-        const int oy = mok ? c3x_fdiv(rem, a.Wo, a.rcp_wo) : 0, ox = rem - oy * a.Wo;
+        const int n = mok ? mnas_fdiv(m, hw, a.rcp_hw) : 0, rem = m - n * hw;
+        const int oy = mok ? mnas_fdiv(rem, a.Wo, a.rcp_wo) : 0, ox = rem - oy * a.Wo;
         const int iy0 = oy * a.stride - 1, ix0 = ox * a.stride - 1;
         const uint16_t* base = (const uint16_t*)a.act.data + (((ptrdiff_t)n * a.Hi + iy0) * a.Wi + ix0) * (ptrdiff_t)a.Ci;
         inb_n = 0;
@@ -152,38 +143,13 @@ __global__ __launch_bounds__(256) void k_c3x(C3xArgs a) {
         }
         __builtin_amdgcn_wave_barrier();
     }
-    if (a.stats) {
-        // 16 pixel lanes -> one value per cout (shuffle tree), then the four waves in order
-#pragma unroll
-        for (int t = 0; t < TPW; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float x1 = s1[t][r], x2 = s2[t][r];
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) { x1 += __shfl_xor(x1, o, 64); x2 += __shfl_xor(x2, o, 64); }
-                if (l15 == 0) {
-                    lds_fin[(wave * 2 + 0) * WC + t * 16 + lg * 4 + r] = x1;
-                    lds_fin[(wave * 2 + 1) * WC + t * 16 + lg * 4 + r] = x2;
-                }
-            }
-        __syncthreads();
-        for (int i = tid; i < 2 * WC; i += 256) {
-            const int r = i / WC, c = i - r * WC;
-            const float v = ((lds_fin[(0 * 2 + r) * WC + c] + lds_fin[(1 * 2 + r) * WC + c]) + lds_fin[(2 * 2 + r) * WC + c]) +
-                            lds_fin[(3 * 2 + r) * WC + c];
-            if (c < a.Co) a.stats[((size_t)r * a.Co + c) * gridDim.x + blockIdx.x] = v;
-        }
-    }
+    if (a.stats) mnas_stats_store<TPW>(s1, s2, lds_fin, 0, a.Co, a.stats, tid, wave, l15, lg);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 struct C3xPlan { int tpw, ks; size_t lds; };
 
-int mnas_c3x_enabled() {
-    static int on = -1;
-    if (on < 0) on = mnas_diag_env("MNAS_C3X", 1);
-    return on;
-}
+MNAS_SWITCH(mnas_c3x_enabled, mnas_diag_env("MNAS_C3X", 1))
 static bool c3x_plan(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int kh, int kw, int stride, int pad, C3xPlan* p) {
     if (!mnas_c3x_enabled() || kh != 3 || kw != 3 || pad != 1 || stride != 2) return false;
     if ((Ci & 7) || (Co & 7) || Ci < 8 || Co < 8 || Ho != (Hi - 1) / 2 + 1 || Wo != (Wi - 1) / 2 + 1) return false;

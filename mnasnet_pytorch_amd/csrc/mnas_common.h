@@ -17,6 +17,8 @@ static inline int mnas_diag_env(const char* name, int dflt) { const char* e = ge
 #else
 #define mnas_diag_env(name, dflt) (dflt)
 #endif
+// a host-side switch: `expr` (a mnas_diag_env default, so a constant in the shipped build) evaluated once
+#define MNAS_SWITCH(fn, expr) int fn() { static int on = -1; if (on < 0) on = (expr); return on; }
 
 #define MNAS_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
@@ -47,6 +49,13 @@ __device__ __forceinline__ float mnas_red_coef(const float* red_bn, int C, int r
     const int row = r == 0 ? 0 : (r == 1 ? 1 : (r == 2 ? 6 : 5));
     const float v = red_bn[(size_t)row * C + c], w = red_bn[(size_t)6 * C + c];
     return r == 3 ? -v * w : v;
+}
+// the whole fused-reduce table dst[4][w]: column j = channel c0 + j of the bnbuf, zero from column nvalid on
+__device__ __forceinline__ void mnas_fill_red_table(float* dst, int w, int nvalid, const float* red_bn, int C, int c0, int tid, int nth) {
+    mnas_fill_table(dst, 4 * w, tid, nth, [&](int i) {
+        const int r = i / w, j = i - r * w;
+        return j < nvalid ? mnas_red_coef(red_bn, C, r, c0 + j) : 0.f;
+    });
 }
 // the same for 16-byte items: store(i, load(i)), i = tid, tid + nth, ... < n, four loads in flight before the first store
 template <class L, class S>
@@ -162,6 +171,34 @@ __device__ __forceinline__ void dma_barrier() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 }
+// operand types of __builtin_amdgcn_global_load_lds
+typedef __attribute__((address_space(3))) void* mnas_lds_ptr;
+typedef const __attribute__((address_space(1))) void* mnas_gbl_ptr;
+
+// floor(n / d) for 0 <= n < 2^24, d > 0 with a float reciprocal and one correction step (7 instructions instead of the ~25
+// of the integer division sequence): the im2col address decode of the dense 3x3 / stride-2 forms runs it twice per staged
+// 16-byte slot; k_igemm<dgrad, stride 2> at 112x112 spent 26 k VALU instructions per wave, most of them here.
+// rcp == 0: the exact integer division (the host passes 0 when n can reach 2^24).
+__device__ __forceinline__ int mnas_fdiv(int n, int d, float rcp) {
+    if (rcp == 0.f) return n / d;
+    int q = (int)((float)n * rcp);
+    const int r = n - q * d;
+    q += (r >= d) ? 1 : 0;
+    q -= (r < 0) ? 1 : 0;
+    return q;
+}
+
+// MFMA A fragment read TRANSPOSED from a row-major bf16 LDS tile (ds_read_tr16_b64 pair): the lane gets
+// rows row0 + (lane>>4)*8 + {0..7} of column col0 + (lane&15)
+typedef __attribute__((ext_vector_type(4))) short mnas_s4_t;
+typedef __attribute__((address_space(3))) mnas_s4_t* mnas_lds_s4_ptr;
+__device__ __forceinline__ bf16x8_t mnas_tr_frag(const uint16_t* tile, int ld, int row0, int col0, int lane) {
+    const int i = lane & 15, g = lane >> 4;
+    const uint16_t* p = tile + (row0 + g * 8 + (i >> 2)) * ld + col0 + (i & 3) * 4;
+    const mnas_s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((mnas_lds_s4_ptr)p);
+    const mnas_s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((mnas_lds_s4_ptr)(p + 4 * ld));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
 
 // Stores of the large activation / gradient tensors.  nt = nontemporal (streaming) store: the written tensor is not read
 // again by this kernel; measured on MI355X (tools/probe/bw.hip) a 1-read : 3-write stream sustains 3.3 TB/s with plain
@@ -224,6 +261,51 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// Workgroup (256 threads) reduction of BatchNorm partial statistics held in MFMA accumulator layout: lane (l15 = pixel, lg) holds
+// s1 / s2[t][r] of channel t*16 + lg*4 + r.  16-lane shuffle tree over the pixels, one LDS slot per (wave, channel) in
+// red[4][2][NT*16], the four waves summed in fixed order (no float atomics: bit-reproducible run to run), then
+// stats[2][Co][gridDim.x] for the channels c0 .. c0 + NT*16 - 1 below Co.  The caller owns the barrier that frees `red`.
+// tid / wave / l15 / lg come from the caller: a readfirstlane(tid >> 6) recomputed here is not merged with the kernel's own.
+template <int NT>
+__device__ __forceinline__ void mnas_stats_store(const float (&s1)[NT][4], const float (&s2)[NT][4], float* red, int c0, int Co,
+                                                 float* stats, int tid, int wave, int l15, int lg) {
+    constexpr int NB = NT * 16;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float x1 = s1[t][r], x2 = s2[t][r];
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) { x1 += __shfl_xor(x1, o, 64); x2 += __shfl_xor(x2, o, 64); }
+            if (l15 == 0) {
+                red[(wave * 2 + 0) * NB + t * 16 + lg * 4 + r] = x1;
+                red[(wave * 2 + 1) * NB + t * 16 + lg * 4 + r] = x2;
+            }
+        }
+    __syncthreads();
+    for (int i = tid; i < 2 * NB; i += 256) {
+        const int r = i / NB, cl = i % NB, c = c0 + cl;
+        const float v = ((red[(0 * 2 + r) * NB + cl] + red[(1 * 2 + r) * NB + cl]) + red[(2 * 2 + r) * NB + cl]) + red[(3 * 2 + r) * NB + cl];
+        if (c < Co) stats[((size_t)r * Co + c) * gridDim.x + blockIdx.x] = v;      // [2][Co][P]
+    }
+}
+// The same for per-thread sums of 8 consecutive channels (the 16-byte copy-out paths): thread th < tcols holds r1 / r2[8] of
+// channel chunk th % step; through fin[256][16], the threads of one channel added in thread order (deterministic), then
+// out[2][C][gridDim.x] for the channels c0 .. c0 + nvalid - 1 of the nc the workgroup covers.  Barriers on both sides of `fin`.
+__device__ __forceinline__ void mnas_colsum_store(const float* r1, const float* r2, float* fin, int nc, int tcols, int step, int c0,
+                                                  int nvalid, int C, float* out, int tid) {
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { fin[tid * 16 + j] = r1[j]; fin[tid * 16 + 8 + j] = r2[j]; }
+    __syncthreads();
+    for (int i = tid; i < 2 * nc; i += 256) {
+        const int r = i / nc, c = i % nc;
+        float v = 0.f;
+        for (int th = c >> 3; th < tcols; th += step) v += fin[th * 16 + r * 8 + (c & 7)];
+        if (c < nvalid) out[((size_t)r * C + c0 + c) * gridDim.x + blockIdx.x] = v;      // [2][C][P]
+    }
 }
 
 // XCD-aware remap of a 1-D block id: consecutive LOGICAL ids share an XCD (and its L2).

@@ -62,18 +62,7 @@ __global__ __launch_bounds__(256, (PXW == 4 && CG == 3 ? 2 : 1)) void k_dimg(Dim
     for (int i = tid; i < 2 * a.Ci; i += 256)
         lds_coef[i] = has_coef ? (i < a.Ci ? a.act.scale[i] : a.act.shift[i - a.Ci]) : 0.f;
     for (int i = tid; i < ((a.ni * img_pitch) >> 3); i += 256) ((uint4*)img)[i] = make_uint4(0, 0, 0, 0);   // zero borders (and interiors)
-    if (do_red)
-        for (int i = tid; i < 4 * rows; i += 256) {
-            const int r = i / rows, cc = ct0 * 16 + i % rows;
-            float v = 0.f;
-            if (cc < a.Co) {
-                if (r == 0) v = a.red_bn[cc];
-                else if (r == 1) v = a.red_bn[a.Co + cc];
-                else if (r == 2) v = a.red_bn[6 * a.Co + cc];
-                else v = -a.red_bn[5 * a.Co + cc] * a.red_bn[6 * a.Co + cc];
-            }
-            lds_rc[i] = v;
-        }
+    if (do_red) mnas_fill_red_table(lds_rc, rows, a.Co - ct0 * 16, a.red_bn, a.Co, ct0 * 16, tid, 256);
 
     // this lane's output pixels (one per 16-pixel tile of the wave) and their base offset in the LDS image
     int pbase[PXW], pix[PXW];
@@ -283,11 +272,7 @@ __global__ __launch_bounds__(256, (PXW == 4 && CG == 3 ? 2 : 1)) void k_dimg(Dim
 struct DimgPlan { int pxw, cg, groups, kc, nkc, ni; size_t lds; };
 int mnas_dimg_parts(int mode, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int kh, int kw, int stride, int pad);
 
-int mnas_dimg_enabled() {
-    static int on = -1;
-    if (on < 0) on = mnas_diag_env("MNAS_DIMG", 1);
-    return on;
-}
+MNAS_SWITCH(mnas_dimg_enabled, mnas_diag_env("MNAS_DIMG", 1))
 static bool dimg_plan(int mode, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int kh, int kw, int stride, int pad,
                       DimgPlan* p) {
     if (!mnas_dimg_enabled() || kh != 3 || kw != 3 || pad != 1 || (stride != 1 && stride != 2)) return false;

@@ -57,8 +57,6 @@ __device__ __forceinline__ void dw_step_barrier() {
 #define DW_BW 4         // output columns per thread
 #define DW_RR 8         // ring rows = 2 * G (two buffers of G rows)
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef const __attribute__((address_space(1))) void* gbl_void_ptr;
 
 struct DwArgs {
     int N, H, W, C;
@@ -165,7 +163,7 @@ __device__ __forceinline__ void dw_dma_rows(const DwArgs& a, const DwDma& p, uin
             const int b = wave + j * nwaves;
             if (b >= a.nb) continue;                                          // uniform
             if (p.ok[j])
-                __builtin_amdgcn_global_load_lds((gbl_void_ptr)(rowsrc + p.goff[j]), (lds_void_ptr)(rowdst + b * 256), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((mnas_gbl_ptr)(rowsrc + p.goff[j]), (mnas_lds_ptr)(rowdst + b * 256), 16, 0, 0);
         }
     }
 }

@@ -34,21 +34,9 @@ struct IgemmArgs {
     const void* red_y;       // MODE 1: fused BN-backward reduce target (raw output of the ConvBlock whose g we produce)
     const float* red_bn;
     int nt;                  // nontemporal output stores
-    float rcp_hw, rcp_wo, rcp_ci;   // reciprocals for igemm_fdiv (0 = use the exact integer division)
+    float rcp_hw, rcp_wo, rcp_ci;   // reciprocals for mnas_fdiv (0 = use the exact integer division)
     const float* gate;       // MODE 0, 1x1 (GATE instantiations): per-(image, input channel) multiplier [N][Ci] applied after the activation
 };
-
-// floor(n / d) for 0 <= n < 2^24, d > 0 with a float reciprocal and one correction step (7 instructions instead of the ~25
-// of the integer division sequence): the im2col address decode of the dense 3x3 / stride-2 forms runs it twice per staged
-// 16-byte slot; k_igemm<dgrad, stride 2> at 112x112 spent 26 k VALU instructions per wave, most of them here.
-__device__ __forceinline__ int igemm_fdiv(int n, int d, float rcp) {
-    if (rcp == 0.f) return n / d;
-    int q = (int)((float)n * rcp);
-    const int r = n - q * d;
-    q += (r >= d) ? 1 : 0;
-    q -= (r < 0) ? 1 : 0;
-    return q;
-}
 
 template <int MODE, int NT, int PT, int KCH, bool PIPE, bool PAR2, bool GATE = false>
 __global__ __launch_bounds__(256) void k_igemm(IgemmArgs a) {
@@ -149,12 +137,12 @@ __global__ __launch_bounds__(256) void k_igemm(IgemmArgs a) {
         const bool kok = k < (par2 ? c_K : a.Ktot);
         int ci = k, th = 0, tw = 0;
         if (par2) {
-            const int tj = igemm_fdiv(k, a.Ci, a.rcp_ci);
+            const int tj = mnas_fdiv(k, a.Ci, a.rcp_ci);
             ci = k - tj * a.Ci;
             const int thj = tj / c_ntw, twj = tj - thj * c_ntw;
             th = c_ph ? 2 * thj : 1; tw = c_pw ? 2 * twj : 1;
         } else if (!a.is_pw && MODE != 2) {
-            const int tap = igemm_fdiv(k, a.Ci, a.rcp_ci);
+            const int tap = mnas_fdiv(k, a.Ci, a.rcp_ci);
             ci = k - tap * a.Ci;
             th = tap / a.kw; tw = tap - th * a.kw;
         }
@@ -162,7 +150,7 @@ __global__ __launch_bounds__(256) void k_igemm(IgemmArgs a) {
         int m_next = 0;                            // GATE: first pixel of the image after the tile's first one
         if constexpr (GATE) {
             const int hw = a.Ho * a.Wo;
-            const int nA = igemm_fdiv(tile0 < a.M ? tile0 : a.M - 1, hw, a.rcp_hw);
+            const int nA = mnas_fdiv(tile0 < a.M ? tile0 : a.M - 1, hw, a.rcp_hw);
             m_next = (nA + 1) * hw;
             gsel = 0;
             if (kok) {
@@ -186,8 +174,8 @@ __global__ __launch_bounds__(256) void k_igemm(IgemmArgs a) {
                 // weight order), 3x3 stride 2 pad 1; Hi,Wi = image dims
                 if (m < a.M) {
                     const int hw = a.Ho * a.Wo;
-                    const int n = igemm_fdiv(m, hw, a.rcp_hw), rem = m - n * hw;
-                    const int oh = igemm_fdiv(rem, a.Wo, a.rcp_wo), ow = rem - oh * a.Wo;
+                    const int n = mnas_fdiv(m, hw, a.rcp_hw), rem = m - n * hw;
+                    const int oh = mnas_fdiv(rem, a.Wo, a.rcp_wo), ow = rem - oh * a.Wo;
                     const float* x = (const float*)a.act.data;
                     float f[8];
 #pragma unroll
@@ -205,8 +193,8 @@ __global__ __launch_bounds__(256) void k_igemm(IgemmArgs a) {
             if (par2) {
                 if (m < a.Mc && kok) {
                     const int w2 = a.Wo >> 1, hw2 = (a.Ho >> 1) * w2;
-                    const int n = igemm_fdiv(m, hw2, a.rcp_hw), rem = m - n * hw2;
-                    const int oh2 = igemm_fdiv(rem, w2, a.rcp_wo), ow2 = rem - oh2 * w2;
+                    const int n = mnas_fdiv(m, hw2, a.rcp_hw), rem = m - n * hw2;
+                    const int oh2 = mnas_fdiv(rem, w2, a.rcp_wo), ow2 = rem - oh2 * w2;
                     const int ih = (2 * oh2 + c_ph + 1 - th) >> 1, iw = (2 * ow2 + c_pw + 1 - tw) >> 1;   // exact: parity matches
                     if (ih < a.Hi && iw < a.Wi) {
                         const size_t src = (((size_t)n * a.Hi + ih) * a.Wi + iw) * a.Ci + ci;
@@ -224,8 +212,8 @@ __global__ __launch_bounds__(256) void k_igemm(IgemmArgs a) {
                     src = (size_t)m * a.Ci + k;
                 } else {
                     const int hw = a.Ho * a.Wo;
-                    const int n = igemm_fdiv(m, hw, a.rcp_hw), rem = m - n * hw;
-                    const int oh = igemm_fdiv(rem, a.Wo, a.rcp_wo), ow = rem - oh * a.Wo;
+                    const int n = mnas_fdiv(m, hw, a.rcp_hw), rem = m - n * hw;
+                    const int oh = mnas_fdiv(rem, a.Wo, a.rcp_wo), ow = rem - oh * a.Wo;
                     int ih, iw;
                     if (MODE == 0) {
                         ih = oh * a.stride + th - a.pad;
@@ -305,6 +293,7 @@ __global__ __launch_bounds__(256) void k_igemm(IgemmArgs a) {
         for (int r = 0; r < 4; ++r) { s1[nt][r] = 0.f; s2[nt][r] = 0.f; }
     // fused BN-backward reduce (MODE 1): per-channel (s, t, invstd, -mean*invstd) of the target layer in LDS
     const bool do_red = (MODE == 1) && a.red_y != nullptr;
+    // (its own chain, not mnas_red_coef(): with the common helper the MODE 1 instances take 4 more VGPRs, one of them a wave less)
     if (do_red) {
         for (int i = tid; i < 4 * NT * 16; i += 256) {
             const int r = i / (NT * 16), co = n0 + i % (NT * 16);
@@ -333,8 +322,8 @@ __global__ __launch_bounds__(256) void k_igemm(IgemmArgs a) {
         if constexpr (!par2) return ml < a.M ? ml : -1;
         if (ml >= a.Mc) return -1;
         const int w2 = a.Wo >> 1, hw2 = (a.Ho >> 1) * w2;
-        const int n = igemm_fdiv(ml, hw2, a.rcp_hw), rem = ml - n * hw2;
-        const int oh2 = igemm_fdiv(rem, w2, a.rcp_wo), ow2 = rem - oh2 * w2;
+        const int n = mnas_fdiv(ml, hw2, a.rcp_hw), rem = ml - n * hw2;
+        const int oh2 = mnas_fdiv(rem, w2, a.rcp_wo), ow2 = rem - oh2 * w2;
         return (n * a.Ho + 2 * oh2 + e_ph) * a.Wo + 2 * ow2 + e_pw;
     };
     if (PIPE && (int)blockIdx.x < ntiles) {
@@ -467,29 +456,8 @@ __global__ __launch_bounds__(256) void k_igemm(IgemmArgs a) {
     }
 
     if ((MODE != 1 || do_red) && a.stats) {
-        // deterministic workgroup reduction: 16-lane shuffle tree, one LDS slot per (wave, channel), waves summed in
-        // fixed order (no float atomics: results are bit-reproducible run to run)
-        float* red4 = (float*)lds_a;                    // [4 waves][2][NT*16], the activation tile is dead by now
-        __syncthreads();
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float x1 = s1[nt][r], x2 = s2[nt][r];
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) { x1 += __shfl_xor(x1, o, 64); x2 += __shfl_xor(x2, o, 64); }
-                if (l15 == 0) {
-                    red4[(wave * 2 + 0) * NT * 16 + nt * 16 + lg * 4 + r] = x1;
-                    red4[(wave * 2 + 1) * NT * 16 + nt * 16 + lg * 4 + r] = x2;
-                }
-            }
-        __syncthreads();
-        for (int i = tid; i < 2 * NT * 16; i += 256) {
-            const int r = i / (NT * 16), cl = i % (NT * 16), c = n0 + cl;
-            const float v = ((red4[(0 * 2 + r) * NT * 16 + cl] + red4[(1 * 2 + r) * NT * 16 + cl]) +
-                             red4[(2 * 2 + r) * NT * 16 + cl]) + red4[(3 * 2 + r) * NT * 16 + cl];
-            if (c < a.Co) a.stats[((size_t)r * a.Co + c) * gridDim.x + blockIdx.x] = v;   // [2][Co][P]
-        }
+        __syncthreads();                                // the activation tile is dead by now: [4 waves][2][NT*16]
+        mnas_stats_store<NT>(s1, s2, (float*)lds_a, n0, a.Co, a.stats, tid, wave, l15, lg);
     }
 }
 

@@ -27,9 +27,6 @@
 #define MNAS_PWB_PF 1        // 0: no form prefetches (A/B builds)
 #endif
 
-typedef __attribute__((ext_vector_type(4))) short pw_s4_t;
-typedef __attribute__((address_space(3))) pw_s4_t* pw_lds_s4_ptr;
-
 struct PwBwdArgs {
     int M, Ci, Co, Kd;       // Kd = Co rounded up to 32 (dgrad reduction length, row length of the packed weights)
     MnasActIn x;
@@ -48,15 +45,6 @@ struct PwBwdArgs {
     int gin_masked;          // out-stage forms: store dz = gin*[s*x+t>0] (the fused reduce's mask) instead of gin
     int seg_px;              // > 0: segment mode (see the tile walk)
 };
-
-__device__ __forceinline__ bf16x8_t pw_tr_frag(const uint16_t* tile, int ld, int row0, int col0, int lane) {
-    // rows row0 + (lane>>4)*8 + {0..7}, column col0 + (lane&15)   (see mnas_wgrad.hip)
-    const int i = lane & 15, g = lane >> 4;
-    const uint16_t* p = tile + (row0 + g * 8 + (i >> 2)) * ld + col0 + (i & 3) * 4;
-    const pw_s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pw_lds_s4_ptr)p);
-    const pw_s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pw_lds_s4_ptr)(p + 4 * ld));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 
 // OS (out-stage; the narrowing convs, where gin is the WIDE tensor): the input-gradient tile goes through LDS (the act(x) tile
 // is dead after the weight-gradient MFMAs) and leaves as 16-byte nontemporal stores of whole row segments -- the tile's
@@ -353,13 +341,13 @@ __global__ __launch_bounds__(256, 2) void k_pw_bwd(PwBwdArgs a) {
             bf16x8_t oth[NOTH];
 #pragma unroll
             for (int j = 0; j < NOTH; ++j)
-                oth[j] = OWN_O ? pw_tr_frag(tile_a, lda, ks * 32, j * 16, lane) : pw_tr_frag(tile_d, ldd, ks * 32, j * 16, lane);
+                oth[j] = OWN_O ? mnas_tr_frag(tile_a, lda, ks * 32, j * 16, lane) : mnas_tr_frag(tile_d, ldd, ks * 32, j * 16, lane);
 #pragma unroll
             for (int i = 0; i < NOWN; ++i) {
                 const int own = wave + 4 * i;
                 if (own >= (OWN_O ? NTO : NTI)) continue;        // uniform per wave
-                const bf16x8_t mine = OWN_O ? pw_tr_frag(tile_d, ldd, ks * 32, own * 16, lane)
-                                            : pw_tr_frag(tile_a, lda, ks * 32, own * 16, lane);
+                const bf16x8_t mine = OWN_O ? mnas_tr_frag(tile_d, ldd, ks * 32, own * 16, lane)
+                                            : mnas_tr_frag(tile_a, lda, ks * 32, own * 16, lane);
 #pragma unroll
                 for (int j = 0; j < NOTH; ++j)
                     acc_w[i][j] = OWN_O ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(mine, oth[j], acc_w[i][j], 0, 0, 0)
@@ -539,11 +527,7 @@ __global__ __launch_bounds__(256, 2) void k_pw_bwd(PwBwdArgs a) {
     }
 }
 
-static int pw_bwd_outstage() {
-    static int on = -1;
-    if (on < 0) on = mnas_diag_env("MNAS_PWB_OS", 2);      // 0 off, 1 narrowing convs, 2 + the 14x14 channel slices
-    return on;
-}
+static MNAS_SWITCH(pw_bwd_outstage, mnas_diag_env("MNAS_PWB_OS", 2))  // 0 off, 1 narrowing convs, 2 + the 14x14 channel slices
 template <int NTO, int NTI, int PT>
 static int launch_pw_bwd(const PwBwdArgs& a, int nparts, hipStream_t stream, int nslices = 1) {
     constexpr int BP = 64 * PT, COP = NTO * 16, CIP = NTI * 16;

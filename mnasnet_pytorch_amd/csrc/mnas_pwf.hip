@@ -29,8 +29,6 @@
 #endif
 #include <cstdlib>
 
-typedef __attribute__((address_space(3))) void* pwf_lds_ptr;
-typedef const __attribute__((address_space(1))) void* pwf_gbl_ptr;
 
 struct PwfArgs {
     int M, Ci, Co;
@@ -108,18 +106,7 @@ __global__ __launch_bounds__(256) void k_pwf(PwfArgs a) {
             }
             lds_coef[i] = v;
         }
-        if (do_red)
-            for (int i = tid; i < 4 * NB; i += 256) {      // (s, t, invstd, -mean*invstd) of the reduce target, as k_igemm
-                const int r = i / NB, co = n0 + i % NB;
-                float v = 0.f;
-                if (co < a.Co) {
-                    if (r == 0) v = a.red_bn[0 * a.Co + co];
-                    else if (r == 1) v = a.red_bn[1 * a.Co + co];
-                    else if (r == 2) v = a.red_bn[6 * a.Co + co];
-                    else v = -a.red_bn[5 * a.Co + co] * a.red_bn[6 * a.Co + co];
-                }
-                lds_redc[i] = v;
-            }
+        if (do_red) mnas_fill_red_table(lds_redc, NB, a.Co - n0, a.red_bn, a.Co, n0, tid, 256);
     }
     __syncthreads();
 
@@ -135,9 +122,9 @@ __global__ __launch_bounds__(256) void k_pwf(PwfArgs a) {
             const int k = k0 + ja[i] * 8;
             if (ja[i] >= 0 && k < a.Ci && tile0 + pa[i] < a.M) {
                 const size_t off = (size_t)(tile0 + pa[i]) * a.Ci + k;
-                __builtin_amdgcn_global_load_lds((pwf_gbl_ptr)(src + off), (pwf_lds_ptr)(dst + 256 * i + wave * 64), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((mnas_gbl_ptr)(src + off), (mnas_lds_ptr)(dst + 256 * i + wave * 64), 16, 0, 0);
                 if (MODE == 1 && has_coef)
-                    __builtin_amdgcn_global_load_lds((pwf_gbl_ptr)(srcy + off), (pwf_lds_ptr)(dsty + 256 * i + wave * 64), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((mnas_gbl_ptr)(srcy + off), (mnas_lds_ptr)(dsty + 256 * i + wave * 64), 16, 0, 0);
             }
         }
     };
@@ -148,8 +135,8 @@ __global__ __launch_bounds__(256) void k_pwf(PwfArgs a) {
             if (i >= nw) break;
             const int k = k0 + jw[i] * 8;
             if (jw[i] >= 0 && k < a.Kpad)
-                __builtin_amdgcn_global_load_lds((pwf_gbl_ptr)(a.w + (size_t)(n0 + pw_[i]) * a.Kpad + k),
-                                                 (pwf_lds_ptr)(dst + 256 * i + wave * 64), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((mnas_gbl_ptr)(a.w + (size_t)(n0 + pw_[i]) * a.Kpad + k),
+                                                 (mnas_lds_ptr)(dst + 256 * i + wave * 64), 16, 0, 0);
         }
     };
     // Single-k-step layers (Ci <= 32: 16 -> 48 at 112x112, 24 -> 72 at 56x56 -- bandwidth-bound, 5.4 TB/s on a materialised input):
@@ -345,43 +332,12 @@ __global__ __launch_bounds__(256) void k_pwf(PwfArgs a) {
     }
 
     if constexpr (MODE == 1) {
-        if (do_red && a.stats) {
-            // per-thread sums -> per-channel: the threads of one channel column added in thread order (deterministic)
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { lds_red[tid * 16 + j] = r1[j]; lds_red[tid * 16 + 8 + j] = r2[j]; }
-            __syncthreads();
-            for (int i = tid; i < 2 * NB; i += 256) {
-                const int r = i / NB, cl = i % NB, c = n0 + cl;
-                float v = 0.f;
-                for (int th = cl >> 3; th < TCOLS; th += NCH8) v += lds_red[th * 16 + r * 8 + (cl & 7)];
-                if (c < a.Co) a.stats[((size_t)r * a.Co + c) * gridDim.x + blockIdx.x] = v;
-            }
-        }
+        if (do_red && a.stats) mnas_colsum_store(r1, r2, lds_red, NB, TCOLS, NCH8, n0, a.Co - n0, a.Co, a.stats, tid);
         return;
     }
     if (a.stats) {
-        // deterministic workgroup reduction (as k_igemm): 16-lane shuffle tree, one LDS slot per (wave, channel), waves in order
         __syncthreads();
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float x1 = s1[nt][r], x2 = s2[nt][r];
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) { x1 += __shfl_xor(x1, o, 64); x2 += __shfl_xor(x2, o, 64); }
-                if (l15 == 0) {
-                    lds_red[(wave * 2 + 0) * NB + nt * 16 + lg * 4 + r] = x1;
-                    lds_red[(wave * 2 + 1) * NB + nt * 16 + lg * 4 + r] = x2;
-                }
-            }
-        __syncthreads();
-        for (int i = tid; i < 2 * NB; i += 256) {
-            const int r = i / NB, cl = i % NB, c = n0 + cl;
-            const float v = ((lds_red[(0 * 2 + r) * NB + cl] + lds_red[(1 * 2 + r) * NB + cl]) + lds_red[(2 * 2 + r) * NB + cl]) +
-                            lds_red[(3 * 2 + r) * NB + cl];
-            if (c < a.Co) a.stats[((size_t)r * a.Co + c) * gridDim.x + blockIdx.x] = v;      // [2][Co][P]
-        }
+        mnas_stats_store<NT>(s1, s2, lds_red, n0, a.Co, a.stats, tid, wave, l15, lg);
     }
 }
 

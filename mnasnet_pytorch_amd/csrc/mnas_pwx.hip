@@ -150,11 +150,7 @@ __global__ __launch_bounds__(64 * NW) void k_pwx(PwxArgs a) {
 // ---- host side ------------------------------------------------------------------------------------------------------
 struct PwxPlan { int tpw, ks, nw, nblocks; size_t lds; };
 
-int mnas_pwx_enabled() {
-    static int on = -1;
-    if (on < 0) on = mnas_diag_env("MNAS_PWX", 1);
-    return on;
-}
+MNAS_SWITCH(mnas_pwx_enabled, mnas_diag_env("MNAS_PWX", 1))
 static bool pwx_plan(int M, int Ci, int Co, PwxPlan* p) {
     if (!mnas_pwx_enabled() || (Ci & 7) || (Co & 7) || Ci < 8 || Co < 8 || M < 1) return false;
     // widening convs on the <= 28x28 maps (bs 256).  192 -> 1152 at 7x7 (three cout blocks over grid.y, 6 waves x 4 tiles x 6 k-steps)

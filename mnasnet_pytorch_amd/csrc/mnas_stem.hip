@@ -17,9 +17,6 @@
 // Roofline: HBM (reads 154 MB image + writes 205 MB / reads 154 + 411 MB at batch 256).
 #include "mnas_common.h"
 
-typedef __attribute__((ext_vector_type(4))) short st_s4_t;
-typedef __attribute__((address_space(3))) st_s4_t* st_lds_s4_ptr;
-
 struct StemArgs {
     int N, H, W, Ho, Wo;
     int RB, nbh;             // output rows per band, bands per image
@@ -145,40 +142,12 @@ __global__ __launch_bounds__(256) void k_stem_fwd(StemArgs a) {
         }
     }
     if (a.stats) {
-        // deterministic workgroup reduction (as k_igemm): 16-lane shuffle tree, one LDS slot per (wave, channel), waves in order
         __syncthreads();
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float x1 = s1[ct][r], x2 = s2[ct][r];
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) { x1 += __shfl_xor(x1, o, 64); x2 += __shfl_xor(x2, o, 64); }
-                if (l15 == 0) {
-                    lds_red[(wave * 2 + 0) * 32 + ct * 16 + lg * 4 + r] = x1;
-                    lds_red[(wave * 2 + 1) * 32 + ct * 16 + lg * 4 + r] = x2;
-                }
-            }
-        __syncthreads();
-        if (tid < 64) {
-            const int r = tid >> 5, c = tid & 31;
-            const float v = ((lds_red[(0 * 2 + r) * 32 + c] + lds_red[(1 * 2 + r) * 32 + c]) + lds_red[(2 * 2 + r) * 32 + c]) +
-                            lds_red[(3 * 2 + r) * 32 + c];
-            a.stats[((size_t)r * 32 + c) * gridDim.x + blockIdx.x] = v;
-        }
+        mnas_stats_store<2>(s1, s2, lds_red, 0, 32, a.stats, tid, wave, l15, lg);
     }
 }
 
 // ---- weight gradient -----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bf16x8_t stem_tr_frag(const uint16_t* tile, int ld, int row0, int col0, int lane) {
-    // rows row0 + (lane>>4)*8 + {0..7}, column col0 + (lane&15)   (see mnas_wgrad.hip)
-    const int i = lane & 15, g = lane >> 4;
-    const uint16_t* p = tile + (row0 + g * 8 + (i >> 2)) * ld + col0 + (i & 3) * 4;
-    const st_s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((st_lds_s4_ptr)p);
-    const st_s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((st_lds_s4_ptr)(p + 4 * ld));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 __global__ __launch_bounds__(256) void k_stem_wgrad(StemArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int LDD = 40;                                  // dy tile row pitch (32 couts + 8 pad)
@@ -258,7 +227,7 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(StemArgs a) {
             }
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) {
-                const bf16x8_t af = stem_tr_frag(tile_d, LDD, s * 32, ct * 16, lane);
+                const bf16x8_t af = mnas_tr_frag(tile_d, LDD, s * 32, ct * 16, lane);
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt) acc[ct][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[kt], acc[ct][kt], 0, 0, 0);
             }
@@ -289,11 +258,7 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(StemArgs a) {
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // preferred persistent grid (host-side, no launch): which = 0 forward, 1 weight gradient; -1 = not a band shape
 extern "C" int mnas_stem_parts(int which, int N, int H, int W, int Co);
-int mnas_stem_band_enabled() {
-    static int on = -1;
-    if (on < 0) on = mnas_diag_env("MNAS_STEM_BAND", 1);
-    return on;
-}
+MNAS_SWITCH(mnas_stem_band_enabled, mnas_diag_env("MNAS_STEM_BAND", 1))
 static bool stem_band_ok(int N, int H, int W, int Ho, int Wo, int Co, bool wgrad) {
     if (!mnas_stem_band_enabled() || Co != 32 || (W & 3) || W < 8 || H < 2 || N < 1) return false;
     if (Ho != (H - 1) / 2 + 1 || Wo != (W - 1) / 2 + 1) return false;

@@ -15,9 +15,6 @@
 // 195 us for 24->16 at 112x112 against a 52 us bandwidth floor.
 #include "mnas_common.h"
 
-typedef __attribute__((address_space(3))) void* tc_lds_ptr;
-typedef const __attribute__((address_space(1))) void* tc_gbl_ptr;
-
 struct TconvArgs {
     int M2;                  // super-pixels = N * Ho * Wo (dy pixels)
     int Ho, Wo, Co, Ci;      // dy plane / channels, gin channels; gin plane = 2Ho x 2Wo
@@ -31,15 +28,6 @@ struct TconvArgs {
     const void* red_y;
     const float* red_bn;
 };
-
-__device__ __forceinline__ int tc_fdiv(int n, int d, float rcp) {
-    if (rcp == 0.f) return n / d;
-    int q = (int)((float)n * rcp);
-    const int r = n - q * d;
-    q += (r >= d) ? 1 : 0;
-    q -= (r < 0) ? 1 : 0;
-    return q;
-}
 
 template <int NT, int PT>
 __global__ __launch_bounds__(256) void k_tconv(TconvArgs a) {
@@ -72,16 +60,7 @@ __global__ __launch_bounds__(256) void k_tconv(TconvArgs a) {
     {
         const int nz = (2 * BP + NB) * pitch;
         for (int i = tid; i < nz; i += 256) lds_a[i] = make_uint4(0, 0, 0, 0);
-        if (do_red)
-            for (int i = tid; i < 4 * a.Ci; i += 256) {
-                const int r = i / a.Ci, c = i - r * a.Ci;
-                float v;
-                if (r == 0) v = a.red_bn[0 * a.Ci + c];
-                else if (r == 1) v = a.red_bn[1 * a.Ci + c];
-                else if (r == 2) v = a.red_bn[6 * a.Ci + c];
-                else v = -a.red_bn[5 * a.Ci + c] * a.red_bn[6 * a.Ci + c];
-                lds_redc[i] = v;
-            }
+        if (do_red) mnas_fill_red_table(lds_redc, a.Ci, a.Ci, a.red_bn, a.Ci, 0, tid, 256);
     }
     __syncthreads();
     // weights: resident
@@ -102,14 +81,14 @@ __global__ __launch_bounds__(256) void k_tconv(TconvArgs a) {
             const int m = tile0 + pa[i];
             if (m >= a.M2) continue;
             const int hw = a.Ho * a.Wo;
-            const int n = tc_fdiv(m, hw, a.rcp_hw), rem = m - n * hw;
-            const int ii = tc_fdiv(rem, a.Wo, a.rcp_wo), jj = rem - ii * a.Wo;
+            const int n = mnas_fdiv(m, hw, a.rcp_hw), rem = m - n * hw;
+            const int ii = mnas_fdiv(rem, a.Wo, a.rcp_wo), jj = rem - ii * a.Wo;
             const int nb = ja[i] / co8, c = ja[i] - nb * co8;
             const int y = ii + (nb >> 1), x = jj + (nb & 1);
             if (y < a.Ho && x < a.Wo) {
                 ok |= 1u << i;
-                __builtin_amdgcn_global_load_lds((tc_gbl_ptr)(a.dy + (((size_t)n * a.Ho + y) * a.Wo + x) * a.Co + c * 8),
-                                                 (tc_lds_ptr)(dst + 256 * i + wave * 64), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((mnas_gbl_ptr)(a.dy + (((size_t)n * a.Ho + y) * a.Wo + x) * a.Co + c * 8),
+                                                 (mnas_lds_ptr)(dst + 256 * i + wave * 64), 16, 0, 0);
             }
         }
         if (slot) ok1 = ok; else ok0 = ok;
@@ -145,8 +124,8 @@ __global__ __launch_bounds__(256) void k_tconv(TconvArgs a) {
             yreg[k] = make_uint4(0, 0, 0, 0);
             if (tid < tcols && p < BP && m < a.M2) {
                 const int hw = a.Ho * a.Wo;
-                const int n = tc_fdiv(m, hw, a.rcp_hw), rem = m - n * hw;
-                const int ii = tc_fdiv(rem, a.Wo, a.rcp_wo), jj = rem - ii * a.Wo;
+                const int n = mnas_fdiv(m, hw, a.rcp_hw), rem = m - n * hw;
+                const int ii = mnas_fdiv(rem, a.Wo, a.rcp_wo), jj = rem - ii * a.Wo;
                 ooff[k] = (((n * 2 * a.Ho + 2 * ii + (ocls >> 1)) * 2 * a.Wo + 2 * jj + (ocls & 1)) * a.Ci + occ * 8);
                 if (do_red) yreg[k] = *(const uint4*)((const uint16_t*)a.red_y + ooff[k]);
             }

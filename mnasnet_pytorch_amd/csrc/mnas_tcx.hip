@@ -35,15 +35,6 @@ struct TcxArgs {
     const float* red_bn;
 };
 
-__device__ __forceinline__ int tcx_fdiv(int n, int d, float rcp) {
-    if (rcp == 0.f) return n / d;
-    int q = (int)((float)n * rcp);
-    const int r = n - q * d;
-    q += (r >= d) ? 1 : 0;
-    q -= (r < 0) ? 1 : 0;
-    return q;
-}
-
 // TPW: 16-row tiles covering the block's result channels; KSM: k-steps of the four-neighbour class (compact K = 4*Co)
 template <int TPW, int KSM>
 __global__ __launch_bounds__(256) void k_tcx(TcxArgs a) {
@@ -62,18 +53,7 @@ __global__ __launch_bounds__(256) void k_tcx(TcxArgs a) {
     const int nslots = (1 + ph) * (1 + pw);                        // neighbours this class reads
     const int kc = nslots * a.Co;                                  // compact K of the class
 
-    if (do_red)
-        for (int i = tid; i < 4 * WC; i += 256) {
-            const int r = i / WC, c = i - r * WC, cc = ci0 + c;
-            float v = 0.f;
-            if (c < cin) {
-                if (r == 0) v = a.red_bn[cc];
-                else if (r == 1) v = a.red_bn[a.Ci + cc];
-                else if (r == 2) v = a.red_bn[6 * a.Ci + cc];
-                else v = -a.red_bn[5 * a.Ci + cc] * a.red_bn[6 * a.Ci + cc];
-            }
-            lds_rc[i] = v;
-        }
+    if (do_red) mnas_fill_red_table(lds_rc, WC, cin, a.red_bn, a.Ci, ci0, tid, 256);
     // ---- this lane's k positions: k-step ks covers compact k = ks*32 + lg*8 .. +7 = 8 channels co.. of neighbour slot `slot`;
     // slot -> neighbour (dh, dw): class (0,1) reads (0,0),(0,1); (1,0) reads (0,0),(1,0); (1,1) all four in packing order
     int koff[KSM];                                                 // pixel / channel offset into dy, -1: past the class's K
@@ -124,8 +104,8 @@ __global__ __launch_bounds__(256) void k_tcx(TcxArgs a) {
     auto issue = [&](int g) {
         const int m = g * 16 + l15;
         const bool mok = m < a.M2;
-        const int n = mok ? tcx_fdiv(m, hw, a.rcp_hw) : 0, rem = m - n * hw;
-        const int i = mok ? tcx_fdiv(rem, a.Wo, a.rcp_wo) : 0, j = rem - i * a.Wo;
+        const int n = mok ? mnas_fdiv(m, hw, a.rcp_hw) : 0, rem = m - n * hw;
+        const int i = mok ? mnas_fdiv(rem, a.Wo, a.rcp_wo) : 0, j = rem - i * a.Wo;
         const uint16_t* base = a.dy + (size_t)(mok ? m : 0) * a.Co;
 #pragma unroll
         for (int ks = 0; ks < KSM; ++ks) {
@@ -141,8 +121,8 @@ __global__ __launch_bounds__(256) void k_tcx(TcxArgs a) {
             ooff_n[p] = -1;
             yv_n[p] = make_uint4(0, 0, 0, 0);
             if (q < 16 * cpp && mm < a.M2) {
-                const int n2 = tcx_fdiv(mm, hw, a.rcp_hw), rem2 = mm - n2 * hw;
-                const int i2 = tcx_fdiv(rem2, a.Wo, a.rcp_wo), j2 = rem2 - i2 * a.Wo;
+                const int n2 = mnas_fdiv(mm, hw, a.rcp_hw), rem2 = mm - n2 * hw;
+                const int i2 = mnas_fdiv(rem2, a.Wo, a.rcp_wo), j2 = rem2 - i2 * a.Wo;
                 ooff_n[p] = ((n2 * 2 * a.Ho + 2 * i2 + ph) * (2 * a.Wo) + 2 * j2 + pw) * a.Ci + ci0 + ch * 8;
                 if (do_red) yv_n[p] = *(const uint4*)((const uint16_t*)a.red_y + ooff_n[p]);
             }
@@ -211,11 +191,7 @@ __global__ __launch_bounds__(256) void k_tcx(TcxArgs a) {
 // ---- host side ------------------------------------------------------------------------------------------------------
 struct TcxPlan { int tpw, ksm, cib, nblocks; size_t lds; };
 
-int mnas_tcx_enabled() {
-    static int on = -1;
-    if (on < 0) on = mnas_diag_env("MNAS_TCX", 1);
-    return on;
-}
+MNAS_SWITCH(mnas_tcx_enabled, mnas_diag_env("MNAS_TCX", 1))
 static bool tcx_plan(int Ho, int Wo, int Co, int Ci, TcxPlan* p) {
     if (!mnas_tcx_enabled() || (Co & 7) || (Ci & 7) || Co < 8 || Ci < 8 || Ho < 1 || Wo < 1) return false;
     const int ksm = (4 * Co + 31) / 32;
@@ -317,18 +293,7 @@ __global__ __launch_bounds__(512) void k_tcr(TcrArgs a) {
     const int npc = a.Ho * a.Wo;                                   // pixels per class
 
     for (int i = tid; i < img_elems >> 3; i += 512) ((uint4*)img)[i] = make_uint4(0, 0, 0, 0);           // zero border (and interior)
-    if (do_red)
-        for (int i = tid; i < 4 * NB; i += 512) {
-            const int r = i / NB, cc = ci0 + i % NB;
-            float v = 0.f;
-            if (cc < a.Ci) {
-                if (r == 0) v = a.red_bn[cc];
-                else if (r == 1) v = a.red_bn[a.Ci + cc];
-                else if (r == 2) v = a.red_bn[6 * a.Ci + cc];
-                else v = -a.red_bn[5 * a.Ci + cc] * a.red_bn[6 * a.Ci + cc];
-            }
-            lds_rc[i] = v;
-        }
+    if (do_red) mnas_fill_red_table(lds_rc, NB, a.Ci - ci0, a.red_bn, a.Ci, ci0, tid, 512);
     // ---- weight fragments: class c, this wave's k-steps ks = kq + 4j of the class's compact K; LDS offset of the lane's 8 channels
     bf16x8_t wf0[KQ0], wf1[KQ1], wf2[KQ1], wf3[KQ3];
     int to0[KQ0], to1[KQ1], to2[KQ1], to3[KQ3];

@@ -15,9 +15,6 @@
 // dy-on-load and act-on-load are applied while staging, exactly as in mnas_gemm.hip.
 #include "mnas_common.h"
 
-typedef __attribute__((ext_vector_type(4))) short s4_t;
-typedef __attribute__((address_space(3))) s4_t* lds_s4_ptr;
-
 struct WgradArgs {
     int M, Hi, Wi, Ci, Ho, Wo, Co;
     int kh, kw, stride, pad;
@@ -29,15 +26,6 @@ struct WgradArgs {
 
 #define WG_BPIX 128
 #define WG_T 4            // 4x4 tiles of 16x16 per workgroup slab
-
-__device__ __forceinline__ bf16x8_t tr_frag(const uint16_t* tile, int ld, int row0, int col0, int lane) {
-    // rows row0 + (lane>>4)*8 + {0..7}, column col0 + (lane&15)
-    const int i = lane & 15, g = lane >> 4;
-    const uint16_t* p = tile + (row0 + g * 8 + (i >> 2)) * ld + col0 + (i & 3) * 4;
-    const s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)p);
-    const s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(p + 4 * ld));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 
 template <bool STEM>
 __global__ __launch_bounds__(256, 2) void k_wgrad(WgradArgs a) {
@@ -205,11 +193,11 @@ __global__ __launch_bounds__(256, 2) void k_wgrad(WgradArgs a) {
         bf16x8_t bf[WG_T];
 #pragma unroll
         for (int kt = 0; kt < WG_T; ++kt)
-            if (kt < ktn) bf[kt] = tr_frag(tile_a, lda, wave * 32, kt * 16, lane);
+            if (kt < ktn) bf[kt] = mnas_tr_frag(tile_a, lda, wave * 32, kt * 16, lane);
 #pragma unroll
         for (int ct = 0; ct < WG_T; ++ct) {
             if (ct >= ctn) continue;
-            const bf16x8_t af = tr_frag(tile_d, ldd, wave * 32, ct * 16, lane);
+            const bf16x8_t af = mnas_tr_frag(tile_d, ldd, wave * 32, ct * 16, lane);
 #pragma unroll
             for (int kt = 0; kt < WG_T; ++kt)
                 if (kt < ktn) acc[ct][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[kt], acc[ct][kt], 0, 0, 0);
@@ -442,11 +430,11 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_t(WgradArgs a) {
             bf16x8_t bf[KT];
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt)
-                if (kt < ktn) bf[kt] = tr_frag(ta, LDA, ks * 32, (wc * KT + kt) * 16, lane);
+                if (kt < ktn) bf[kt] = mnas_tr_frag(ta, LDA, ks * 32, (wc * KT + kt) * 16, lane);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
                 if (ct >= ctn) continue;
-                const bf16x8_t af = tr_frag(td, LDD, ks * 32, (wr * CT + ct) * 16, lane);
+                const bf16x8_t af = mnas_tr_frag(td, LDD, ks * 32, (wr * CT + ct) * 16, lane);
 #pragma unroll
                 for (int kt = 0; kt < KT; ++kt)
                     if (kt < ktn) acc[ct][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf[kt], acc[ct][kt], 0, 0, 0);

@@ -173,7 +173,7 @@ def _run_case(cs, expect_route, expect_inst=None, nparts=(13, 38)):
 #   DENSE[8], [10] are stride 2 onto <= 64 pixels, which k_dimg refuses: k_igemm.  No entry of DENSE reaches k_dimg with stride 2
 #   (it needs 64 < output plane <= 256); DIMG_S2 below adds that form, which the bench configuration runs (40 -> 80, 28^2 -> 14^2).
 PW_FWD_ROUTE = ["k_pwf", "k_igemm", "k_igemm", "k_pwx", "k_pws", "k_igemm", "k_pws", "k_pwx", "k_pws", "k_pws", "k_igemm",
-                "k_pwx", "k_pwx", "k_pwx", "k_pwx", "k_pwx", "k_pws"]          # [16] !
+                "k_pwx", "k_pwx", "k_pwx", "k_pwx", "k_pwx", "k_pws", "k_pwf"]          # [16] !
 DENSE_FWD_ROUTE = ["k_igemm"] * 5 + ["k_dimg", "k_c3r", "k_c3r", "k_igemm", "k_dimg", "k_igemm"] + ["k_c3r"] * 4 + ["k_c3x"] * 3   # [6] [7] [8] [10] !
 
 

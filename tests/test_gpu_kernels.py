@@ -66,6 +66,9 @@ PW = [  # N,H,W,Ci,Co
     # the widening convs of the <= 28x28 maps: weight-stationary kernel (csrc/mnas_pwx.hip); ragged last pixel group, several
     # groups per workgroup (nparts 13), cout counts that do and do not fill the waves' tiles
     (3, 14, 14, 96, 576), (5, 13, 11, 80, 480), (2, 28, 27, 40, 240), (7, 9, 9, 96, 568), (1, 5, 3, 40, 232), (9, 7, 7, 192, 1152),
+    # the DMA-pipelined forward (csrc/mnas_pwf.hip) with a ragged last cout tile (40 of 48) and a ragged last pixel tile (198 pixels):
+    # its statistics epilogue stores under the c < Co guard
+    (2, 9, 11, 24, 40),
 ]
 
 
@@ -281,7 +284,7 @@ def test_dense_wgrad_slabs_and_empty_splits(shape, nsplit):
 DW = [  # N,H,W,C,k
     (2, 12, 12, 48, 3), (2, 12, 12, 72, 5), (2, 7, 9, 240, 5), (3, 14, 14, 480, 3), (5, 7, 7, 1152, 3),
     (2, 33, 20, 32, 3), (2, 28, 28, 72, 5), (3, 7, 7, 576, 5), (1, 40, 24, 120, 5),
-    (3, 14, 14, 576, 5), (2, 14, 13, 96, 5),          # the 14-wide planes (forward: 2-column strips, round 6)
+    (3, 14, 14, 576, 5), (2, 14, 13, 96, 5),          # the 14-wide planes, on the 4-column strips like every other width
 ]
 
 
