@@ -338,9 +338,11 @@ def check_gemm_bound(hip, ref, S, K, what):
     adds at most half an ulp, which is at most 2^-8*|value| (reached just above a power of two; 2^-9 just below one).
     Asserted for EVERY element: |hip - ref| <= 2^-8*|ref| + (K+1)*2^-22*S -- the store term is the exact worst case, the
     accumulation term carries a factor of two (it also absorbs a value that the fp32 error moves across a rounding
-    boundary or a power of two).  Correct kernels were measured at up to 0.99 of this bound.  Not covered: an operand
-    formed on load (act-on-load, dy-on-load) -- one bf16 ulp of an operand computed in fp32 on the device and in fp64 on
-    the host is outside this derivation; those launches keep the max-normalised tolerance."""
+    boundary or a power of two).  Correct kernels were measured at up to 0.99 of this bound.  An operand formed on load
+    (act-on-load, dy-on-load) is outside this derivation: check_onload_bound below is this bound plus the operand's
+    interval.  Not covered by any per-element bound: the squeeze-excite kernels and the gated act-on-load (act8g), the
+    stem's weight and input gradients, mnas_add_act / the pooling glue, and the BatchNorm finalizes (all of which keep
+    their max-normalised tolerances)."""
     hip, ref, S = hip.double(), ref.double(), S.double()
     assert hip.shape == ref.shape == S.shape, (what, hip.shape, ref.shape, S.shape)
     err = (hip - ref).abs()
@@ -351,3 +353,358 @@ def check_gemm_bound(hip, ref, S, K, what):
         raise AssertionError("%s: %d of %d elements outside the per-element bound; first at %s: got %r, fp64 %r, |err| %.3e > bound %.3e"
                              % (what, int(bad.sum()), bad.numel(), idx, float(hip[idx]), float(ref[idx]), float(err[idx]), float(bound[idx])))
     return float((err / bound.clamp_min(1e-300)).max())
+
+
+# ---- per-element bounds for launches whose operand is formed on load, for the depthwise sweeps and for fp32 sums ------------------
+# u = 2^-24 is the unit roundoff of fp32 (round to nearest).  The host never re-enacts the device's fp32 evaluation of an operand: it
+# brackets it in fp64 by an interval [lo, hi] that every correctly rounded evaluation (fused or not) falls into, and carries the
+# interval's half width through the reference as `slack`.  Nothing here is fitted to a kernel's output.
+U32 = 2.0 ** -24
+HINGE = 1e-3            # inputs are moved off the ReLU hinge |s*v+t| < HINGE: host and device then agree on every mask bit
+MAX_ACT_SPLIT = 1e-3    # largest share of bf16 activation operand elements whose interval straddles a bf16 rounding boundary
+MAX_DY_SPLIT = 2e-2     # the same for a dy operand (it cancels: three terms of either sign)
+MAX_HINGE_MOVED = 1e-2  # largest share of elements off_hinge may move
+
+
+def _pre(v, s, t):
+    return s.double().to(v.device) * v.double() + t.double().to(v.device)
+
+
+def _on_hinge(v, s, t):
+    """|s*v+t| < HINGE, except where v == 0 and t == 0: there s*v+t is exactly zero in fp32 and in fp64 alike"""
+    exact0 = (v.double() == 0) & (t.double().to(v.device) == 0).expand_as(v)
+    return (_pre(v, s, t).abs() < HINGE) & ~exact0
+
+
+def off_hinge(v, s, t):
+    """v (..., C) fp32 holding bf16 values; s, t [C]: move the elements with |s*v+t| < HINGE to where s*v+t ~ +0.05 (bf16).
+    An element with v == 0 under t == 0 stays: its s*v+t is the exact zero on host and device.  At most MAX_HINGE_MOVED of the
+    elements may need moving (a test whose inputs sit on the hinge wholesale is testing something else)."""
+    sd, td = s.double().to(v.device), t.double().to(v.device)
+    bad = _on_hinge(v, s, t)
+    share = float(bad.double().mean())
+    assert share <= MAX_HINGE_MOVED, "off_hinge would move %.3g of the elements (limit %.3g)" % (share, MAX_HINGE_MOVED)
+    alt = bf16r(((0.05 - td) / sd).float()).expand_as(v)
+    out = torch.where(bad, alt, v)
+    assert not bool(_on_hinge(out, s, t).any())
+    off_hinge.worst = max(off_hinge.worst, share)
+    return out
+
+
+off_hinge.worst = 0.0
+
+
+def zero_on_hinge(g, y, s, t):
+    """Where y cannot be moved (it is another kernel's output, e.g. the forward's stored y that RECOMP recomputes): g = 0 at the
+    elements with y on the hinge, so that g*[s*y+t > 0] = 0 whichever way the mask bit falls.  Same share limit as off_hinge."""
+    bad = _on_hinge(y, s, t)
+    share = float(bad.double().mean())
+    assert share <= MAX_HINGE_MOVED, "zero_on_hinge would clear %.3g of the elements (limit %.3g)" % (share, MAX_HINGE_MOVED)
+    off_hinge.worst = max(off_hinge.worst, share)
+    return torch.where(bad, torch.zeros_like(g), g)
+
+
+def relu_mask(v, s, t):
+    """[s*v+t > 0] in fp64; v must be off the hinge (off_hinge), so the device's fp32 fma (within u*|s*v+t|) gives the same bits"""
+    assert not bool(_on_hinge(v, s, t).any()), "mask input on the ReLU hinge: move it with off_hinge first"
+    return _pre(v, s, t) > 0
+
+
+def _bf16_64(t):
+    """fp64 -> fp32 -> bf16 (both round to nearest even) -> fp64: monotone, so it maps an interval's ends to the ends of the
+    interval of rounded values"""
+    return t.float().to(torch.bfloat16).double()
+
+
+class Interval:
+    """an operand tensor known to lie in [lo, hi] element by element (fp64)"""
+    worst_act = 0.0      # largest measured shares of split bf16 elements (DESIGN.md section 6)
+    worst_dy = 0.0
+
+    def __init__(self, lo, hi, D=None, val=None):
+        """D: the magnitude the operand's rounding is relative to; val: the exact (fp64) value of the operand"""
+        assert bool((lo <= hi).all())
+        self.lo, self.hi, self.D, self.val = lo, hi, D, val
+
+    @staticmethod
+    def exact(x, device=None):
+        x = x.double() if device is None else _f64(x, device)
+        return Interval(x, x, x.abs(), x)
+
+    @property
+    def mid(self):
+        return (self.lo + self.hi) / 2
+
+    @property
+    def half(self):
+        return (self.hi - self.lo) / 2
+
+    @property
+    def amax(self):
+        return torch.maximum(self.lo.abs(), self.hi.abs())
+
+    def split_share(self):
+        return float((self.lo != self.hi).double().mean())
+
+
+def act_interval(z, s, t, bf16, device="cpu"):
+    """Interval of the act-on-load operand relu(s*z+t) over the last (channel) dimension; z holds bf16 values, s, t fp32.
+    Exact value pre = s*z+t (fp64).  The device evaluates one fmaf (act8, dw_act_raw: within u*|pre| <= u*(|s||z|+|t|)); an
+    unfused evaluation rounds the product and the sum (within 2u*(|s||z|+|t|) to first order), so eps = 2u*(|s||z|+|t|) covers
+    both.  relu is monotone: an fp32 operand (the depthwise sweeps) lies in [relu(pre-eps), relu(pre+eps)].  bf16=True: the MFMA
+    kernels round it to bf16 (pack_bf16, round to nearest even), which is monotone too: [bf16(relu(pre-eps)), bf16(relu(pre+eps))].
+    Asserted: at most MAX_ACT_SPLIT of the bf16 elements have lo != hi (the interval straddles a rounding boundary).
+    .D = |s||z|+|t|, the magnitude the depthwise bound's S is built from."""
+    z, s, t = _f64(z, device), _f64(s, device), _f64(t, device)
+    pre = s * z + t
+    D = s.abs() * z.abs() + t.abs()
+    eps = 2 * U32 * D
+    lo, hi = torch.relu(pre - eps), torch.relu(pre + eps)
+    if bf16:
+        lo, hi = _bf16_64(lo), _bf16_64(hi)
+    iv = Interval(lo, hi, D, torch.relu(pre))
+    if bf16:
+        share = iv.split_share()
+        assert share <= MAX_ACT_SPLIT, "act operand: %.3g of the bf16 elements straddle a rounding boundary (limit %.3g)" % (share, MAX_ACT_SPLIT)
+        Interval.worst_act = max(Interval.worst_act, share)
+    return iv
+
+
+def dy_interval(g, y, coef, bf16, device="cpu", g_masked=False):
+    """Interval of the dy-on-load operand dy = c1*g*[s*y+t > 0] + c2*y + c3 (coef rows 0..4) over the last dimension; g, y hold
+    bf16 values.  y must be off the ReLU hinge (asserted; an element with g == 0 is exempt: its dz is 0 under either mask bit), so
+    the mask bit is the device's.  With D = |c1||g| +
+    |c2||y| + |c3|: dy8 / dw_read_dy evaluate fma(c1, dz, fma(c2, y, c3)) -- two nested roundings, within 2u*D -- and an unfused
+    evaluation twice as many: eps = 4u*D.  fp32 operand (depthwise): [dy-eps, dy+eps]; bf16=True (pack8 of dy8 in the MFMA
+    kernels): both ends rounded to bf16.  Asserted: at most MAX_DY_SPLIT of the bf16 elements have lo != hi.
+    g_masked: g already holds g*mask (the g_masked form of mnas_dw_bwd), no mask is applied."""
+    g, y, cf = _f64(g, device), _f64(y, device), _f64(coef, device)
+    s, t, c1, c2, c3 = cf[0], cf[1], cf[2], cf[3], cf[4]
+    if not g_masked:
+        assert not bool((_on_hinge(y, s, t) & (g != 0)).any()), "dy-on-load: y on the ReLU hinge under a non-zero g (off_hinge / zero_on_hinge)"
+    dz = g if g_masked else g * (s * y + t > 0)
+    d = c1 * dz + c2 * y + c3
+    D = c1.abs() * g.abs() + c2.abs() * y.abs() + c3.abs()
+    eps = 4 * U32 * D
+    lo, hi = d - eps, d + eps
+    if bf16:
+        lo, hi = _bf16_64(lo), _bf16_64(hi)
+    iv = Interval(lo, hi, D, d)
+    if bf16:
+        share = iv.split_share()
+        assert share <= MAX_DY_SPLIT, "dy operand: %.3g of the bf16 elements straddle a rounding boundary (limit %.3g)" % (share, MAX_DY_SPLIT)
+        Interval.worst_dy = max(Interval.worst_dy, share)
+    return iv
+
+
+WORST = {}          # family -> largest measured error / bound (printed by the tests; DESIGN.md section 6 records them)
+
+
+def _assert_bound(hip, ref, bound, what, family):
+    hip, ref, bound = hip.double(), ref.double(), bound.double()
+    assert hip.shape == ref.shape == bound.shape, (what, hip.shape, ref.shape, bound.shape)
+    err = (hip - ref).abs()
+    bad = ~(err <= bound)                     # (a NaN fails)
+    if bool(bad.any()):
+        ratio = torch.where(bad, err / bound.clamp_min(1e-300), torch.zeros_like(err))
+        idx = tuple(int(v) for v in torch.unravel_index(ratio.reshape(-1).argmax(), ratio.shape)) if ratio.dim() else ()
+        raise AssertionError("%s: %d of %d elements outside the per-element bound; worst at %s: got %r, fp64 %r, |err| %.3e > bound %.3e (x%.2f)"
+                             % (what, int(bad.sum()), bad.numel(), idx, float(hip[idx]), float(ref[idx]), float(err[idx]),
+                                float(bound[idx]), float(err[idx] / bound[idx].clamp_min(1e-300))))
+    worst = float((err / bound.clamp_min(1e-300)).max()) if err.numel() else 0.0
+    if family:
+        WORST[family] = max(WORST.get(family, 0.0), worst)
+    return worst
+
+
+def onload_elem_err(slack, S, K):
+    """what the fp32 value in the accumulator (before the bf16 store) may differ from the fp64 reference by: (K+1)*2^-22*S + slack"""
+    return (K + 1) * 2.0 ** -22 * S.double() + slack.double()
+
+
+def check_onload_bound(hip, ref, slack, S, K, what, family="mfma on-load"):
+    """Per-element bound for an MFMA launch (bf16 output) whose operand is formed on load and known as an Interval `a` (bf16 ends).
+    ref = conv(a.mid, w) (+bias, +resid); slack = conv(a.half, |w|): how far the exact result over ANY operand inside the
+    interval can lie from ref; S = conv(a.amax, |w|) + |bias| + |resid|.  As check_gemm_bound: bf16 x bf16 products are exact,
+    K accumulations and the bias / residual add lose (K+1)*2^-23*S, doubled; the bf16 store rounds a value of at most
+    |ref|+slack (+ the fp32 error, which the doubled accumulation term absorbs) by at most 2^-8 of it.  EVERY element:
+        |hip - ref| <= 2^-8*(|ref| + slack) + (K+1)*2^-22*S + slack.
+    With lo == hi everywhere (slack = 0) this is check_gemm_bound."""
+    bound = 2.0 ** -8 * (ref.double().abs() + slack.double()) + onload_elem_err(slack, S, K)
+    return _assert_bound(hip, ref, bound, what, family)
+
+
+def dw_elem_err(S, k):
+    """fp32 error of a depthwise accumulator before its bf16 store: (2k^2+2)*2^-23*S"""
+    return (2 * k * k + 2) * 2.0 ** -23 * S.double()
+
+
+def check_dw_bound(hip, ref, S, k, what, family="depthwise"):
+    """Per-element bound for the depthwise sweeps (fp32 operands formed on read, fp32 weights as given -- NOT rounded to bf16 by
+    the test --, k*k taps accumulated in fp32, bf16 output).  ref: the fp64 result over the exact operands (relu(s*z+t) resp. dy in
+    fp64).  S: the same sum over magnitudes -- forward |bias| + sum (|s||z|+|t|)*|w| (act_interval(...).D), input gradient
+    sum D*|w| (dy_interval(...).D).  Each tap is one fma rounding (or a multiply and an add rounding), 2^-24 of a running
+    magnitude <= S each: at most 2k^2*2^-24*S; the operand's own rounding (u resp. 2u of its magnitude, act_interval /
+    dy_interval) is at most 2*2^-24*S more; doubled as in check_gemm_bound: (2k^2+2)*2^-23*S.  The bf16 store adds 2^-8*|value|.
+        |hip - ref| <= 2^-8*|ref| + (2k^2+2)*2^-23*S      for EVERY element."""
+    bound = 2.0 ** -8 * ref.double().abs() + dw_elem_err(S, k)
+    return _assert_bound(hip, ref, bound, what, family)
+
+
+def check_sum_bound(hip, ref, S, M, P, c, what, slack=None, family="fp32 sums"):
+    """Bound for an fp32 sum of M terms per output, written as P partial slabs / columns that a finalize (or the host) adds:
+    weight-gradient partials after mnas_wgrad_finalize, BatchNorm statistics (sum y, sum y^2), the fused reduce (sum dz,
+    sum dz*xhat).  ref: the fp64 sum; S: the same sum over absolute values.  Every add loses at most 2^-24 of a running
+    magnitude <= S (M in the kernel, P in the finalize, 1 for an accumulate target or bias); a term that is itself rounded (c = 2:
+    fp32 x fp32 products of the depthwise weight gradient, xhat = fma(y, inv, m), y^2) doubles the per-term loss, an exact term
+    (c = 1: bf16 x bf16) does not; the whole is doubled as in check_gemm_bound:
+        |hip - ref| <= (c*M + P + 1)*2^-22*S + slack.
+    slack: what the exact sum over any operands inside their intervals may differ from ref by -- for two interval operands a, b
+    sum(|a.mid|*b.half + |b.mid|*a.half + a.half*b.half) (prod_slack); for statistics of an fp32 accumulator, the sum of the
+    elements' own fp32 error (onload_elem_err / dw_elem_err)."""
+    bound = (c * M + P + 1) * 2.0 ** -22 * S.double()
+    if slack is not None:
+        bound = bound + slack.double()
+    return _assert_bound(hip, ref, bound, what, family)
+
+
+def stats_bound_terms(ref, e, dims=None):
+    """BatchNorm statistics of an fp32 accumulator v with |v - ref| <= e element by element (the kernels sum the accumulator, not
+    the stored bf16 value: mnas_stat2 / `s1 += v; s2 = fma(v, v, s2)` sit before pack_bf16 in every forward epilogue).  Returns
+    (ref1, S1, slack1, ref2, S2, slack2) per channel for check_sum_bound: sum v against sum ref with slack sum e; sum v^2 against
+    sum ref^2 with slack sum (2|ref|e + e^2); S over (|ref|+e) resp. its square."""
+    ref, e = ref.double(), e.double()
+    dims = tuple(range(ref.dim() - 1)) if dims is None else dims
+    a = ref.abs() + e
+    return (ref.sum(dims), a.sum(dims), e.sum(dims), (ref * ref).sum(dims), (a * a).sum(dims), (2 * ref.abs() * e + e * e).sum(dims))
+
+
+def check_stats_bound(st, ref, e, M, what, family="statistics"):
+    """st: the [2][C][P] table of a forward launch; ref (..., C): fp64 reference elements; e: their fp32 error bound.  c = 1 for
+    sum v, c = 2 for sum v^2 (the square is rounded)."""
+    P = st.shape[-1]
+    p = st.double().sum(-1)
+    r1, S1, k1, r2, S2, k2 = stats_bound_terms(ref, e)
+    a = check_sum_bound(p[0].to(r1.device), r1, S1, M, P, 1, what + " stats sum", k1, family)
+    b = check_sum_bound(p[1].to(r1.device), r2, S2, M, P, 2, what + " stats sum of squares", k2, family)
+    return max(a, b)
+
+
+def check_red_bound(table, gq, yin, bn, M, what, family="fused reduce"):
+    """Fused BatchNorm-backward reduce (sum dz, sum dz*xhat) per channel; table [2][C][P].  The kernels sum the gradient AS STORED
+    (mnas_red2 takes the packed bf16 pair; dw: f2bf(pk)): gq is the launch's own bf16 output, yin the raw output of the producer
+    (off the hinge), bn its bnbuf.  dz = gq*[s*y+t>0] is exact: c = 1 for sum dz.  xhat = fma(y, inv, m) with m = -mean*inv
+    rounded, within 2u*(|y|+|mean|)*|inv| of (y-mean)*inv: c = 2 for sum dz*xhat with S = sum |dz|*(|y|+|mean|)*|inv|."""
+    C_ = gq.shape[-1]
+    gq, yin = gq.reshape(-1, C_), yin.reshape(-1, C_)
+    bn = bn.double().to(gq.device)
+    acc = [torch.zeros(C_, dtype=torch.float64, device=gq.device) for _ in range(4)]
+    step = max(1, (8 << 20) // C_)                       # fp64 temporaries of at most 8 M elements
+    for m0 in range(0, gq.shape[0], step):
+        g, y = gq[m0:m0 + step].double(), yin[m0:m0 + step].double()
+        dz = g * relu_mask(y, bn[0], bn[1])
+        xhat = (y - bn[5]) * bn[6]
+        xabs = (y.abs() + bn[5].abs()) * bn[6].abs()
+        for a_, v in zip(acc, (dz, dz.abs(), dz * xhat, dz.abs() * xabs)):
+            a_ += v.sum(0)
+    P = table.shape[-1]
+    p = table.double().sum(-1).to(gq.device)
+    a = check_sum_bound(p[0], acc[0], acc[1], M, P, 1, what + " sum dz", None, family)
+    b = check_sum_bound(p[1], acc[2], acc[3], M, P, 2, what + " sum dz*xhat", None, family)
+    return max(a, b)
+
+
+def prod_slack(a, b):
+    """element-wise slack of a product of two interval operands: |a.mid|*b.half + |b.mid|*a.half + a.half*b.half"""
+    return a.mid.abs() * b.half + b.mid.abs() * a.half + a.half * b.half
+
+
+def pad_hw(x, p):
+    """zero-pad an NHWC tensor by p rows / columns on each side"""
+    if p == 0:
+        return x
+    N, H, W, C_ = x.shape
+    out = torch.zeros((N, H + 2 * p, W + 2 * p, C_), dtype=x.dtype, device=x.device)
+    out[:, p:p + H, p:p + W] = x
+    return out
+
+
+def onload_fwd_terms(a, w, bias=None, stride=1, pad=None, device="cpu"):
+    """(ref, slack, S) of check_onload_bound for a forward conv over the interval operand a (N,H,W,Ci), w (Co,Ci,k,k)"""
+    aw = _f64(w, device).abs()
+    ref = ref_dense_fwd(a.mid, w, bias, stride, pad, device)
+    slack = ref_dense_fwd(a.half, aw, None, stride, pad, device)
+    S = ref_dense_fwd(a.amax, aw, None if bias is None else bias.abs(), stride, pad, device)
+    return ref, slack, S
+
+
+def onload_dgrad_terms(d, w, H, W, stride=1, pad=None, resid=None, device="cpu"):
+    """(ref, slack, S) of check_onload_bound for an input gradient over the interval operand d (N,Ho,Wo,Co), w (Co,Ci,k,k)"""
+    aw = _f64(w, device).abs()
+    ref = ref_dense_dgrad(d.mid, w, H, W, stride, pad, device)
+    slack = ref_dense_dgrad(d.half, aw, H, W, stride, pad, device)
+    S = ref_dense_dgrad(d.amax, aw, H, W, stride, pad, device)
+    if resid is not None:
+        r = _f64(resid, device)
+        ref, S = ref + r, S + r.abs()
+    return ref, slack, S
+
+
+def wgrad_terms(a, d, k, stride=1, pad=None, device="cpu"):
+    """(ref, S, slack) of check_sum_bound for a dense weight gradient over interval operands a (N,H,W,Ci), d (N,Ho,Wo,Co)
+    -> (Co,Ci,k,k).  slack = sum prod_slack = S - sum |a.mid||d.mid|, because amax = |mid| + half for any interval (exactly zero
+    for two zero-width intervals: both sums are then the same computation)."""
+    ref = ref_dense_wgrad(a.mid, d.mid, k, stride, pad, device)
+    S = ref_dense_wgrad(a.amax, d.amax, k, stride, pad, device)
+    slack = (S - ref_dense_wgrad(a.mid.abs(), d.mid.abs(), k, stride, pad, device)).clamp_min(0)
+    return ref, S, slack
+
+
+def ref_dw_wgrad_s(x, dy, k, stride=1, device="cpu"):
+    """weight gradient of ref_dw_fwd_s: x (N,H,W,C), dy (N,Ho,Wo,C) -> (C,k,k)"""
+    x, dy = _f64(x, device), _f64(dy, device)
+    N, H, W, C_ = x.shape
+    _, Ho, Wo, _ = dy.shape
+    xp = pad_hw(x, k // 2)
+    dw = torch.zeros((C_, k, k), dtype=torch.float64, device=device)
+    for kh in range(k):
+        for kw in range(k):
+            dw[:, kh, kw] = (xp[:, kh:kh + (Ho - 1) * stride + 1:stride, kw:kw + (Wo - 1) * stride + 1:stride] * dy).sum((0, 1, 2))
+    return dw
+
+
+def ref_dw_dgrad_s(dy, w, H, W, stride=1, device="cpu"):
+    """input gradient of ref_dw_fwd_s: dy (N,Ho,Wo,C) -> (N,H,W,C)"""
+    dy, w = _f64(dy, device), _f64(w, device)
+    N, Ho, Wo, C_ = dy.shape
+    k = w.shape[-1]
+    p = k // 2
+    gp = torch.zeros((N, max(H + 2 * p, (Ho - 1) * stride + k), max(W + 2 * p, (Wo - 1) * stride + k), C_), dtype=torch.float64, device=device)
+    for kh in range(k):
+        for kw in range(k):
+            gp[:, kh:kh + (Ho - 1) * stride + 1:stride, kw:kw + (Wo - 1) * stride + 1:stride] += dy * w[:, kh, kw]
+    return gp[:, p:p + H, p:p + W].contiguous()
+
+
+def dw_fwd_terms(a, w, bias=None, stride=1, device="cpu"):
+    """(ref, S) of check_dw_bound for the depthwise forward over the fp32 interval operand a = act_interval(..., bf16=False) (or
+    Interval.exact of a plain input): ref over the exact operand a.val, S = |bias| + sum a.D*|w|"""
+    aw = _f64(w, device).abs()
+    ref = ref_dw_fwd_s(a.val, w, bias, stride, device)
+    S = ref_dw_fwd_s(a.D, aw, None if bias is None else bias.abs(), stride, device)
+    return ref, S
+
+
+def dw_dgrad_terms(d, w, H, W, stride=1, device="cpu"):
+    """(ref, S) of check_dw_bound for the depthwise input gradient over d = dy_interval(..., bf16=False): S = sum D*|w|"""
+    aw = _f64(w, device).abs()
+    return ref_dw_dgrad_s(d.val, w, H, W, stride, device), ref_dw_dgrad_s(d.D, aw, H, W, stride, device)
+
+
+def dw_wgrad_terms(a, d, k, stride=1, device="cpu"):
+    """(ref, S, slack) of check_sum_bound (c = 2) for the depthwise weight gradient over fp32 interval operands (slack as in
+    wgrad_terms)"""
+    ref = ref_dw_wgrad_s(a.mid, d.mid, k, stride, device)
+    S = ref_dw_wgrad_s(a.amax, d.amax, k, stride, device)
+    slack = (S - ref_dw_wgrad_s(a.mid.abs(), d.mid.abs(), k, stride, device)).clamp_min(0)
+    return ref, S, slack

@@ -7,7 +7,9 @@ backward on a masked gradient.  Part 2: the distinct launches of the bench confi
 replayed standalone with the production integers against fp64 references computed on the device.
 
 Every output and partial table lives in a guarded buffer (tests/gpu_util.py): a write outside it, or an element never written,
-fails the test.  Where include/mnas.h promises bit-identical results (RECOMP vs the stored y, masked vs plain gradients, grid
+fails the test.  On top of the max-normalised tolerances every launch is held to the derived bounds of tests/gpu_util.py: the
+input gradients element by element (check_onload_bound over the dy-on-load interval, check_dw_bound for the sweeps), the weight
+gradients and fused reduces per element / channel (check_sum_bound, check_red_bound).  Where include/mnas.h promises bit-identical results (RECOMP vs the stored y, masked vs plain gradients, grid
 size), the comparison is bit for bit and names the first differing element."""
 import ctypes as C
 
@@ -15,13 +17,17 @@ import pytest
 import torch
 
 from cases import O
-from gpu_util import (L, act_in, bf16r, bits_equal, conv_gemm, grad_in, guarded, pack, rand_bn_coefs, ref_dense_s2_dgrad,
-                      ref_dw_dgrad, ref_dw_wgrad, ref_dy, relerr)
+from gpu_util import (HINGE, Interval, L, act_in, act_interval, bf16r, bits_equal, check_dw_bound, check_onload_bound,
+                      check_red_bound, check_sum_bound, conv_gemm, dw_dgrad_terms, dw_wgrad_terms, dy_interval, grad_in, guarded,
+                      off_hinge, onload_dgrad_terms, pack, rand_bn_coefs, ref_dense_s2_dgrad, ref_dw_dgrad, ref_dw_wgrad,
+                      ref_dy, relerr, relu_mask, zero_on_hinge)
 from test_gpu_kernels import DW, PWB, TOL_BF16, TOL_F32
 
 pytestmark = pytest.mark.gpu
 TOL_RED = 1e-3          # fused BatchNorm-backward reduce sums (as test_pw_dgrad)
-HINGE = 1e-3            # inputs are moved off the ReLU hinge |s*v+t| < HINGE: host and device then agree on every mask bit
+_off_hinge = off_hinge  # (gpu_util: inputs are moved off the ReLU hinge |s*v+t| < HINGE, host and device then agree on every mask bit)
+assert HINGE == 1e-3
+BOUND_ELEMS = 16 << 20  # fp64 elements of one operand chunk of the per-element bounds
 
 
 def _x(shape, seed):
@@ -30,16 +36,6 @@ def _x(shape, seed):
 
 def _cdiv(a, b):
     return (a + b - 1) // b
-
-
-def _off_hinge(v, s, t):
-    """v (..., C) fp32 holding bf16 values; s, t [C]: move the elements with |s*v+t| < HINGE to where s*v+t ~ +0.05 (bf16)"""
-    vd, sd, td = v.double(), s.double().to(v.device), t.double().to(v.device)
-    bad = ((sd * vd + td).abs() < HINGE)
-    alt = bf16r(((0.05 - td) / sd).float()).expand_as(v)
-    out = torch.where(bad, alt, v)
-    assert bool(((sd * out.double() + td).abs() >= HINGE).all())
-    return out
 
 
 def _mask(v, s, t):
@@ -106,6 +102,7 @@ def _tconv_launch(lib, N, Ho, Wo, Co, Ci, dyd, wp, nparts, red=None):
 @pytest.mark.parametrize("case", TCONV, ids=["%s_%dx%dx%d_%d_%d" % c for c in TCONV])
 @pytest.mark.parametrize("fused_red", [False, True], ids=["plain", "red"])
 def test_tconv_dgrad(case, fused_red):
+    """+ check_onload_bound (materialised dy: the plain special case) and check_red_bound"""
     kernel, N, Ho, Wo, Co, Ci = case
     lib = L.load()
     H, W = 2 * Ho, 2 * Wo
@@ -121,16 +118,20 @@ def test_tconv_dgrad(case, fused_red):
     wp = pack(w, L.PACK_TCONV)
     red = None
     if fused_red:
-        y_in = _x((N, H, W, Ci), 21)
         b_in = rand_bn_coefs(Ci, 22, O)
+        y_in = _off_hinge(_x((N, H, W, Ci), 21), b_in[0], b_in[1])
         red = (y_in.to(torch.bfloat16).cuda(), b_in.cuda())
+    # per-element bound: dy is materialised (a zero-width interval), K = 9*Co bounds the accumulations of any output pixel
+    r64, slack, S = onload_dgrad_terms(Interval.exact(dy, "cuda"), w, H, W, 2, 1, None, "cuda")
     outs = []
     for nparts in sorted({1, pref, pref + 7}):
         out, st = _tconv_launch(lib, N, Ho, Wo, Co, Ci, dyd, wp, nparts, red)
         outs.append((nparts, out))
         assert relerr(out.double().cpu(), ref) < TOL_BF16, (kernel, nparts, relerr(out.double().cpu(), ref))
+        check_onload_bound(out, r64, slack, S, 9 * Co, "tconv %s nparts %d" % (kernel, nparts), "transposed-conv input gradient")
         if fused_red:
             _check_red(st.cpu(), out.float().cpu(), y_in, b_in, "tconv %s nparts %d" % (kernel, nparts))
+            check_red_bound(st, out.float(), red[0].float(), b_in, N * H * W, "tconv %s nparts %d" % (kernel, nparts), "fused reduce (GEMM)")
     for nparts, out in outs[1:]:
         bits_equal(out, outs[0][1], "tconv %s out, nparts %d vs %d" % (kernel, nparts, outs[0][0]))
     # the input-gradient GEMM the dispatcher replaced, on the same operands
@@ -342,7 +343,7 @@ def test_bwd_post_level0_slots_and_rejects():
 class _PwCase:
     """operands of one fused 1x1 backward: x (M,Ci) read through its producer's (scale, shift) when virtual, dy-on-load of (g, y)
     with this layer's coefficients, fp32 weights rounded to bf16 by the packer.  Device tensors; `gen` seeds them."""
-    def __init__(self, M, Ci, Co, gen, virt=True, y=None, bias=False, off_hinge_x=False, off_hinge_y=False):
+    def __init__(self, M, Ci, Co, gen, virt=True, y=None, bias=False):
         dev = "cuda"
         self.M, self.Ci, self.Co, self.virt = M, Ci, Co, virt
         u = lambda *s: torch.rand(*s, generator=gen, device=dev) * 2 - 1
@@ -350,9 +351,7 @@ class _PwCase:
         self.bx[0], self.bx[1] = 1 + 0.3 * u(Ci), 0.2 * u(Ci)
         self.bx[2], self.bx[3], self.bx[4] = self.bx[0], 0.05 * u(Ci), 0.02 * u(Ci)
         self.bx[5], self.bx[6] = 0.1 * u(Ci), 1 + 0.2 * u(Ci).abs()
-        x = bf16r(u(M, Ci))
-        if off_hinge_x:
-            x = _off_hinge(x, self.bx[0], self.bx[1])
+        x = _off_hinge(bf16r(u(M, Ci)), self.bx[0], self.bx[1])      # (always: x feeds the fused reduce's mask)
         self.x = x.to(torch.bfloat16)
         self.b = torch.zeros(8, Co, device=dev)
         self.b[0], self.b[1] = 1 + 0.3 * u(Co), 0.2 * u(Co)
@@ -363,11 +362,15 @@ class _PwCase:
         self.wd = pack(self.w.view(Co, Ci, 1, 1), L.PACK_DGRAD)
         self.bias = 0.1 * u(Co) if bias else None
         if y is None:
-            yv = bf16r(u(M, Co))
-            if off_hinge_y:
-                yv = _off_hinge(yv, self.b[0], self.b[1])
-            y = yv.to(torch.bfloat16)
+            y = _off_hinge(bf16r(u(M, Co)), self.b[0], self.b[1]).to(torch.bfloat16)
+            self.y = y
+        else:
+            self.set_y(y)
+
+    def set_y(self, y):
+        """a y that another kernel wrote (the forward's stored output, for RECOMP) cannot be moved off the hinge: g is cleared there"""
         self.y = y
+        self.g = zero_on_hinge(self.g, y, self.b[0], self.b[1])
 
     def act(self):
         a = self.x.double()
@@ -423,6 +426,31 @@ class _PwCase:
         if redp is not None:
             # the reduce's dz = gin*[s*x+t>0]: the same sums from a masked gin
             _check_red(redp, gin.float(), self.x.float(), self.bx, what)
+            check_red_bound(redp, gin.float(), self.x.float(), self.bx, self.M, what, "fused 1x1 backward: reduce")
+        self.check_bounds(gin, grad, wpart.shape[0], what, masked)
+
+    def check_bounds(self, gin, grad, nparts, what, masked):
+        """check_onload_bound on gin (dy-on-load interval, rounded to bf16 as pack8 of dy8 stages it; masked: reference, slack and S
+        times the mask -- the kernel stores an exact zero there) and check_sum_bound (c = 1) on dW over the act-on-load and
+        dy-on-load intervals, pixel chunk by pixel chunk"""
+        w64 = self.w.double()
+        aw = w64.abs()
+        acc = [torch.zeros(self.Co, self.Ci, dtype=torch.float64, device="cuda") for _ in range(3)]
+        step = max(1, BOUND_ELEMS // max(self.Ci, self.Co))
+        for m0 in range(0, self.M, step):
+            m1 = min(self.M, m0 + step)
+            d = dy_interval(self.g[m0:m1], self.y[m0:m1], self.b, True, "cuda")
+            ref, slack, S = d.mid @ w64, d.half @ aw, d.amax @ aw
+            if masked:
+                m = relu_mask(self.x[m0:m1], self.bx[0], self.bx[1])
+                ref, slack, S = ref * m, slack * m, S * m
+            check_onload_bound(gin[m0:m1], ref, slack, S, self.Co, "%s gin pixels %d..%d" % (what, m0, m1), "fused 1x1 backward: gin")
+            a = act_interval(self.x[m0:m1], self.bx[0], self.bx[1], True, "cuda") if self.virt else Interval.exact(self.x[m0:m1], "cuda")
+            acc[0] += d.mid.t() @ a.mid
+            acc[1] += d.amax.t() @ a.amax
+            acc[2] += d.mid.abs().t() @ a.mid.abs()
+        # slack = sum prod_slack = S - sum |d.mid||a.mid| (amax = |mid| + half)
+        check_sum_bound(grad, acc[0], acc[1], self.M, nparts, 1, what + " dW", (acc[1] - acc[2]).clamp_min(0), "fused 1x1 backward: dW")
 
 
 def _pw_shapes(bit):
@@ -453,7 +481,7 @@ def test_pw_bwd_recomp(shape, virt):
     y, _ = conv_gemm(0, N, H, W, Ci, H, W, Co, 1, 1, 0, wf, cs.bias,
                      act=act_in(cs.x, cs.bx[0], cs.bx[1]) if virt else act_in(cs.x),
                      nparts=max(1, lib.mnas_conv_gemm_parts(0, M, Ci, Co, 1)))
-    cs.y = y.view(M, Co)
+    cs.set_y(y.view(M, Co))
     for nparts in (5, 64):
         a = cs.launch(nparts, red=virt)
         b = cs.launch(nparts, red=virt, recomp=(wf, cs.bias))
@@ -483,7 +511,7 @@ def test_pw_bwd_gin_masked(shape):
     forms = lib.mnas_pw_bwd_forms(Ci, Co)
     M = N * H * W
     gen = torch.Generator(device="cuda").manual_seed(13)
-    cs = _PwCase(M, Ci, Co, gen, virt=True, off_hinge_x=True)
+    cs = _PwCase(M, Ci, Co, gen, virt=True)
     if not forms & 4:
         cs.launch(3, masked=1, expect=L.EINVAL)
         return
@@ -569,7 +597,7 @@ class _DwCase:
         self.b = torch.zeros(8, C_, device=dev)
         self.b[0], self.b[1] = 1 + 0.3 * u(C_), 0.2 * u(C_)
         self.b[2], self.b[3], self.b[4] = self.b[0], 0.05 * u(C_), 0.02 * u(C_)
-        self.x = bf16r(u(N, H, W, C_)).to(torch.bfloat16)
+        self.x = _off_hinge(bf16r(u(N, H, W, C_)), self.bx[0], self.bx[1]).to(torch.bfloat16)     # (the fused reduce's mask input)
         self.g = bf16r(u(N, H, W, C_)).to(torch.bfloat16)
         self.y = _off_hinge(bf16r(u(N, H, W, C_)), self.b[0], self.b[1]).to(torch.bfloat16)
         self.w = u(C_, k, k) * (1.0 / k)
@@ -595,6 +623,24 @@ class _DwCase:
         assert relerr(grad.double(), ref_w.view(self.C, -1)) < TOL_F32, (what, "dW")
         if redp is not None:
             _check_red(redp, gin.float(), self.x.float(), self.bx, what)
+            check_red_bound(redp, gin.float(), self.x.float(), self.bx, self.N * self.H * self.W, what, "fused reduce (depthwise)")
+        self.check_bounds(gin, grad.view(self.C, self.k, self.k), rows, what)
+
+    def check_bounds(self, gin, grad, rows, what):
+        """check_dw_bound on gin and check_sum_bound (c = 2) on dW over the fp32 intervals of dy and act(x), image chunk by image chunk
+        (the weights are fp32 as given; a masked g gives the same dy: dy_interval masks the raw g)"""
+        acc = [torch.zeros(self.C, self.k, self.k, dtype=torch.float64, device="cuda") for _ in range(3)]
+        step = max(1, BOUND_ELEMS // (self.H * self.W * self.C))
+        for n0 in range(0, self.N, step):
+            n1 = min(self.N, n0 + step)
+            d = dy_interval(self.g[n0:n1], self.y[n0:n1], self.b, False, "cuda")
+            ref, S = dw_dgrad_terms(d, self.w, self.H, self.W, 1, "cuda")
+            check_dw_bound(gin[n0:n1], ref, S, self.k, "%s gin images %d..%d" % (what, n0, n1), "depthwise input gradient")
+            del ref, S
+            a = act_interval(self.x[n0:n1], self.bx[0], self.bx[1], False, "cuda")
+            for t, v in zip(acc, dw_wgrad_terms(a, d, self.k, 1, "cuda")):
+                t += v
+        check_sum_bound(grad, acc[0], acc[1], self.N * self.H * self.W, rows, 2, what + " dW", acc[2], "depthwise weight gradient")
 
 
 @pytest.mark.parametrize("shape", DW, ids=["%dx%dx%dx%d_k%d" % s for s in DW])
@@ -649,7 +695,7 @@ def _rand(gen, *shape):
 def _replay_pw(ints, flags, gen, N):
     M, Ci, Co, nparts, masked, seg = ints
     lib = L.load()
-    cs = _PwCase(M, Ci, Co, gen, virt=flags["virt"], bias=flags["b_fwd"], off_hinge_x=bool(masked))
+    cs = _PwCase(M, Ci, Co, gen, virt=flags["virt"], bias=flags["b_fwd"])
     recomp = None
     if flags["w_fwd"]:
         assert not flags["dy.y"]
@@ -661,7 +707,7 @@ def _replay_pw(ints, flags, gen, N):
         assert N * H * H == M
         y, _ = conv_gemm(0, N, H, H, Ci, H, H, Co, 1, 1, 0, wf, cs.bias,
                          act=act_in(cs.x, cs.bx[0], cs.bx[1]) if cs.virt else act_in(cs.x), nparts=nfp)
-        cs.y = y.view(M, Co)
+        cs.set_y(y.view(M, Co))
         recomp = (wf, cs.bias)
     r = cs.launch(nparts, red=flags["red"], recomp=recomp, masked=masked, seg_px=seg)
     cs.check_ref(*r, masked=bool(masked))

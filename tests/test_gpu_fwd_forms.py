@@ -9,15 +9,19 @@ configuration's two training Programs (float and uint8 input), replayed standalo
 
 Every output, statistics table and partial slab lives in a guarded buffer (tests/gpu_util.py).  References are fp64, built from
 slicing and matmul (gpu_util.ref_*), on the device.  Launches whose operand needs no transform on load are held to the
-per-element bound of gpu_util.check_gemm_bound; the others to the project's max-normalised tolerances."""
+per-element bound of gpu_util.check_gemm_bound; those with act-on-load / dy-on-load to gpu_util.check_onload_bound over the
+operand's interval (the same bound plus the interval's slack), their statistics to check_stats_bound, their fused reduce to
+check_red_bound; the depthwise forward with fp32 weights to check_dw_bound.  The max-normalised tolerances are asserted as well."""
 import ctypes as C
 from fractions import Fraction
 
 import pytest
 import torch
 
-from gpu_util import (L, act_in, bf16r, bits_equal, check_gemm_bound, conv_gemm, grad_in, guarded, pack, ref_dense_dgrad,
-                      ref_dense_fwd, ref_dense_wgrad, ref_dw_fwd_s, ref_dy, ref_stem, ref_stem_wgrad, relerr, route_of)
+from gpu_util import (Interval, L, act_in, act_interval, bf16r, bits_equal, check_dw_bound, check_gemm_bound, check_onload_bound,
+                      check_red_bound, check_sum_bound, conv_gemm, dw_elem_err, dw_fwd_terms, dy_interval, grad_in, guarded,
+                      onload_dgrad_terms, onload_elem_err, onload_fwd_terms, pack, ref_dense_dgrad, ref_dense_fwd, ref_dense_wgrad,
+                      ref_dw_fwd_s, ref_dy, ref_stem, ref_stem_wgrad, relerr, route_of, stats_bound_terms)
 from test_gpu_bwd_forms import _cdiv, _check_red, _off_hinge, _rand
 from test_gpu_kernels import DENSE, DW, PW, TOL_BF16, TOL_F32
 
@@ -59,8 +63,8 @@ class _GemmCase:
             self.bias = 0.1 * _rand(gen, Co) if bias else None
         else:
             self.g = bf16r(_rand(gen, N, self.Ho, self.Wo, Co)).to(torch.bfloat16)
-            self.y = bf16r(_rand(gen, N, self.Ho, self.Wo, Co)).to(torch.bfloat16) if coef else None
             self.b = _bn(gen, Co) if coef else None
+            self.y = _off_hinge(bf16r(_rand(gen, N, self.Ho, self.Wo, Co)), self.b[0], self.b[1]).to(torch.bfloat16) if coef else None
             if resid:
                 self.resid = bf16r(_rand(gen, N, H, W, Ci)).to(torch.bfloat16)
             if red:
@@ -99,7 +103,10 @@ class _GemmCase:
             " resid" if self.resid is not None else "", " red" if self.y_in is not None else "")
 
     def check(self, out, st, images=None):
-        """fp64 on the device, image chunk by image chunk; `images`: a subset (the statistics then are not compared)"""
+        """fp64 on the device, image chunk by image chunk; `images`: a subset (the statistics then are not compared).
+        Plain operand: check_gemm_bound.  Operand formed on load: check_onload_bound over act_interval / dy_interval (bf16 ends), the
+        reference being the interval's midpoint; forward statistics: check_stats_bound terms summed over the chunks (the epilogues sum
+        the fp32 accumulator, whose own error is onload_elem_err); fused reduce: check_red_bound on the output as stored."""
         what = self.what()
         K = self.k * self.k * (self.Ci if self.mode == 0 else self.Co)
         per = max(self.H * self.W * self.Ci, self.Ho * self.Wo * self.Co) * (self.k * self.k if self.k > 1 else 1)
@@ -108,29 +115,29 @@ class _GemmCase:
         s2 = torch.zeros_like(s1)
         worst, scale = 0.0, 0.0
         errs = []
+        sterms = None
         for n0, n1 in chunks:
             if self.mode == 0:
-                xs = self.x[n0:n1].float()
-                a = bf16r(torch.relu(self.sc * xs + self.sh)) if self.virt else xs
-                ref = ref_dense_fwd(a, self.w, self.bias, self.stride, self.pad, device="cuda")
-                if self.plain:
-                    S = ref_dense_fwd(a.abs(), self.w.abs(), None if self.bias is None else self.bias.abs(), self.stride, self.pad,
-                                      device="cuda")
+                iv = act_interval(self.x[n0:n1], self.sc, self.sh, True, "cuda") if self.virt else Interval.exact(self.x[n0:n1], "cuda")
+                ref, slack, S = onload_fwd_terms(iv, self.w, self.bias, self.stride, self.pad, "cuda")
+                del iv
                 s1 += ref.sum((0, 1, 2))
                 s2 += (ref * ref).sum((0, 1, 2))
+                t = stats_bound_terms(ref, onload_elem_err(slack, S, K))
+                sterms = t if sterms is None else tuple(a_ + b_ for a_, b_ in zip(sterms, t))
             else:
                 gs = self.g[n0:n1]
-                dy = bf16r(ref_dy(gs, self.y[n0:n1], self.b, device="cuda").float()) if self.coef else gs.float()
-                ref = ref_dense_dgrad(dy, self.w, self.H, self.W, self.stride, self.pad, device="cuda")
-                if self.resid is not None:
-                    ref = ref + self.resid[n0:n1].double()
-                if self.plain:
-                    S = ref_dense_dgrad(dy.abs(), self.w.abs(), self.H, self.W, self.stride, self.pad, device="cuda")
-                    if self.resid is not None:
-                        S = S + self.resid[n0:n1].double().abs()
+                iv = dy_interval(gs, self.y[n0:n1], self.b, True, "cuda") if self.coef else Interval.exact(gs, "cuda")
+                ref, slack, S = onload_dgrad_terms(iv, self.w, self.H, self.W, self.stride, self.pad,
+                                                   None if self.resid is None else self.resid[n0:n1], "cuda")
+                del iv
             if self.plain:
+                assert float(slack.max()) == 0.0
                 worst = max(worst, check_gemm_bound(out[n0:n1], ref, S, K, "%s images %d..%d" % (what, n0, n1)))
-                del S
+            else:
+                worst = max(worst, check_onload_bound(out[n0:n1], ref, slack, S, K, "%s images %d..%d" % (what, n0, n1),
+                                                      "%s %s" % ("1x1" if self.k == 1 else "3x3", "forward" if self.mode == 0 else "input gradient")))
+            del S, slack
             errs.append(float((out[n0:n1].double() - ref).abs().max()))
             scale = max(scale, float(ref.abs().max()))
             del ref
@@ -140,8 +147,12 @@ class _GemmCase:
             p = st.double().sum(-1)
             assert relerr(p[0], s1) < TOL_F32, (what, "stats sum", relerr(p[0], s1))
             assert relerr(p[1], s2) < TOL_F32, (what, "stats sum of squares", relerr(p[1], s2))
+            Mo, P = self.N * self.Ho * self.Wo, st.shape[-1]
+            check_sum_bound(p[0], sterms[0], sterms[1], Mo, P, 1, what + " stats sum", sterms[2], "forward statistics")
+            check_sum_bound(p[1], sterms[3], sterms[4], Mo, P, 2, what + " stats sum of squares", sterms[5], "forward statistics")
         if images is None and self.mode == 1 and st is not None:
             _check_red(st, out.float(), self.y_in.float(), self.b_in, what)
+            check_red_bound(st, out.float(), self.y_in.float(), self.b_in, self.N * self.H * self.W, what, "fused reduce (GEMM)")
         return rel, worst
 
 
@@ -547,17 +558,28 @@ def _dw_fwd(x, N, H, W, C_, k, stride, wp, bias, nparts, sc=None, sh=None):
     return out, st, what
 
 
-def _dw_check(out, st, a, w, bias, k, stride, what, plain):
-    """a: the activated input (N,H,W,C) fp32 (bf16 values when plain); w (C,k,k)"""
+def _dw_check(out, st, a, w, bias, k, stride, what, plain, act=None):
+    """a: the activated input (N,H,W,C) fp32 (bf16 values when plain); w (C,k,k).  plain (bf16-rounded weights, products exact):
+    check_gemm_bound.  Otherwise (fp32 weights as given): check_dw_bound over act_interval of act = (x, scale, shift), or over a
+    itself when the input is not virtual, and check_sum_bound on the statistics (the sweep sums its fp32 accumulator)."""
     N = a.shape[0]
     s1 = torch.zeros(a.shape[-1], dtype=torch.float64, device="cuda")
     s2 = torch.zeros_like(s1)
     err, scale = 0.0, 0.0
+    sterms = None
     for n0, n1 in _img_chunks(N, a[0].numel()):
-        ref = ref_dw_fwd_s(a[n0:n1], w, bias, stride, device="cuda")
         if plain:
+            ref = ref_dw_fwd_s(a[n0:n1], w, bias, stride, device="cuda")
             S = ref_dw_fwd_s(a[n0:n1].abs(), w.abs(), bias.abs(), stride, device="cuda")
             check_gemm_bound(out[n0:n1], ref, S, k * k, "%s images %d..%d" % (what, n0, n1))
+        else:
+            iv = act_interval(act[0][n0:n1], act[1], act[2], False, "cuda") if act is not None else Interval.exact(a[n0:n1], "cuda")
+            ref, S = dw_fwd_terms(iv, w, bias, stride, "cuda")
+            del iv
+            check_dw_bound(out[n0:n1], ref, S, k, "%s images %d..%d" % (what, n0, n1), "depthwise forward")
+            t = stats_bound_terms(ref, dw_elem_err(S, k))
+            sterms = t if sterms is None else tuple(a_ + b_ for a_, b_ in zip(sterms, t))
+        del S
         err = max(err, float((out[n0:n1].double() - ref).abs().max()))
         scale = max(scale, float(ref.abs().max()))
         s1 += ref.sum((0, 1, 2))
@@ -565,6 +587,10 @@ def _dw_check(out, st, a, w, bias, k, stride, what, plain):
     assert err / scale < TOL_BF16, (what, err / scale)
     p = st.double().sum(-1)
     assert relerr(p[0], s1) < TOL_F32 and relerr(p[1], s2) < TOL_F32, (what, relerr(p[0], s1), relerr(p[1], s2))
+    if sterms is not None:
+        Mo, P = out.shape[0] * out.shape[1] * out.shape[2], st.shape[-1]
+        check_sum_bound(p[0], sterms[0], sterms[1], Mo, P, 1, what + " stats sum", sterms[2], "depthwise statistics")
+        check_sum_bound(p[1], sterms[3], sterms[4], Mo, P, 2, what + " stats sum of squares", sterms[5], "depthwise statistics")
 
 
 DW_PLAIN = DW + [(2, 12, 12, 48, 5), (2, 13, 14, 72, 3)]
@@ -821,7 +847,7 @@ def _replay_dw(ints, flags, gen):
     a = torch.relu(sc * x + sh) if virt else x               # act-on-read: fp32, not re-rounded
     out, st, what = _dw_fwd(xb, N, H, W, C_, k, stride, wp, bias, nlaunch, sc if virt else None, sh if virt else None)
     zb = torch.zeros(C_, device="cuda") if bias is None else bias
-    _dw_check(out, st, a, w, zb, k, stride, what, plain=False)
+    _dw_check(out, st, a, w, zb, k, stride, what, plain=False, act=(x, sc, sh) if virt else None)
     alt = nlaunch // 2 + 3
     out2, st2, _ = _dw_fwd(xb, N, H, W, C_, k, stride, wp, bias, alt, sc if virt else None, sh if virt else None)
     bits_equal(out2, out, what + ": out vs nparts %d" % alt)

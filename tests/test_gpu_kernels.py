@@ -1,7 +1,14 @@
 """-m gpu: every HIP kernel, called through the C ABI, against fp32 torch-CPU math on the same bf16-rounded
 inputs.  Tolerance: outputs are stored as bf16 (half-ulp 2^-9) after fp32 accumulation, so the bound is
 max|hip - ref| <= 6e-3 * max|ref| for bf16 tensors and 2e-3 for fp32 reductions (statistics, weight
-gradients; limited by bf16 rounding of the staged operands, which the reference reproduces)."""
+gradients; limited by bf16 rounding of the staged operands, which the reference reproduces).
+
+On top of that, the conv / depthwise launches are held element by element (resp. channel by channel) to the derived bounds of
+tests/gpu_util.py against fp64 references on the device: check_onload_bound (MFMA launches, operand formed on load and known
+as an interval), check_dw_bound (depthwise sweeps, fp32 weights as given), check_sum_bound (weight gradients),
+check_stats_bound / check_red_bound (BatchNorm statistics, fused reduce).  Inputs that feed a ReLU mask are moved off the hinge
+(gpu_util.off_hinge).  The sparse-pixel probes at the end put a handful of live pixels at the first / last position and on
+both sides of the tile and workgroup boundaries, where the same bounds see one dropped, doubled or misplaced pixel."""
 import ctypes as C
 
 import pytest
@@ -9,7 +16,10 @@ import torch
 import torch.nn.functional as F
 
 from cases import O
-from gpu_util import (L, act_in, bf16r, conv_gemm, dy_ref, from_nhwc, grad_in, guarded, nhwc, pack, rand_bn_coefs, relerr)
+from gpu_util import (Interval, L, act_in, act_interval, bf16r, check_dw_bound, check_onload_bound, check_red_bound,
+                      check_stats_bound, check_sum_bound, conv_gemm, dw_dgrad_terms, dw_elem_err, dw_fwd_terms, dw_wgrad_terms,
+                      dy_interval, dy_ref, from_nhwc, grad_in, guarded, nhwc, off_hinge, onload_dgrad_terms, onload_elem_err,
+                      onload_fwd_terms, pack, rand_bn_coefs, ref_dense_wgrad, relerr, wgrad_terms)
 
 pytestmark = pytest.mark.gpu
 TOL_BF16 = 6e-3
@@ -18,6 +28,19 @@ TOL_F32 = 2e-3
 
 def _x(shape, seed):
     return bf16r(O.det_uniform(shape, seed))
+
+
+DEV = "cuda"            # where the fp64 terms of the per-element bounds are computed
+
+
+def _nh(t):
+    """NCHW (cpu) -> NHWC view"""
+    return t.permute(0, 2, 3, 1)
+
+
+def _xoff(shape, seed, s, t):
+    """_x moved off the ReLU hinge of (s, t) (per channel, NCHW)"""
+    return off_hinge(_nh(_x(shape, seed)), s, t).permute(0, 3, 1, 2).contiguous()
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -75,6 +98,8 @@ PW = [  # N,H,W,Ci,Co
 @pytest.mark.parametrize("shape", PW)
 @pytest.mark.parametrize("virt", [True, False])
 def test_pw_fwd(shape, virt):
+    """+ check_onload_bound (act-on-load interval; plain x: the zero-width interval) and check_stats_bound (the epilogues sum the
+    fp32 accumulator)"""
     N, H, W, Ci, Co = shape
     x = _x((N, Ci, H, W), 1)
     w = bf16r(O.det_param("t.conv.weight", (Co, Ci, 1, 1), 2))
@@ -87,6 +112,10 @@ def test_pw_fwd(shape, virt):
     out, st = conv_gemm(0, N, H, W, Ci, H, W, Co, 1, 1, 0, pack(w, L.PACK_FWD), bias.cuda(),
                         act=act_in(xd, dsc if virt else None, dsh if virt else None), nparts=13, stats=True)
     assert relerr(from_nhwc(out), ref) < TOL_BF16
+    iv = act_interval(_nh(x), sc, sh, True, DEV) if virt else Interval.exact(_nh(x), DEV)
+    r64, slack, S = onload_fwd_terms(iv, w, bias, device=DEV)
+    check_onload_bound(out, r64, slack, S, Ci, "pw_fwd %s virt %d" % (shape, virt), "1x1 forward")
+    check_stats_bound(st, r64, onload_elem_err(slack, S, Ci), N * H * W, "pw_fwd %s virt %d" % (shape, virt), "forward statistics")
     st = st.cpu().double().sum(-1)
     assert relerr(st[0], ref.double().sum((0, 2, 3))) < TOL_F32
     assert relerr(st[1], (ref.double() ** 2).sum((0, 2, 3))) < TOL_F32
@@ -106,6 +135,7 @@ DENSE = [  # N,H,W,Ci,Co,stride
 
 @pytest.mark.parametrize("shape", DENSE)
 def test_dense_fwd(shape):
+    """+ check_onload_bound and check_stats_bound, as test_pw_fwd"""
     N, H, W, Ci, Co, s = shape
     Ho, Wo = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
     x = _x((N, Ci, H, W), 1)
@@ -119,6 +149,10 @@ def test_dense_fwd(shape):
     out, st = conv_gemm(0, N, H, W, Ci, Ho, Wo, Co, 3, s, 1, pack(w, L.PACK_FWD), bias.cuda(),
                         act=act_in(xd, dsc, dsh), nparts=5, stats=True)
     assert relerr(from_nhwc(out), ref) < TOL_BF16
+    r64, slack, S = onload_fwd_terms(act_interval(_nh(x), sc, sh, True, DEV), w, bias, s, 1, device=DEV)
+    check_onload_bound(out, r64, slack, S, 9 * Ci, "dense_fwd %s" % (shape,), "3x3 forward")
+    check_stats_bound(st, r64, onload_elem_err(slack, S, 9 * Ci), N * Ho * Wo, "dense_fwd %s" % (shape,), "forward statistics")
+    del r64, slack, S
     st = st.cpu().double().sum(-1)
     assert relerr(st[0], ref.double().sum((0, 2, 3))) < TOL_F32
     assert relerr(st[1], (ref.double() ** 2).sum((0, 2, 3))) < TOL_F32
@@ -127,9 +161,10 @@ def test_dense_fwd(shape):
 @pytest.mark.parametrize("shape", PW)
 @pytest.mark.parametrize("with_resid", [True, False])
 def test_pw_dgrad(shape, with_resid):
+    """+ check_onload_bound (dy-on-load interval, y off the hinge) and check_red_bound (the reduce sums the gradient as stored)"""
     N, H, W, Ci, Co = shape
-    g, y = _x((N, Co, H, W), 1), _x((N, Co, H, W), 2)
     b = rand_bn_coefs(Co, 9, O)
+    g, y = _x((N, Co, H, W), 1), _xoff((N, Co, H, W), 2, b[0], b[1])
     dy = dy_ref(g, y, b)
     w = bf16r(O.det_param("t.conv.weight", (Co, Ci, 1, 1), 2))
     ref = F.conv_transpose2d(dy, w)
@@ -138,12 +173,17 @@ def test_pw_dgrad(shape, with_resid):
         ref = ref + resid
     gd, yd, bd, rd = nhwc(g), nhwc(y), b.cuda(), nhwc(resid)
     # fused BN-backward reduce for the producer of the conv's input: (sum dz, sum dz*xhat) of (out, y_in, bn_in)
-    y_in = _x((N, Ci, H, W), 21)
     b_in = rand_bn_coefs(Ci, 22, O)
+    y_in = _xoff((N, Ci, H, W), 21, b_in[0], b_in[1])
     yid, bid = nhwc(y_in), b_in.cuda()
     out, st = conv_gemm(1, N, H, W, Co, H, W, Ci, 1, 1, 0, pack(w, L.PACK_DGRAD), None, grad=grad_in(gd, yd, bd),
                         resid=rd if with_resid else None, nparts=11, stats=True, red_y=yid, red_bn=bid)
     assert relerr(from_nhwc(out), ref) < TOL_BF16
+    what = "pw_dgrad %s resid %d" % (shape, with_resid)
+    r64, slack, S = onload_dgrad_terms(dy_interval(_nh(g), _nh(y), b, True, DEV), w, H, W, 1, 0,
+                                       _nh(resid) if with_resid else None, DEV)
+    check_onload_bound(out, r64, slack, S, Co, what, "1x1 input gradient")
+    check_red_bound(st, out.float(), yid.float(), b_in, N * H * W, what, "fused reduce (GEMM)")
     gq = from_nhwc(out)                                  # the reduce sees g as stored (bf16)
     s_, t_, mu_, is_ = (b_in[i].view(1, -1, 1, 1) for i in (0, 1, 5, 6))
     dz = (gq * ((s_ * y_in + t_) > 0)).double()
@@ -170,16 +210,19 @@ def test_pw_dgrad_plain_dy(shape, nparts):
 
 @pytest.mark.parametrize("shape", DENSE)
 def test_dense_dgrad(shape):
+    """+ check_onload_bound (dy-on-load interval, y off the hinge)"""
     N, H, W, Ci, Co, s = shape
     Ho, Wo = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
-    g, y = _x((N, Co, Ho, Wo), 1), _x((N, Co, Ho, Wo), 2)
     b = rand_bn_coefs(Co, 9, O)
+    g, y = _x((N, Co, Ho, Wo), 1), _xoff((N, Co, Ho, Wo), 2, b[0], b[1])
     dy = dy_ref(g, y, b)
     w = bf16r(O.det_param("t.conv.weight", (Co, Ci, 3, 3), 2))
     ref = torch.nn.grad.conv2d_input((N, Ci, H, W), w, dy, stride=s, padding=1)
     gd, yd, bd = nhwc(g), nhwc(y), b.cuda()
     out, _ = conv_gemm(1, N, Ho, Wo, Co, H, W, Ci, 3, s, 1, pack(w, L.PACK_DGRAD), None, grad=grad_in(gd, yd, bd), nparts=7)
     assert relerr(from_nhwc(out), ref) < TOL_BF16
+    r64, slack, S = onload_dgrad_terms(dy_interval(_nh(g), _nh(y), b, True, DEV), w, H, W, s, 1, None, DEV)
+    check_onload_bound(out, r64, slack, S, 9 * Co, "dense_dgrad %s" % (shape,), "3x3 input gradient")
 
 
 @pytest.mark.parametrize("shape", [(32, 14, 14, 80, 96), (32, 7, 7, 192, 320), (36, 9, 11, 24, 40), (32, 16, 16, 16, 24), (2, 14, 14, 80, 96),
@@ -228,54 +271,64 @@ def _wgrad(N, H, W, Ci, Ho, Wo, Co, k, s, pad, xact, dy, nsplit, accumulate=Fals
 
 @pytest.mark.parametrize("shape", PW)
 def test_pw_wgrad(shape):
+    """+ check_sum_bound (c = 1) over the act-on-load and dy-on-load intervals, overwrite and accumulate"""
     N, H, W, Ci, Co = shape
     x = _x((N, Ci, H, W), 1)
     sc, sh = 1 + 0.3 * O.det_uniform((Ci,), 4), 0.2 * O.det_uniform((Ci,), 5)
     a = bf16r(F.relu(x * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1)))
-    g, y = _x((N, Co, H, W), 6), _x((N, Co, H, W), 7)
     b = rand_bn_coefs(Co, 9, O)
+    g, y = _x((N, Co, H, W), 6), _xoff((N, Co, H, W), 7, b[0], b[1])
     dy = dy_ref(g, y, b)
     ref = torch.nn.grad.conv2d_weight(a, (Co, Ci, 1, 1), dy)
     xd, gd, yd, bd, dsc, dsh = nhwc(x), nhwc(g), nhwc(y), b.cuda(), sc.cuda(), sh.cuda()
     got = _wgrad(N, H, W, Ci, H, W, Co, 1, 1, 0, act_in(xd, dsc, dsh), grad_in(gd, yd, bd), 3)
     assert relerr(got, ref) < TOL_F32
+    r64, S, slack = wgrad_terms(act_interval(_nh(x), sc, sh, True, DEV), dy_interval(_nh(g), _nh(y), b, True, DEV), 1, 1, 0, DEV)
+    check_sum_bound(got.to(DEV), r64, S, N * H * W, 3, 1, "pw_wgrad %s" % (shape,), slack, "weight gradient")
     init = O.det_uniform((Co, Ci, 1, 1), 12)
     got2 = _wgrad(N, H, W, Ci, H, W, Co, 1, 1, 0, act_in(xd, dsc, dsh), grad_in(gd, yd, bd), 2, True, init)
     assert relerr(got2, ref + init) < TOL_F32
+    i64 = init.double().to(DEV)
+    check_sum_bound(got2.to(DEV), r64 + i64, S + i64.abs(), N * H * W, 2, 1, "pw_wgrad %s accumulate" % (shape,), slack, "weight gradient")
 
 
 @pytest.mark.parametrize("shape", DENSE)
 def test_dense_wgrad(shape):
+    """+ check_sum_bound (c = 1): plain x, dy-on-load interval"""
     N, H, W, Ci, Co, s = shape
     Ho, Wo = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
     x = _x((N, Ci, H, W), 1)
-    g, y = _x((N, Co, Ho, Wo), 6), _x((N, Co, Ho, Wo), 7)
     b = rand_bn_coefs(Co, 9, O)
+    g, y = _x((N, Co, Ho, Wo), 6), _xoff((N, Co, Ho, Wo), 7, b[0], b[1])
     dy = dy_ref(g, y, b)
     ref = torch.nn.grad.conv2d_weight(x, (Co, Ci, 3, 3), dy, stride=s, padding=1)
     xd, gd, yd, bd = nhwc(x), nhwc(g), nhwc(y), b.cuda()
     got = _wgrad(N, H, W, Ci, Ho, Wo, Co, 3, s, 1, act_in(xd), grad_in(gd, yd, bd), 2)
     assert relerr(got, ref) < TOL_F32
+    r64, S, slack = wgrad_terms(Interval.exact(_nh(x), DEV), dy_interval(_nh(g), _nh(y), b, True, DEV), 3, s, 1, DEV)
+    check_sum_bound(got.to(DEV), r64, S, N * Ho * Wo, 2, 1, "dense_wgrad %s" % (shape,), slack, "weight gradient")
 
 
 @pytest.mark.parametrize("shape,nsplit", [((1, 5, 5, 24, 40, 1), 7), ((2, 7, 7, 192, 320, 1), 3), ((1, 6, 6, 16, 24, 2), 5),
                                           ((3, 7, 7, 8, 168, 1), 2)])
 def test_dense_wgrad_slabs_and_empty_splits(shape, nsplit):
     """k_wgrad_t: more pixel splits than 64-pixel chunks (empty splits must contribute zeros), slab shapes with padded edge
-    tiles in both dimensions, and mnas_conv_wgrad_slabs consistent with a full cover of dW."""
+    tiles in both dimensions, and mnas_conv_wgrad_slabs consistent with a full cover of dW.  + check_sum_bound as test_dense_wgrad."""
     N, H, W, Ci, Co, s = shape
     lib = L.load()
     slabs = lib.mnas_conv_wgrad_slabs(Co, Ci, 9)
     assert 1 <= slabs <= ((Co + 31) // 32) * ((9 * Ci + 31) // 32)
     Ho, Wo = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
     x = _x((N, Ci, H, W), 31)
-    g, y = _x((N, Co, Ho, Wo), 36), _x((N, Co, Ho, Wo), 37)
     b = rand_bn_coefs(Co, 39, O)
+    g, y = _x((N, Co, Ho, Wo), 36), _xoff((N, Co, Ho, Wo), 37, b[0], b[1])
     dy = dy_ref(g, y, b)
     ref = torch.nn.grad.conv2d_weight(x, (Co, Ci, 3, 3), dy, stride=s, padding=1)
     xd, gd, yd, bd = nhwc(x), nhwc(g), nhwc(y), b.cuda()
     got = _wgrad(N, H, W, Ci, Ho, Wo, Co, 3, s, 1, act_in(xd), grad_in(gd, yd, bd), nsplit)
     assert relerr(got, ref) < TOL_F32
+    r64, S, slack = wgrad_terms(Interval.exact(_nh(x), DEV), dy_interval(_nh(g), _nh(y), b, True, DEV), 3, s, 1, DEV)
+    check_sum_bound(got.to(DEV), r64, S, N * Ho * Wo, nsplit, 1, "dense_wgrad %s nsplit %d" % (shape, nsplit), slack, "weight gradient")
     again = _wgrad(N, H, W, Ci, Ho, Wo, Co, 3, s, 1, act_in(xd), grad_in(gd, yd, bd), nsplit)
     assert torch.equal(got, again)                 # fixed summation order: bit-reproducible
 
@@ -290,6 +343,7 @@ DW = [  # N,H,W,C,k
 
 @pytest.mark.parametrize("shape", DW)
 def test_dw_fwd(shape):
+    """+ check_dw_bound (fp32 weights as given) and check_stats_bound (the sweep sums the fp32 accumulator)"""
     lib = L.load()
     N, H, W, C_, k = shape
     x = _x((N, C_, H, W), 1)
@@ -311,6 +365,9 @@ def test_dw_fwd(shape):
     a_.w, a_.bias, a_.out, a_.stats = wp.data_ptr(), db.data_ptr(), out.data_ptr(), st.data_ptr()
     L.check(lib.mnas_dw_fwd(C.byref(a_), L.cur_stream()), "dw_fwd")
     assert relerr(from_nhwc(out), ref) < TOL_BF16
+    r64, S = dw_fwd_terms(act_interval(_nh(x), sc, sh, False, DEV), w.view(C_, k, k), bias, 1, DEV)
+    check_dw_bound(out, r64, S, k, "dw_fwd %s" % (shape,), "depthwise forward")
+    check_stats_bound(st, r64, dw_elem_err(S, k), N * H * W, "dw_fwd %s" % (shape,), "depthwise statistics")
     st = st.cpu().double().sum(-1)
     assert relerr(st[0], ref.double().sum((0, 2, 3))) < TOL_F32
     assert relerr(st[1], (ref.double() ** 2).sum((0, 2, 3))) < TOL_F32
@@ -319,15 +376,17 @@ def test_dw_fwd(shape):
 @pytest.mark.parametrize("shape", DW)
 @pytest.mark.parametrize("phase", [0, 12])
 def test_dw_bwd(shape, phase):
-    """phase 0: fused one-sweep backward; 12: the two-launch form (input gradient, then weight gradient)"""
+    """phase 0: fused one-sweep backward; 12: the two-launch form (input gradient, then weight gradient).
+    + check_dw_bound (input gradient), check_sum_bound with c = 2 (weight gradient: fp32 x fp32 products), check_red_bound; x (the
+    reduce's mask input) and y (dy's) are off the hinge"""
     lib = L.load()
     N, H, W, C_, k = shape
-    x = _x((N, C_, H, W), 1)
     w = O.det_param("t.conv.weight", (C_, 1, k, k), 2)
     sc, sh = 1 + 0.3 * O.det_uniform((C_,), 4), 0.2 * O.det_uniform((C_,), 5)
+    x = _xoff((N, C_, H, W), 1, sc, sh)
     a = F.relu(x * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1))      # act-on-read / dy-on-read: fp32
-    g, y = _x((N, C_, H, W), 6), _x((N, C_, H, W), 7)
     b = rand_bn_coefs(C_, 9, O)
+    g, y = _x((N, C_, H, W), 6), _xoff((N, C_, H, W), 7, b[0], b[1])
     dy = dy_ref(g, y, b, rounded=False)
     ref_gin = torch.nn.grad.conv2d_input((N, C_, H, W), w, dy, padding=k // 2, groups=C_)
     ref_dw = torch.nn.grad.conv2d_weight(a, (C_, 1, k, k), dy, padding=k // 2, groups=C_)
@@ -357,6 +416,11 @@ def test_dw_bwd(shape, phase):
             a_.phase = ph
             L.check(lib.mnas_dw_bwd(C.byref(a_), L.cur_stream()), "dw_bwd")
     assert relerr(from_nhwc(gin), ref_gin) < TOL_BF16
+    what = "dw_bwd %s phase %d" % (shape, phase)
+    div = dy_interval(_nh(g), _nh(y), b, False, DEV)
+    r64, S = dw_dgrad_terms(div, w.view(C_, k, k), H, W, 1, DEV)
+    check_dw_bound(gin, r64, S, k, what, "depthwise input gradient")
+    check_red_bound(redp, gin.float(), xd.float(), b_in, N * H * W, what, "fused reduce (depthwise)")
     gq = from_nhwc(gin)
     s_, t_, mu_, is_ = (b_in[i].view(1, -1, 1, 1) for i in (0, 1, 5, 6))
     dz = (gq * ((s_ * x + t_) > 0)).double()
@@ -367,6 +431,8 @@ def test_dw_bwd(shape, phase):
     grad = torch.full((C_, 1, k, k), float("nan"), device="cuda")
     L.check(lib.mnas_dw_wgrad_finalize(wpart.data_ptr(), rows1, C_, k, grad.data_ptr(), 0, L.cur_stream()))
     assert relerr(grad.cpu(), ref_dw) < TOL_F32
+    r64, S, slack = dw_wgrad_terms(act_interval(_nh(x), sc, sh, False, DEV), div, k, 1, DEV)
+    check_sum_bound(grad.view(C_, k, k), r64, S, N * H * W, rows1, 2, what + " dW", slack, "depthwise weight gradient")
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -374,6 +440,7 @@ def test_dw_bwd(shape, phase):
 # gradient through mnas_dw_fwd / mnas_dw_bwd with stride = 2; odd planes, 5x5, more than 256 channel pairs (two channel blocks)
 @pytest.mark.parametrize("shape", [(2, 12, 12, 48, 3), (3, 13, 11, 72, 5), (2, 9, 9, 600, 3), (5, 7, 8, 32, 5)])
 def test_dw_stride2(shape):
+    """+ the bounds of test_dw_fwd / test_dw_bwd at stride 2"""
     lib = L.load()
     N, H, W, C_, k = shape
     p = k // 2
@@ -398,11 +465,15 @@ def test_dw_stride2(shape):
     f.w, f.bias, f.out, f.stats = wp.data_ptr(), db.data_ptr(), out.data_ptr(), st.data_ptr()
     L.check(lib.mnas_dw_fwd(C.byref(f), L.cur_stream()), "dw_fwd stride 2")
     assert relerr(from_nhwc(out), ref) < TOL_BF16
+    aiv = act_interval(_nh(x), sc, sh, False, DEV)
+    r64, S = dw_fwd_terms(aiv, w.view(C_, k, k), bias, 2, DEV)
+    check_dw_bound(out, r64, S, k, "dw_fwd s2 %s" % (shape,), "depthwise forward")
+    check_stats_bound(st, r64, dw_elem_err(S, k), N * Ho * Wo, "dw_fwd s2 %s" % (shape,), "depthwise statistics")
     s1, s2 = st[0].cpu().double().sum(-1), st[1].cpu().double().sum(-1)
     assert relerr(s1, ref.double().sum((0, 2, 3))) < 1e-3 and relerr(s2, (ref.double() ** 2).sum((0, 2, 3))) < 1e-3
     # backward: dy-on-read from (g, y, coef) at the OUTPUT resolution
-    g, y = _x((N, C_, Ho, Wo), 6), _x((N, C_, Ho, Wo), 7)
     b = rand_bn_coefs(C_, 9, O)
+    g, y = _x((N, C_, Ho, Wo), 6), _xoff((N, C_, Ho, Wo), 7, b[0], b[1])
     dy = dy_ref(g, y, b, rounded=False)
     ref_gin = torch.nn.grad.conv2d_input((N, C_, H, W), w, dy, stride=2, padding=p, groups=C_)
     ref_dw = torch.nn.grad.conv2d_weight(a, (C_, 1, k, k), dy, stride=2, padding=p, groups=C_)
@@ -418,9 +489,14 @@ def test_dw_stride2(shape):
         d.phase = ph
         L.check(lib.mnas_dw_bwd(C.byref(d), L.cur_stream()), "dw_bwd stride 2")
     assert relerr(from_nhwc(gin), ref_gin) < TOL_BF16
+    div = dy_interval(_nh(g), _nh(y), b, False, DEV)
+    r64, S = dw_dgrad_terms(div, w.view(C_, k, k), H, W, 2, DEV)
+    check_dw_bound(gin, r64, S, k, "dw_bwd s2 %s" % (shape,), "depthwise input gradient")
     grad = torch.full((C_, 1, k, k), float("nan"), device="cuda")
     L.check(lib.mnas_dw_wgrad_finalize(wpart.data_ptr(), wrows, C_, k, grad.data_ptr(), 0, L.cur_stream()))
     assert relerr(grad.cpu(), ref_dw) < TOL_F32
+    r64, S, slack = dw_wgrad_terms(aiv, div, k, 2, DEV)
+    check_sum_bound(grad.view(C_, k, k), r64, S, N * Ho * Wo, wrows, 2, "dw_bwd s2 %s dW" % (shape,), slack, "depthwise weight gradient")
     d.phase = 0                                        # the fused one-sweep form exists for stride 1 only
     assert lib.mnas_dw_bwd(C.byref(d), L.cur_stream()) == L.EINVAL
 
@@ -647,16 +723,17 @@ PWB = [  # N,H,W,Ci,Co  -- every supported (cin tiles, cout tiles) pair; ragged 
 @pytest.mark.parametrize("variant", ["virt_red", "plain_resid", "virt"])
 @pytest.mark.parametrize("nparts", [1, 3])
 def test_pw_bwd_fused(shape, variant, nparts):
+    """+ check_onload_bound (gin), check_sum_bound c = 1 (dW over both intervals), check_red_bound; x and y off the hinge"""
     lib = L.load()
     N, H, W, Ci, Co = shape
     assert lib.mnas_pw_bwd_supported(Ci, Co) == 1
     M = N * H * W
-    x = _x((N, Ci, H, W), 1)
     virt = variant != "plain_resid"
     bx = rand_bn_coefs(Ci, 22, O)                         # bnbuf of x's producer: rows 0/1 = scale/shift
+    x = _xoff((N, Ci, H, W), 1, bx[0], bx[1])
     a = bf16r(F.relu(x * bx[0].view(1, -1, 1, 1) + bx[1].view(1, -1, 1, 1))) if virt else x
-    g, y = _x((N, Co, H, W), 6), _x((N, Co, H, W), 7)
     b = rand_bn_coefs(Co, 9, O)
+    g, y = _x((N, Co, H, W), 6), _xoff((N, Co, H, W), 7, b[0], b[1])
     dy = dy_ref(g, y, b)
     w = bf16r(O.det_param("t.conv.weight", (Co, Ci, 1, 1), 2))
     resid = _x((N, Ci, H, W), 5)
@@ -679,7 +756,15 @@ def test_pw_bwd_fused(shape, variant, nparts):
     grad = torch.full((Co, Ci, 1, 1), float("nan"), device="cuda")
     L.check(lib.mnas_wgrad_finalize(wpart.data_ptr(), nparts, Co, Ci, 1, grad.data_ptr(), 0, L.cur_stream()))
     assert relerr(grad.cpu(), ref_dw) < TOL_F32
+    what = "pw_bwd %s %s nparts %d" % (shape, variant, nparts)
+    div = dy_interval(_nh(g), _nh(y), b, True, DEV)
+    r64, slack, S = onload_dgrad_terms(div, w, H, W, 1, 0, _nh(resid) if variant == "plain_resid" else None, DEV)
+    check_onload_bound(gin, r64, slack, S, Co, what + " gin", "fused 1x1 backward: gin")
+    aiv = act_interval(_nh(x), bx[0], bx[1], True, DEV) if virt else Interval.exact(_nh(x), DEV)
+    r64, S, slack = wgrad_terms(aiv, div, 1, 1, 0, DEV)
+    check_sum_bound(grad, r64, S, M, nparts, 1, what + " dW", slack, "fused 1x1 backward: dW")
     if variant == "virt_red":
+        check_red_bound(redp, gin.float(), xd.float(), bx, M, what, "fused 1x1 backward: reduce")
         gq = from_nhwc(gin)                               # the reduce sees g as stored (bf16)
         s_, t_, mu_, is_ = (bx[i].view(1, -1, 1, 1) for i in (0, 1, 5, 6))
         dz = (gq * ((s_ * x + t_) > 0)).double()
@@ -720,3 +805,207 @@ def test_pack_weights_batch_matches_single():
     torch.cuda.synchronize()
     for a, b in zip(singles, batched):
         assert torch.equal(a, b)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Sparse-pixel probes.  A worst-case bound over M pixels grows with M, so one pixel dropped from (doubled in, misplaced in) a long
+# sum of dense operands can hide inside it.  Here all but a handful of pixels contribute exactly zero -- the live ones sit at the
+# first and last position, on both sides of the first tile boundary and of a workgroup boundary, and at the image corners for
+# k > 1 -- and the operands need no transform (plain x, materialised dy; where the ABI takes a dy-on-load operand only, the
+# identity coefficients below, under which fma(c1, g, fma(c2, y, c3)) = g exactly).  S then holds only those terms and the same
+# check_sum_bound is a few 1e-5 of ONE product.
+def _ident_bn(C_):
+    """bnbuf rows under which s*y+t = y, dy = g and xhat = y exactly: (s,t,c1,c2,c3,mean,invstd) = (1,0,1,0,0,0,1)"""
+    b = torch.zeros(8, C_)
+    b[0] = b[2] = b[6] = 1.0
+    return b
+
+
+def _live(shape, pixels, seed):
+    """(N,H,W,C) NHWC fp32 of bf16 values, zero except at the flat pixel indices `pixels`"""
+    N, H, W, C_ = shape
+    t = torch.zeros(N * H * W, C_)
+    t[pixels] = bf16r(O.det_uniform((len(pixels), C_), seed))
+    return t.view(N, H, W, C_)
+
+
+def _plain_grad(t):
+    g = L.MnasGradIn()
+    g.g = t.data_ptr()
+    return g
+
+
+def _each_pixel_visible(contrib, bound, what):
+    """every live pixel's own contribution exceeds the bound somewhere: dropping or doubling it would leave the bound"""
+    for p, c in contrib:
+        assert bool((c.abs() > 2 * bound).any()), "%s: the probe could not see pixel %d dropped" % (what, p)
+
+
+@pytest.mark.parametrize("k", [1, 3])
+def test_sparse_probe_conv_wgrad(k):
+    """mnas_conv_wgrad (k_wgrad_t: 64-pixel chunks, split b owns pixels [b*chunk, (b+1)*chunk), chunk = 128 here), dense plain x,
+    materialised dy live at 6 (1x1) / 12 (3x3: + image corners) pixels: check_sum_bound, c = 1, zero slack"""
+    N, H, W, Ci, Co, nsplit = 2, 10, 10, 16, 24, 2
+    M = N * H * W
+    px = sorted({0, 63, 64, 127, 128, M - 1} | ({W - 1, (H - 1) * W, H * W - 1, H * W, H * W + W - 1, M - W} if k > 1 else set()))
+    x = _nh(_x((N, Ci, H, W), 1)).contiguous()
+    dy = _live((N, H, W, Co), px, 2)
+    xd, dyd = x.to(torch.bfloat16).cuda(), dy.to(torch.bfloat16).cuda()
+    got = _wgrad(N, H, W, Ci, H, W, Co, k, 1, k // 2, act_in(xd), _plain_grad(dyd), nsplit)
+    r64, S, slack = wgrad_terms(Interval.exact(x, DEV), Interval.exact(dy, DEV), k, 1, k // 2, DEV)
+    assert float(slack.max()) == 0.0
+    what = "sparse conv_wgrad k%d" % k
+    check_sum_bound(got.to(DEV), r64, S, M, nsplit, 1, what, None, "sparse probes")
+    bound = (M + nsplit + 1) * 2.0 ** -22 * S
+    def one(p):
+        d1 = torch.zeros_like(dy)
+        d1.view(M, Co)[p] = dy.view(M, Co)[p]
+        return ref_dense_wgrad(x, d1, k, 1, k // 2, DEV)
+    _each_pixel_visible([(p, one(p)) for p in px], bound, what)
+
+
+def test_sparse_probe_pw_bwd():
+    """mnas_pw_bwd in segment mode (workgroup b owns pixels [b*seg_px, (b+1)*seg_px)): dW and the fused reduce with g live at the
+    first / last pixel and on both sides of the first tile and the first segment boundary; x read through the identity (1, 0)
+    (act = relu(x) exactly), dy through the identity coefficients (dy = g exactly).  check_sum_bound c = 1 (zero slack) and
+    check_red_bound (gin is zero off the live pixels)."""
+    lib = L.load()
+    Ci, Co = 32, 16
+    tile = lib.mnas_pw_bwd_tile_pixels(Ci, Co)
+    assert tile in (64, 128)
+    seg = tile + tile // 2
+    M = 2 * seg + 37
+    nparts = (M + seg - 1) // seg
+    px = sorted({0, tile - 1, tile, seg - 1, seg, M - 1})
+    bx, b = _ident_bn(Ci), _ident_bn(Co)
+    x = off_hinge(bf16r(O.det_uniform((1, 1, M, Ci), 1)), bx[0], bx[1])
+    g = _live((1, 1, M, Co), px, 2)
+    w = bf16r(O.det_param("t.conv.weight", (Co, Ci, 1, 1), 2))
+    xd, gd, yd = x.to(torch.bfloat16).cuda(), g.to(torch.bfloat16).cuda(), torch.ones((1, 1, M, Co), dtype=torch.bfloat16, device="cuda")
+    bxd, bd = bx.cuda(), b.cuda()
+    gin, gchk = guarded((1, 1, M, Ci), torch.bfloat16)
+    wpart, wchk = guarded((nparts, Co, Ci), torch.float32)
+    redp, rchk = guarded((2, Ci, nparts), torch.float32)
+    c = L.MnasPwBwd()
+    c.M, c.Ci, c.Co, c.nparts, c.seg_px = M, Ci, Co, nparts, seg
+    c.x, c.dy = act_in(xd, bxd[0], bxd[1]), grad_in(gd, yd, bd)
+    c.w, c.gin, c.wpartial = L.ptr(pack(w, L.PACK_DGRAD)), L.ptr(gin), L.ptr(wpart)
+    c.red_partial, c.red_y, c.red_bn = L.ptr(redp), L.ptr(xd), L.ptr(bxd)
+    L.check(lib.mnas_pw_bwd(C.byref(c), L.cur_stream()), "pw_bwd")
+    for chk, n in ((gchk, "gin"), (wchk, "wpartial"), (rchk, "red_partial")):
+        chk("sparse pw_bwd " + n)
+    grad = torch.full((Co, Ci, 1, 1), float("nan"), device="cuda")
+    L.check(lib.mnas_wgrad_finalize(wpart.data_ptr(), nparts, Co, Ci, 1, grad.data_ptr(), 0, L.cur_stream()))
+    a = torch.relu(x)
+    r64, S, slack = wgrad_terms(Interval.exact(a, DEV), Interval.exact(g, DEV), 1, 1, 0, DEV)
+    check_sum_bound(grad, r64, S, M, nparts, 1, "sparse pw_bwd dW", None, "sparse probes")
+    _each_pixel_visible([(p, torch.outer(g.view(M, Co)[p], a.view(M, Ci)[p]).view(Co, Ci, 1, 1).to(DEV)) for p in px],
+                        (M + nparts + 1) * 2.0 ** -22 * S, "sparse pw_bwd dW")
+    dead = torch.ones(M, dtype=torch.bool)
+    dead[px] = False
+    assert not bool(gin.view(M, Ci)[dead.cuda()].any()), "gin of a pixel with dy = 0 is not zero"
+    check_red_bound(redp, gin.float(), xd.float(), bx, M, "sparse pw_bwd", "sparse probes")
+
+
+def _dw_probe_case(N, H, W, C_, k, which):
+    """live dy pixels for a depthwise sweep of launch form `which` (as mnas_dw_rows): image corners (first and last pixel among
+    them), both sides of the first strip boundary (column 4*sx) on both sides of the first DMA row-group boundary"""
+    lib = L.load()
+    geo = (C.c_int * 7)()
+    assert lib.mnas_dw_geometry(N, H, W, C_, k, which, geo) == 0
+    tw, strips, G_ = 4 * geo[1], geo[3], geo[6]
+    rb = next(r for r in range(G_ - k // 2, H, G_) if r >= 1)     # groups start at row -PAD: first boundary inside the image (rows rb-1 | rb)
+    assert strips >= 2 and 0 < tw < W and 0 < rb < H, (tw, strips, G_)
+    at = lambda n, h, w_: (n * H + h) * W + w_
+    px = {at(n, h, w_) for n in range(N) for h in (0, H - 1) for w_ in (0, W - 1)}
+    px |= {at(0, h, w_) for h in (rb - 1, rb) for w_ in (tw - 1, tw)}
+    return sorted(px)
+
+
+@pytest.mark.parametrize("phase,k", [(0, 3), (2, 5)])
+def test_sparse_probe_dw_bwd(phase, k):
+    """mnas_dw_bwd phase 0 (fused: dW and reduce checked) and phase 2 (dW): g live at the image corners and around the first strip /
+    row-group boundary (mnas_dw_geometry), x dense through the identity (1, 0), dy = g through the identity coefficients.
+    check_sum_bound c = 2 (zero slack), check_red_bound."""
+    lib = L.load()
+    N, H, W, C_ = 2, 9, 20, 144
+    which = 1 if phase == 0 else 3
+    px = _dw_probe_case(N, H, W, C_, k, which)
+    bx, b = _ident_bn(C_), _ident_bn(C_)
+    x = off_hinge(bf16r(O.det_uniform((N, H, W, C_), 1)), bx[0], bx[1])
+    g = _live((N, H, W, C_), px, 2)
+    w = O.det_param("t.conv.weight", (C_, 1, k, k), 2)
+    xd, gd = x.to(torch.bfloat16).cuda(), g.to(torch.bfloat16).cuda()
+    yd = torch.ones((N, H, W, C_), dtype=torch.bfloat16, device="cuda")
+    bxd, bd = bx.cuda(), b.cuda()
+    nparts = 37
+    rows = lib.mnas_dw_rows(N, H, W, C_, k, nparts, which)
+    assert rows >= 2
+    gin, gchk = guarded((N, H, W, C_), torch.bfloat16)
+    wpart, wchk = guarded((rows, k * k, C_), torch.float32)
+    redp, rchk = guarded((2, C_, rows), torch.float32)
+    d = L.MnasDwBwd()
+    d.N, d.H, d.W, d.C, d.k, d.nparts, d.phase = N, H, W, C_, k, nparts, phase
+    d.x, d.dy = act_in(xd, bxd[0], bxd[1]), grad_in(gd, yd, bd)
+    d.w, d.gin, d.wpartial = L.ptr(pack(w, L.PACK_DW)), L.ptr(gin), L.ptr(wpart)
+    if phase == 0:
+        d.red_bn, d.red_partial = L.ptr(bxd), L.ptr(redp)
+    L.check(lib.mnas_dw_bwd(C.byref(d), L.cur_stream()), "dw_bwd")
+    what = "sparse dw_bwd phase %d k%d" % (phase, k)
+    wchk(what + " wpartial")
+    grad = torch.full((C_, k, k), float("nan"), device="cuda")
+    L.check(lib.mnas_dw_wgrad_finalize(wpart.data_ptr(), rows, C_, k, grad.data_ptr(), 0, L.cur_stream()))
+    r64, S, slack = dw_wgrad_terms(Interval.exact(torch.relu(x), DEV), Interval.exact(g, DEV), k, 1, DEV)
+    check_sum_bound(grad, r64, S, N * H * W, rows, 2, what + " dW", None, "sparse probes")
+    if phase == 0:
+        gchk(what + " gin")
+        rchk(what + " red_partial")
+        check_red_bound(redp, gin.float(), xd.float(), bx, N * H * W, what, "sparse probes")
+
+
+def test_sparse_probe_conv_gemm_statistics():
+    """statistics of mnas_conv_gemm mode 0 (1x1, plain x, no bias, two workgroups): x live at the first / last pixel and on both
+    sides of the first two tile boundaries; every other output element must be exactly zero, check_stats_bound"""
+    lib = L.load()
+    Ci, Co = 48, 16
+    tile = lib.mnas_conv_gemm_tile_pixels(2 * 128 + 37, Co, Ci)
+    assert tile in (64, 128)
+    M = 2 * tile + 37
+    assert lib.mnas_conv_gemm_tile_pixels(M, Co, Ci) == tile
+    px = sorted({0, tile - 1, tile, 2 * tile - 1, 2 * tile, M - 1})
+    x = _live((1, 1, M, Ci), px, 1)
+    w = bf16r(O.det_param("t.conv.weight", (Co, Ci, 1, 1), 2))
+    xd = x.to(torch.bfloat16).cuda()
+    out, st = conv_gemm(0, 1, 1, M, Ci, 1, M, Co, 1, 1, 0, pack(w, L.PACK_FWD), None, act=act_in(xd), nparts=2, stats=True, guard=True)
+    r64, slack, S = onload_fwd_terms(Interval.exact(x, DEV), w, None, device=DEV)
+    check_onload_bound(out, r64, slack, S, Ci, "sparse conv_gemm", "sparse probes: elements")
+    dead = torch.ones(M, dtype=torch.bool, device="cuda")
+    dead[px] = False
+    assert not bool(out.view(M, Co)[dead].any())
+    check_stats_bound(st, r64, onload_elem_err(slack, S, Ci), M, "sparse conv_gemm", "sparse probes")
+
+
+def test_sparse_probe_dw_fwd_statistics():
+    """statistics of mnas_dw_fwd (plain x, no bias, fp32 weights): x live at the image corners and around the first strip /
+    row-group boundary; check_dw_bound and check_stats_bound"""
+    lib = L.load()
+    N, H, W, C_, k = 2, 9, 20, 144, 5
+    px = _dw_probe_case(N, H, W, C_, k, 0)
+    x = _live((N, H, W, C_), px, 1)
+    w = O.det_param("t.conv.weight", (C_, 1, k, k), 2)
+    xd = x.to(torch.bfloat16).cuda()
+    nparts = 40
+    rows = lib.mnas_dw_rows(N, H, W, C_, k, nparts, 0)
+    assert rows >= 2
+    out, ochk = guarded((N, H, W, C_), torch.bfloat16)
+    st, schk = guarded((2, C_, rows), torch.float32)
+    f = L.MnasDwFwd()
+    f.N, f.H, f.W, f.C, f.k, f.nparts = N, H, W, C_, k, nparts
+    f.in_ = act_in(xd)
+    f.w, f.out, f.stats = L.ptr(pack(w, L.PACK_DW)), L.ptr(out), L.ptr(st)
+    L.check(lib.mnas_dw_fwd(C.byref(f), L.cur_stream()), "dw_fwd")
+    ochk("sparse dw_fwd out")
+    schk("sparse dw_fwd stats")
+    r64, S = dw_fwd_terms(Interval.exact(x, DEV), w.view(C_, k, k), None, 1, DEV)
+    check_dw_bound(out, r64, S, k, "sparse dw_fwd", "sparse probes: elements")
+    check_stats_bound(st, r64, dw_elem_err(S, k), N * H * W, "sparse dw_fwd", "sparse probes")

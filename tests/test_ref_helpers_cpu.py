@@ -5,7 +5,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import (bits_equal, guarded, ref_dense_s2_dgrad, ref_dw_dgrad, ref_dw_fwd, ref_dw_wgrad, ref_dy)
+from gpu_util import (Interval, bits_equal, guarded, ref_dense_s2_dgrad, ref_dw_dgrad, ref_dw_dgrad_s, ref_dw_fwd, ref_dw_wgrad,
+                      ref_dw_wgrad_s, ref_dy)
 
 
 def _r(shape, seed):
@@ -30,6 +31,25 @@ def test_depthwise_references(N, H, W, C_, k):
            torch.nn.grad.conv2d_input((N, C_, H, W), w4, _nchw(dy), padding=k // 2, groups=C_))
     _close(ref_dw_wgrad(x, dy, k),
            torch.nn.grad.conv2d_weight(_nchw(x), (C_, 1, k, k), _nchw(dy), padding=k // 2, groups=C_).view(C_, k, k))
+
+
+@pytest.mark.parametrize("N,H,W,C_,k,stride", [(2, 7, 9, 8, 3, 2), (1, 6, 4, 16, 5, 2), (2, 5, 5, 8, 5, 1), (2, 8, 8, 8, 3, 2)])
+def test_strided_depthwise_gradient_references(N, H, W, C_, k, stride):
+    p = k // 2
+    Ho, Wo = (H + 2 * p - k) // stride + 1, (W + 2 * p - k) // stride + 1
+    x, dy, w = _r((N, H, W, C_), 1), _r((N, Ho, Wo, C_), 2), _r((C_, k, k), 3)
+    w4 = w.view(C_, 1, k, k)
+    _close(_nchw(ref_dw_dgrad_s(dy, w, H, W, stride)),
+           torch.nn.grad.conv2d_input((N, C_, H, W), w4, _nchw(dy), stride=stride, padding=p, groups=C_))
+    _close(ref_dw_wgrad_s(x, dy, k, stride),
+           torch.nn.grad.conv2d_weight(_nchw(x), (C_, 1, k, k), _nchw(dy), stride=stride, padding=p, groups=C_).view(C_, k, k))
+
+
+def test_interval_identities():
+    lo = _r((40, 8), 9)
+    iv = Interval(lo, lo + _r((40, 8), 10).abs())
+    assert torch.allclose(iv.amax, iv.mid.abs() + iv.half, rtol=0, atol=1e-15)       # what wgrad_terms' slack relies on
+    assert bool((iv.mid - iv.half - iv.lo).abs().max() < 1e-15)
 
 
 @pytest.mark.parametrize("N,H,W,Ci,Co", [(2, 8, 10, 16, 24), (1, 7, 9, 8, 16), (3, 14, 14, 24, 8), (2, 2, 2, 8, 8), (1, 1, 3, 8, 8)])
