@@ -56,7 +56,7 @@ typedef struct MnasGradIn {
     const float* coef;    /* float[5][C] */
 } MnasGradIn;
 
-int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, additive: no layout or opcode changed; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
+int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, and + mnas_grad_sqnorm / mnas_*_step_ex, all additive: no layout or opcode changed, so still 8; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
                                          * 5 = squeeze-excite on load: MnasConvGemm.gate, MnasPwBwd.seg_px -- and in round 5: 6 = the opt-in
                                          * forms that lost their A/B are gone (MnasPwBwd.dy_out / red4, MnasDwBwd.src_* / g_gate / g_bias,
                                          * mnas_dw_exp_*, mnas_irb_*, mnas_gram*, mnas_se_bn_assemble); their opcode numbers stay retired) */
@@ -635,6 +635,59 @@ int mnas_rmsprop_step(float* p, const float* g, float* square_avg, float* moment
                       float eps, float weight_decay, float momentum, float grad_scale, void* stream);
 int mnas_sgd_step(float* p, const float* g, float* momentum_buf, int64_t n, float lr, float momentum, float dampening,
                   float weight_decay, int nesterov, int step, float grad_scale, void* stream);
+
+/* ---- global-norm gradient clipping, non-finite skip and weight EMA on the flat buffers ------------------
+ * Additive: four new symbols and three new structs; no existing entry point, struct layout, opcode or kernel changes, so the ABI
+ * version stays 8.
+ *
+ * The norm is that of the gradient the optimizer consumes, g[i] * grad_scale (the product formed in fp32), over every trainable
+ * run of the flat buffer.  One deterministic launch per run leaves fp64 partial sums of squares in consecutive slots of ONE table of
+ * MNAS_GRADNORM_MAX_PARTS doubles; every workgroup of every *_step_ex launch of the step then reduces the nparts used slots itself,
+ * in a fixed order, so all of them derive the same bits  S = sum of the slots,  norm = (float)sqrt(S)  with no finalize launch and
+ * nothing read by the host.  No atomics anywhere: the same input gives the same partials, norm and coefficient on every run and on
+ * every rank of a data-parallel job. */
+#define MNAS_GRADNORM_MAX_PARTS 1024
+/* Device block the *_step_ex launch with update_stats != 0 moves (thread 0 of workgroup 0; zero it to reset).  32 bytes. */
+typedef struct MnasGradStats {
+    float   last_norm;        /* norm of the last step (0 when no norm was taken: EMA only) */
+    float   last_coef;        /* clip coefficient of the last step as computed (1 when not clipping) */
+    int64_t steps;            /* *_step_ex steps, skipped ones included */
+    int64_t clipped_steps;    /* steps applied with coef < 1 */
+    int64_t skipped_steps;    /* steps dropped by skip_nonfinite */
+} MnasGradStats;
+/* One run's partial sums: grid = min(256, ceil(n / 1024)) workgroups of 256 threads, a function of n only; workgroup b writes
+ * partial[part_offset + b].  Every lane adds the squares of its grid-stride elements in increasing index order in fp64 (the fp32
+ * product g[i] * grad_scale widened first: 1e25 squares to a finite value), then a wave-64 butterfly, then the four waves through
+ * LDS in wave order.  g needs 4-byte alignment only (a run may start at any element).  *nparts_out (HOST, may be NULL) = the
+ * grid; n == 0 launches nothing and reports 0.  MNAS_EINVAL, and no launch, when part_offset < 0 or part_offset + grid exceeds
+ * MNAS_GRADNORM_MAX_PARTS. */
+int mnas_grad_sqnorm(const float* g, int64_t n, float grad_scale, double* partial, int part_offset, int* nparts_out, void* stream);
+/* HOST struct: what a *_step_ex launch does beyond its plain counterpart.
+ *   coef = 1, or with 0 < max_norm < +inf:  q = max_norm / (norm + 1e-6f) in fp32, coef = q < 1 ? q : 1, a NaN q kept
+ *          (torch.nn.utils.clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max = 1)); the update consumes
+ *          (g[i] * grad_scale) * coef in front of the weight-decay fma -- with coef == 1 bit for bit the plain update;
+ *   skip_nonfinite and a NaN / Inf norm: the launch writes nothing to p, the moments or the EMA, and the step counts as skipped;
+ *          without the flag a non-finite norm propagates through coef as in torch (error_if_nonfinite = False);
+ *   ema != NULL: after p[i] is written, ema[i] = fmaf(ema_decay, ema[i], (1 - ema_decay) * p[i]); ema points at the run's first
+ *          element like p; ema_decay in [0, 1);
+ *   update_stats: set on ONE launch of a step (the first run's).
+ * nparts == 0 (no norm taken) is valid for an EMA-only step: max_norm and skip_nonfinite must then be off. */
+typedef struct MnasOptExtra {
+    const double*  partial;         /* the table mnas_grad_sqnorm filled; may be NULL when nparts == 0 */
+    int32_t        nparts;          /* used slots, 0 .. MNAS_GRADNORM_MAX_PARTS */
+    float          max_norm;        /* <= 0 or +inf: do not clip */
+    int32_t        skip_nonfinite;
+    float*         ema;             /* NULL: no EMA */
+    float          ema_decay;
+    MnasGradStats* stats;           /* DEVICE; may be NULL when update_stats == 0 */
+    int32_t        update_stats;
+} MnasOptExtra;
+int mnas_adam_step_ex(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                      float weight_decay, int step, float grad_scale, const MnasOptExtra* extra, void* stream);
+int mnas_rmsprop_step_ex(float* p, const float* g, float* square_avg, float* momentum_buf, int64_t n, float lr, float alpha,
+                         float eps, float weight_decay, float momentum, float grad_scale, const MnasOptExtra* extra, void* stream);
+int mnas_sgd_step_ex(float* p, const float* g, float* momentum_buf, int64_t n, float lr, float momentum, float dampening,
+                     float weight_decay, int nesterov, int step, float grad_scale, const MnasOptExtra* extra, void* stream);
 
 /* ---- batched launch: run a pre-built list of the calls above with ONE host->library transition ------- */
 #define MNAS_OP_CONV_GEMM 1

@@ -287,6 +287,21 @@ class MnasMultiLabelMeters(C.Structure):
                                         "last_dice_sum", "last_f1_sum")]
 
 
+GRADNORM_MAX_PARTS = 1024                                       # MNAS_GRADNORM_MAX_PARTS
+
+
+class MnasGradStats(C.Structure):
+    """include/mnas.h: the device block the *_step_ex launches move (32 bytes: two floats, three int64)"""
+    _fields_ = [("last_norm", c_float), ("last_coef", c_float), ("steps", c_int64), ("clipped_steps", c_int64),
+                ("skipped_steps", c_int64)]
+
+
+class MnasOptExtra(C.Structure):
+    """include/mnas.h: HOST struct of the clip / skip / EMA arguments of a *_step_ex launch"""
+    _fields_ = [("partial", c_void_p), ("nparts", C.c_int32), ("max_norm", c_float), ("skip_nonfinite", C.c_int32),
+                ("ema", c_void_p), ("ema_decay", c_float), ("stats", c_void_p), ("update_stats", C.c_int32)]
+
+
 SYMBOLS = {
     "mnas_conv_img_parts": (c_int, [c_int] * 11),
     "mnas_stem_parts": (c_int, [c_int, c_int, c_int, c_int, c_int]),
@@ -369,6 +384,13 @@ SYMBOLS = {
                                   c_float, c_void_p]),
     "mnas_sgd_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int, c_int, c_float,
                               c_void_p]),
+    "mnas_grad_sqnorm": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_int, C.POINTER(c_int), c_void_p]),
+    "mnas_adam_step_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
+                                  c_float, c_int, c_float, C.POINTER(MnasOptExtra), c_void_p]),
+    "mnas_rmsprop_step_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
+                                     c_float, C.POINTER(MnasOptExtra), c_void_p]),
+    "mnas_sgd_step_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int, c_int, c_float,
+                                 C.POINTER(MnasOptExtra), c_void_p]),
     "mnas_run_ops": (c_int, [C.POINTER(MnasOp), c_int, c_void_p, C.POINTER(c_int)]),
     "mnas_run_ops_multi": (c_int, [C.POINTER(MnasOp), c_int, C.POINTER(c_void_p), c_int, C.POINTER(c_int)]),
     "mnas_event_create": (c_int, [C.POINTER(c_void_p)]),

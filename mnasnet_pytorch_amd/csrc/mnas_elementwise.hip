@@ -925,3 +925,210 @@ extern "C" int mnas_adam_step(float* p, const float* g, float* m, float* v, int6
     MNAS_CHECK_LAUNCH();
     return MNAS_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// global-norm gradient clipping, non-finite skip and weight EMA on the flat buffers (include/mnas.h)
+// ------------------------------------------------------------------------------------------------
+// wave-64 butterfly: every lane ends with the same bits (each level adds the same two values on both sides)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// 256 threads: wave butterfly, then the four waves in wave order.  red: 4 doubles of LDS.  Every thread gets the sum.
+__device__ __forceinline__ double block_sum_f64(double v, double* red, int tid) {
+    v = wave_sum_f64(v);
+    if ((tid & 63) == 0) red[tid >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+// partial[part_offset + blockIdx.x] = sum over the workgroup's grid-stride elements of ((double)(g[i] * gscale))^2.  Dword loads
+// (the run starts at any element), four in flight per lane and trip; one fp64 accumulator per lane, elements in increasing order.
+__global__ __launch_bounds__(256) void k_grad_sqnorm(const float* __restrict__ g, int64_t n, float gscale,
+                                                     double* __restrict__ partial, int part_offset) {
+    __shared__ double red[4];
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += 4 * stride) {
+        float v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = (i + j * stride < n) ? g[i + j * stride] : 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double d = (double)(v[j] * gscale);
+            acc = fma(d, d, acc);               // d * d is exact in fp64 (24-bit significands)
+        }
+    }
+    acc = block_sum_f64(acc, red, threadIdx.x);
+    if (threadIdx.x == 0) partial[part_offset + blockIdx.x] = acc;
+}
+static int sqnorm_blocks(int64_t n) {
+    const int64_t blocks = (n + 1023) / 1024;
+    return (int)(blocks > 256 ? 256 : blocks);
+}
+extern "C" int mnas_grad_sqnorm(const float* g, int64_t n, float grad_scale, double* partial, int part_offset, int* nparts_out,
+                                void* stream) {
+    if (!g || !partial || n < 0 || part_offset < 0) return MNAS_EINVAL;
+    const int blocks = sqnorm_blocks(n);
+    if (part_offset > MNAS_GRADNORM_MAX_PARTS - blocks) return MNAS_EINVAL;
+    if (nparts_out) *nparts_out = blocks;
+    if (blocks == 0) return MNAS_OK;
+    hipLaunchKernelGGL(k_grad_sqnorm, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n, grad_scale, partial, part_offset);
+    MNAS_CHECK_LAUNCH();
+    return MNAS_OK;
+}
+
+// What the *_ex kernels receive of a MnasOptExtra (by value).
+struct OptExtra {
+    const double* partial;
+    float* ema;
+    MnasGradStats* stats;
+    int nparts;
+    float max_norm;       // 0: do not clip (the host folds <= 0 and +inf into 0)
+    float ema_decay;
+    int skip_nonfinite, update_stats;
+};
+// Head of every *_ex kernel: the workgroup's own reduce of the partial table (thread t takes slots t, t + 256, ... in index
+// order, then the fixed tree: the same bits in every workgroup of every launch of the step), the clip coefficient, the skip
+// decision and the stats block.  false: the launch writes nothing.  Wave-uniform throughout.
+__device__ __forceinline__ bool opt_extra_head(const OptExtra& x, float* coef_out) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    float norm = 0.f;
+    if (x.nparts > 0) {
+        double s = 0.0;
+        for (int i = tid; i < x.nparts; i += 256) s += x.partial[i];
+        norm = (float)sqrt(block_sum_f64(s, red, tid));
+    }
+    float coef = 1.f;
+    if (x.max_norm > 0.f) {
+        const float q = x.max_norm / (norm + 1e-6f);
+        coef = (q < 1.f || q != q) ? q : 1.f;       // min(q, 1) that keeps a NaN (torch.clamp)
+    }
+    const bool skip = x.skip_nonfinite && !(fabsf(norm) <= 3.402823466e+38f);
+    if (x.update_stats && blockIdx.x == 0 && tid == 0) {
+        MnasGradStats* st = x.stats;
+        st->last_norm = norm;
+        st->last_coef = coef;
+        st->steps += 1;
+        if (skip) st->skipped_steps += 1;
+        else if (coef < 1.f) st->clipped_steps += 1;
+    }
+    *coef_out = coef;
+    return !skip;
+}
+__device__ __forceinline__ void opt_ema(float* __restrict__ ema, int64_t i, float d, float pn) {
+    ema[i] = fmaf(d, ema[i], (1.f - d) * pn);
+}
+// k_adam / k_rmsprop / k_sgd with gi = (g[i] * gscale) * coef and the EMA written behind p[i]; the rest of each update as above
+__global__ __launch_bounds__(256) void k_adam_ex(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                 float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
+                                                 float wd, float bc1, float bc2_sqrt, float gscale, OptExtra x) {
+    float coef;
+    if (!opt_extra_head(x, &coef)) return;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float gi = (g[i] * gscale) * coef;
+        const float pi = p[i];
+        if (wd != 0.f) gi = fmaf(wd, pi, gi);
+        const float mi = fmaf(b1, m[i], (1.f - b1) * gi);
+        const float vi = fmaf(b2, v[i], (1.f - b2) * gi * gi);
+        m[i] = mi;
+        v[i] = vi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        const float pn = pi - (lr / bc1) * (mi / denom);
+        p[i] = pn;
+        if (x.ema) opt_ema(x.ema, i, x.ema_decay, pn);
+    }
+}
+__global__ __launch_bounds__(256) void k_rmsprop_ex(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sq,
+                                                    float* __restrict__ buf, int64_t n, float lr, float alpha, float eps, float wd,
+                                                    float momentum, float gscale, OptExtra x) {
+    float coef;
+    if (!opt_extra_head(x, &coef)) return;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float gi = (g[i] * gscale) * coef;
+        const float pi = p[i];
+        if (wd != 0.f) gi = fmaf(wd, pi, gi);
+        const float s = fmaf(alpha, sq[i], (1.f - alpha) * gi * gi);
+        sq[i] = s;
+        const float avg = sqrtf(s) + eps;
+        float pn;
+        if (momentum > 0.f) {
+            const float b = fmaf(momentum, buf[i], gi / avg);
+            buf[i] = b;
+            pn = pi - lr * b;
+        } else {
+            pn = pi - lr * (gi / avg);
+        }
+        p[i] = pn;
+        if (x.ema) opt_ema(x.ema, i, x.ema_decay, pn);
+    }
+}
+__global__ __launch_bounds__(256) void k_sgd_ex(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n,
+                                                float lr, float momentum, float dampening, float wd, int nesterov, int first,
+                                                float gscale, OptExtra x) {
+    float coef;
+    if (!opt_extra_head(x, &coef)) return;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float gi = (g[i] * gscale) * coef;
+        const float pi = p[i];
+        if (wd != 0.f) gi = fmaf(wd, pi, gi);
+        if (momentum != 0.f) {
+            const float b = first ? gi : fmaf(momentum, buf[i], (1.f - dampening) * gi);
+            buf[i] = b;
+            gi = nesterov ? fmaf(momentum, b, gi) : b;
+        }
+        const float pn = pi - lr * gi;
+        p[i] = pn;
+        if (x.ema) opt_ema(x.ema, i, x.ema_decay, pn);
+    }
+}
+// MnasOptExtra -> OptExtra; false = MNAS_EINVAL
+static bool opt_extra_args(const MnasOptExtra* e, OptExtra* x) {
+    if (!e || e->nparts < 0 || e->nparts > MNAS_GRADNORM_MAX_PARTS || (e->nparts > 0 && !e->partial)) return false;
+    if (e->ema && !(e->ema_decay >= 0.f && e->ema_decay < 1.f)) return false;
+    if (e->update_stats && !e->stats) return false;
+    if (e->max_norm != e->max_norm) return false;
+    const bool clip = e->max_norm > 0.f && e->max_norm <= 3.402823466e+38f;
+    if ((clip || e->skip_nonfinite) && e->nparts < 1) return false;      // both need the norm
+    x->partial = e->partial; x->ema = e->ema; x->stats = e->stats; x->nparts = e->nparts;
+    x->max_norm = clip ? e->max_norm : 0.f;
+    x->ema_decay = e->ema_decay;
+    x->skip_nonfinite = e->skip_nonfinite ? 1 : 0;
+    x->update_stats = e->update_stats ? 1 : 0;
+    return true;
+}
+extern "C" int mnas_adam_step_ex(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                                 float eps, float weight_decay, int step, float grad_scale, const MnasOptExtra* extra, void* stream) {
+    OptExtra x;
+    if (step < 1 || n < 0 || !p || !g || !m || !v || !opt_extra_args(extra, &x)) return MNAS_EINVAL;
+    if (n == 0) return MNAS_OK;
+    const float bc1 = 1.f - powf(beta1, (float)step);
+    const float bc2 = 1.f - powf(beta2, (float)step);
+    hipLaunchKernelGGL(k_adam_ex, dim3(opt_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2, eps,
+                       weight_decay, bc1, sqrtf(bc2), grad_scale, x);
+    MNAS_CHECK_LAUNCH();
+    return MNAS_OK;
+}
+extern "C" int mnas_rmsprop_step_ex(float* p, const float* g, float* square_avg, float* momentum_buf, int64_t n, float lr,
+                                    float alpha, float eps, float weight_decay, float momentum, float grad_scale,
+                                    const MnasOptExtra* extra, void* stream) {
+    OptExtra x;
+    if (n < 0 || !p || !g || !square_avg || (momentum > 0.f && !momentum_buf) || !opt_extra_args(extra, &x)) return MNAS_EINVAL;
+    if (n == 0) return MNAS_OK;
+    hipLaunchKernelGGL(k_rmsprop_ex, dim3(opt_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, square_avg, momentum_buf, n, lr,
+                       alpha, eps, weight_decay, momentum, grad_scale, x);
+    MNAS_CHECK_LAUNCH();
+    return MNAS_OK;
+}
+extern "C" int mnas_sgd_step_ex(float* p, const float* g, float* momentum_buf, int64_t n, float lr, float momentum, float dampening,
+                                float weight_decay, int nesterov, int step, float grad_scale, const MnasOptExtra* extra,
+                                void* stream) {
+    OptExtra x;
+    if (n < 0 || step < 1 || !p || !g || (momentum != 0.f && !momentum_buf) || !opt_extra_args(extra, &x)) return MNAS_EINVAL;
+    if (n == 0) return MNAS_OK;
+    hipLaunchKernelGGL(k_sgd_ex, dim3(opt_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, momentum_buf, n, lr, momentum,
+                       dampening, weight_decay, nesterov, step == 1 ? 1 : 0, grad_scale, x);
+    MNAS_CHECK_LAUNCH();
+    return MNAS_OK;
+}

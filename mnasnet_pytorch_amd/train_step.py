@@ -16,7 +16,10 @@ small ones.  The optimizer is one fused Adam launch over the flat par
 """
 from __future__ import annotations
 
-from typing import List, Optional
+import contextlib
+import ctypes
+import math
+from typing import List, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -101,6 +104,15 @@ class BucketSchedule:
         self.buckets.wait()
 
 
+class GradStats(NamedTuple):
+    """FlatAdam.grad_stats() / Trainer.grad_stats(): the MnasGradStats block (include/mnas.h) on the host"""
+    last_norm: float
+    last_coef: float
+    steps: int
+    clipped_steps: int
+    skipped_steps: int
+
+
 class FlatAdam(torch.optim.Optimizer):
     """``torch.optim.Adam`` (train.py:219-221) over ONE flat fp32 buffer: a single fused launch (``mnas_adam_step``) instead
     of ~110 per-tensor updates.  It is a real ``torch.optim.Optimizer``:
@@ -112,9 +124,28 @@ class FlatAdam(torch.optim.Optimizer):
     * parameters with ``requires_grad == False`` (``FineTuneModelPool.freeze()``, classifiers.py:95-99) are left
       untouched: the update runs over the contiguous runs of trainable elements only, so weight decay cannot move a
       frozen weight.
+
+    Three optional pieces of the step run on the same buffers without a host read (include/mnas.h).  They
+    are plain attributes read at every step, like ``lr``, so a caller can schedule them (an EMA warm-up, say):
+
+    * ``clip_grad_norm`` (None = off, else > 0): the gradient the update consumes -- ``flat_g * grad_scale`` over the trainable runs
+      -- is scaled by ``min(1, clip_grad_norm / (norm + 1e-6))``, ``torch.nn.utils.clip_grad_norm_``'s arithmetic;
+    * ``skip_nonfinite``: a step whose gradient norm is NaN / Inf changes neither the parameters nor the moments nor the EMA;
+    * ``ema_decay`` (None = off, else in [0, 1)): ``flat_ema = d * flat_ema + (1 - d) * flat_p`` behind the update, in the same
+      launch.  ``flat_ema`` is a copy of ``flat_p`` taken when the EMA is first enabled (:meth:`reset_ema` takes it again, e.g.
+      after loading a checkpoint into the model).  Frozen parameters are outside the norm and the EMA update.
+
+    With all three off ``step()`` issues exactly the plain launches.  Otherwise: one ``mnas_grad_sqnorm`` launch per trainable run
+    (none when only the EMA is on), then one ``*_step_ex`` launch per run; :meth:`grad_stats` reads the device counters.
+
+    Deviation on skipped steps: the skip is decided on the device, so the host ``step_count`` advances on a skipped step too
+    (rolling it back would take the host read this path exists to avoid).  After a skip, Adam's bias correction and the native
+    head's dropout seeds are therefore one step ahead of a torch run that skipped the same step, and SGD with ``dampening != 0``
+    differs from it when step 1 is the skipped one (torch would seed the momentum buffer with the next gradient, undamped).
     """
 
-    def __init__(self, params, flat_p, flat_g, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
+    def __init__(self, params, flat_p, flat_g, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0,
+                 clip_grad_norm=None, skip_nonfinite=False, ema_decay=None):
         params = list(params)
         n = sum(p.numel() for p in params)
         if flat_p.numel() != n or flat_g.numel() != n:
@@ -134,6 +165,73 @@ class FlatAdam(torch.optim.Optimizer):
         self.grad_scale = grad_scale      # 1/world_size: the all-reduce sums, Adam sees the mean (DataParallel semantics)
         self._lib = L.load()
         self._runs_key, self._runs = None, []
+        self.clip_grad_norm, self.skip_nonfinite, self.ema_decay = clip_grad_norm, bool(skip_nonfinite), ema_decay
+        self._check_extras()
+        self.flat_ema = None              # the EMA shadow of flat_p (allocated when the EMA is first enabled)
+        self._partial = None              # MNAS_GRADNORM_MAX_PARTS doubles: the norm launches' partial sums
+        self._stats = None                # one MnasGradStats block, as 4 int64 (the two floats share the first)
+        if ema_decay is not None:
+            self.reset_ema()
+
+    # ---- gradient clipping / non-finite skip / EMA ------------------------------------------------------------------------
+    def _check_extras(self):
+        """the three attributes, before anything is launched (the constructor and every step with one of them on call it)"""
+        c, d = self.clip_grad_norm, self.ema_decay
+        if c is not None and not float(c) > 0.0:
+            raise ValueError("clip_grad_norm must be > 0 (None: no clipping), got %r" % (c,))
+        if d is not None and not 0.0 <= float(d) < 1.0:
+            raise ValueError("ema_decay must be in [0, 1) (None: no EMA), got %r" % (d,))
+
+    def reset_ema(self):
+        """flat_ema = a copy of the current parameters"""
+        if self.flat_ema is None:
+            self.flat_ema = self.flat_p.detach().clone()
+        else:
+            self.flat_ema.copy_(self.flat_p)
+
+    def _stats_block(self):
+        if self._stats is None:
+            assert ctypes.sizeof(L.MnasGradStats) == 32
+            self._stats = torch.zeros(4, dtype=torch.int64, device=self.flat_p.device)
+        return self._stats
+
+    @property
+    def last_grad_norm(self):
+        """device tensor view (one fp32 element) of MnasGradStats.last_norm: no sync"""
+        return self._stats_block().view(torch.float32)[0:1]
+
+    def grad_stats(self):
+        """ONE device-to-host copy of the MnasGradStats block (waits for what was enqueued before it)."""
+        host = self._stats_block().cpu()
+        raw = L.MnasGradStats()
+        ctypes.memmove(ctypes.byref(raw), host.data_ptr(), ctypes.sizeof(raw))
+        return GradStats(float(raw.last_norm), float(raw.last_coef), int(raw.steps), int(raw.clipped_steps), int(raw.skipped_steps))
+
+    def _step_extras(self, g, runs):
+        """the step with clipping, the skip or the EMA on: norm launches into consecutive slots of one table, then the _ex launches"""
+        self._check_extras()
+        if self.ema_decay is not None and self.flat_ema is None:
+            self.reset_ema()
+        stream = L.cur_stream()
+        nparts = 0
+        if self.clip_grad_norm is not None or self.skip_nonfinite:
+            if self._partial is None:
+                self._partial = torch.zeros(L.GRADNORM_MAX_PARTS, dtype=torch.float64, device=self.flat_p.device)
+            got = ctypes.c_int(0)
+            for a, b in runs:
+                L.check(self._lib.mnas_grad_sqnorm(self.flat_g.data_ptr() + 4 * a, b - a, float(self.grad_scale),
+                                                   self._partial.data_ptr(), nparts, ctypes.byref(got), stream), "grad_sqnorm")
+                nparts += got.value
+        clip = self.clip_grad_norm
+        ex = L.MnasOptExtra(partial=L.ptr(self._partial) if nparts else None, nparts=nparts,
+                            max_norm=float(clip) if clip is not None and math.isfinite(float(clip)) else 0.0,
+                            skip_nonfinite=1 if self.skip_nonfinite else 0, ema=None,
+                            ema_decay=float(self.ema_decay) if self.ema_decay is not None else 0.0,
+                            stats=self._stats_block().data_ptr(), update_stats=0)
+        for k, (a, b) in enumerate(runs):
+            ex.ema = self.flat_ema.data_ptr() + 4 * a if self.ema_decay is not None else None
+            ex.update_stats = 1 if k == 0 else 0
+            self._launch(a, b, g, ex)
 
     def _trainable_runs(self):
         ps = self.param_groups[0]["params"]
@@ -162,20 +260,33 @@ class FlatAdam(torch.optim.Optimizer):
                 loss = closure()
         g = self.param_groups[0]
         self.step_count += 1
-        for a, b in self._trainable_runs():
+        runs = self._trainable_runs()
+        if self.clip_grad_norm is not None or self.skip_nonfinite or self.ema_decay is not None:
+            self._step_extras(g, runs)
+            return loss
+        for a, b in runs:
             self._launch(a, b, g)
         return loss
 
-    def _launch(self, a, b, g):
-        L.check(self._lib.mnas_adam_step(self.flat_p.data_ptr() + 4 * a, self.flat_g.data_ptr() + 4 * a,
-                                         self.flat_m.data_ptr() + 4 * a, self.flat_v.data_ptr() + 4 * a, b - a,
-                                         float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                         float(g["weight_decay"]), self.step_count, float(self.grad_scale),
-                                         L.cur_stream()), "adam_step")
+    def _launch(self, a, b, g, ex=None):
+        """the update of flat elements [a, b); ex: a MnasOptExtra -> the _ex entry point"""
+        args = (self.flat_p.data_ptr() + 4 * a, self.flat_g.data_ptr() + 4 * a,
+                self.flat_m.data_ptr() + 4 * a, self.flat_v.data_ptr() + 4 * a, b - a,
+                float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                float(g["weight_decay"]), self.step_count, float(self.grad_scale))
+        if ex is None:
+            L.check(self._lib.mnas_adam_step(*args, L.cur_stream()), "adam_step")
+        else:
+            L.check(self._lib.mnas_adam_step_ex(*args, ctypes.byref(ex), L.cur_stream()), "adam_step_ex")
 
     def state_dict(self):
         g = self.param_groups[0]
-        return {"state": {"step": self.step_count, "exp_avg": self.flat_m.clone(), "exp_avg_sq": self.flat_v.clone()},
+        state = {"step": self.step_count, "exp_avg": self.flat_m.clone(), "exp_avg_sq": self.flat_v.clone()}
+        if self.ema_decay is not None:
+            if self.flat_ema is None:
+                self.reset_ema()
+            state["ema"] = self.flat_ema.clone()
+        return {"state": state,
                 "param_groups": [{k: v for k, v in g.items() if k != "params"} | {"params": list(range(len(g["params"])))}]}
 
     def load_state_dict(self, sd):
@@ -185,6 +296,14 @@ class FlatAdam(torch.optim.Optimizer):
         self.step_count = int(st["step"])
         self.flat_m.copy_(st["exp_avg"].to(self.flat_m.device))
         self.flat_v.copy_(st["exp_avg_sq"].to(self.flat_v.device))
+        if "ema" in st:
+            if st["ema"].numel() != self.flat_p.numel():
+                raise ValueError("EMA state has %d elements, this model %d" % (st["ema"].numel(), self.flat_p.numel()))
+            if self.flat_ema is None:
+                self.flat_ema = torch.empty_like(self.flat_p)
+            self.flat_ema.copy_(st["ema"].to(self.flat_ema.device))
+        elif self.ema_decay is not None:
+            self.reset_ema()              # a checkpoint written with the EMA off: the shadow restarts from the current parameters
         for k, v in sd["param_groups"][0].items():
             if k != "params":
                 self.param_groups[0][k] = v
@@ -195,45 +314,55 @@ class FlatRMSprop(FlatAdam):
     buffers: one fused launch (``mnas_rmsprop_step``).  Same Optimizer contract as :class:`FlatAdam`."""
 
     def __init__(self, params, flat_p, flat_g, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, centered=False,
-                 grad_scale=1.0):
+                 grad_scale=1.0, **extras):
         if centered:
             raise NotImplementedError("centered RMSprop is not fused (the reference never asks for it: train.py:222-224)")
-        super().__init__(params, flat_p, flat_g, lr=lr, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+        super().__init__(params, flat_p, flat_g, lr=lr, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, **extras)
         self.param_groups[0].pop("betas", None)
         self.param_groups[0].update(alpha=alpha, momentum=momentum, centered=False)
         # flat_m = momentum buffer, flat_v = square average (same checkpoint layout as FlatAdam: exp_avg / exp_avg_sq)
 
-    def _launch(self, a, b, g):
-        L.check(self._lib.mnas_rmsprop_step(self.flat_p.data_ptr() + 4 * a, self.flat_g.data_ptr() + 4 * a,
-                                            self.flat_v.data_ptr() + 4 * a, self.flat_m.data_ptr() + 4 * a, b - a, float(g["lr"]),
-                                            float(g["alpha"]), float(g["eps"]), float(g["weight_decay"]), float(g["momentum"]),
-                                            float(self.grad_scale), L.cur_stream()), "rmsprop_step")
+    def _launch(self, a, b, g, ex=None):
+        args = (self.flat_p.data_ptr() + 4 * a, self.flat_g.data_ptr() + 4 * a,
+                self.flat_v.data_ptr() + 4 * a, self.flat_m.data_ptr() + 4 * a, b - a, float(g["lr"]),
+                float(g["alpha"]), float(g["eps"]), float(g["weight_decay"]), float(g["momentum"]), float(self.grad_scale))
+        if ex is None:
+            L.check(self._lib.mnas_rmsprop_step(*args, L.cur_stream()), "rmsprop_step")
+        else:
+            L.check(self._lib.mnas_rmsprop_step_ex(*args, ctypes.byref(ex), L.cur_stream()), "rmsprop_step_ex")
 
 
 class FlatSGD(FlatAdam):
     """``torch.optim.SGD`` (train.py:226-228: ``--optimizer sgd``; momentum 0 by default) over the flat buffers
     (``mnas_sgd_step``).  ``flat_m`` is the momentum buffer (initialised with the first gradient, as torch does)."""
 
-    def __init__(self, params, flat_p, flat_g, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0):
+    def __init__(self, params, flat_p, flat_g, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0,
+                 **extras):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        super().__init__(params, flat_p, flat_g, lr=lr, weight_decay=weight_decay, grad_scale=grad_scale)
+        super().__init__(params, flat_p, flat_g, lr=lr, weight_decay=weight_decay, grad_scale=grad_scale, **extras)
         for k in ("betas", "eps"):
             self.param_groups[0].pop(k, None)
         self.param_groups[0].update(momentum=momentum, dampening=dampening, nesterov=nesterov)
 
-    def _launch(self, a, b, g):
-        L.check(self._lib.mnas_sgd_step(self.flat_p.data_ptr() + 4 * a, self.flat_g.data_ptr() + 4 * a,
-                                        self.flat_m.data_ptr() + 4 * a, b - a, float(g["lr"]), float(g["momentum"]),
-                                        float(g["dampening"]), float(g["weight_decay"]), 1 if g["nesterov"] else 0, self.step_count,
-                                        float(self.grad_scale), L.cur_stream()), "sgd_step")
+    def _launch(self, a, b, g, ex=None):
+        args = (self.flat_p.data_ptr() + 4 * a, self.flat_g.data_ptr() + 4 * a,
+                self.flat_m.data_ptr() + 4 * a, b - a, float(g["lr"]), float(g["momentum"]),
+                float(g["dampening"]), float(g["weight_decay"]), 1 if g["nesterov"] else 0, self.step_count,
+                float(self.grad_scale))
+        if ex is None:
+            L.check(self._lib.mnas_sgd_step(*args, L.cur_stream()), "sgd_step")
+        else:
+            L.check(self._lib.mnas_sgd_step_ex(*args, ctypes.byref(ex), L.cur_stream()), "sgd_step_ex")
 
 
 class Trainer:
     """Owns flat parameter / gradient / Adam-moment buffers for ``model`` (a FineTuneModelPool or anything with
     a ``features`` engine module plus ordinary PyTorch head parameters) and runs train.py's step.
     ``trainer.optimizer`` is a :class:`FlatAdam` (a ``torch.optim.Optimizer``): hand it to the reference's schedulers and
-    checkpoint it with ``optimizer.state_dict()`` exactly as train.py does."""
+    checkpoint it with ``optimizer.state_dict()`` exactly as train.py does.  ``clip_grad_norm=``, ``skip_nonfinite=`` and
+    ``ema_decay=`` go to the optimizer (see :class:`FlatAdam`); in a distributed trainer the norm is taken after the all-reduce with
+    ``grad_scale = 1/world``, i.e. over the mean gradient, and is bit-identical on every rank."""
 
     def __init__(self, model: nn.Module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  criterion: Optional[nn.Module] = None, distributed: bool = False, process_group=None,
@@ -332,6 +461,55 @@ class Trainer:
 
     def load_state_dict(self, sd):
         self.optimizer.load_state_dict(sd["optimizer"])
+
+    # ---- gradient clipping / non-finite skip / weight EMA (FlatAdam; Trainer(clip_grad_norm=, skip_nonfinite=, ema_decay=)) ----
+    def grad_stats(self) -> GradStats:
+        """The optimizer's device counters -- last_norm, last_coef, steps, clipped_steps, skipped_steps -- in ONE host read, the
+        only one of this feature."""
+        return self.optimizer.grad_stats()
+
+    @property
+    def last_grad_norm(self) -> torch.Tensor:
+        """Device tensor view of the last step's gradient norm (no sync: for loggers that batch their reads)."""
+        return self.optimizer.last_grad_norm
+
+    @property
+    def flat_ema(self):
+        return self.optimizer.flat_ema
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the body on the EMA weights: the CONTENTS of flat_p and flat_ema are swapped on entry and swapped back on exit, also
+        when the body raises.  The parameters are views of flat_p and the engine packs its weights from them inside every forward,
+        so the model, the engine and ``state_dict()`` all see the averaged weights and nothing else needs to be told.  BatchNorm
+        running statistics are shared, not averaged (they are moving averages already).  Do not step inside the body."""
+        opt = self.optimizer
+        if opt.ema_decay is None or opt.flat_ema is None:
+            raise RuntimeError("ema_weights() needs the EMA on (Trainer(..., ema_decay=d) or optimizer.ema_decay = d)")
+        self._swap_ema()
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+
+    @torch.no_grad()
+    def _swap_ema(self):
+        p, e = self.flat_p, self.optimizer.flat_ema
+        t = p.clone()
+        p.copy_(e)
+        e.copy_(t)
+
+    def validate_ema(self, batches, meters=None, transform=None, max_batches=None, reduce=True):
+        """:meth:`validate` under the EMA weights: the pass runs inside :meth:`ema_weights`.  (A method of its own and not an
+        ``ema=`` keyword of ``validate``: that signature is pinned by tests/test_metrics_cpu.py.)"""
+        with self.ema_weights():
+            return self.validate(batches, meters, transform, max_batches, reduce)
+
+    def ema_state_dict(self):
+        """``model.state_dict()`` under the EMA weights, cloned: the checkpoint to evaluate from (it loads into the reference model
+        like any other state dict of this model)."""
+        with self.ema_weights():
+            return {k: v.detach().clone() for k, v in self.model.state_dict().items()}
 
     def _multilabel(self):
         """the criterion is this package's MultiClassBCELoss itself: the reference's multi-label branch (train.py:274-279).  A
@@ -494,7 +672,8 @@ class Trainer:
         targets, the BCE kernels, and a MultiLabelMeters (loss, HardDice(0.5), macro-F1; the default is a fresh one).  Any input shape works: the engine keeps one eval program per shape.  A model or criterion the native head
         does not cover runs as ``model(x)`` / ``criterion`` / ``meters.update``.  Distributed trainers broadcast rank 0's
         BatchNorm statistics first and sum the meters over the ranks at the end (``reduce=False``: neither).  The modules'
-        train/eval flags are restored on the way out, also when a batch raises.  Returns ``meters.read()``."""
+        train/eval flags are restored on the way out, also when a batch raises.  Returns ``meters.read()``.  The same pass under the
+        EMA weights: :meth:`validate_ema`."""
         from .metrics import DeviceMeters, MultiLabelMeters
         multilabel = self._multilabel()
         if meters is None:
