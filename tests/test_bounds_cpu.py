@@ -338,3 +338,408 @@ def test_dw_statistics_emulation(dw):
     st = torch.stack([v.sum((0, 1, 2)), (v * v).sum((0, 1, 2))]).unsqueeze(-1)
     M = dw.N * dw.H * dw.W
     assert check_stats_bound(st, ref, dw_elem_err(S, dw.k), M, "dw%d forward" % dw.k, family=None) <= 1.0
+
+
+# ---- squeeze-excite, stem gradients, glue, finalizes ----------------------------------------------------------------------------
+# The device's sigmoid is modelled as the fp64 value moved 0.8 of the way to an end of its bracket (end = -1, 0, +1) and rounded to
+# fp32; everything else is fp32 torch arithmetic in the kernels' operation order where the kernels fix one.
+def _sig(v, end=0):
+    iv = G.sigmoid_interval(v)
+    return (iv.val + 0.8 * end * (iv.hi - iv.val if end > 0 else iv.val - iv.lo)).float()
+
+
+def _ok(r):
+    print("ratio %.3f" % r)
+    assert r <= 1.0
+    return r
+
+
+def test_sigmoid_bracket_and_faults():
+    v = torch.cat([torch.arange(-30 * 64, 30 * 64 + 1).float() / 64, torch.tensor([0.0, -0.0])])
+    iv = G.sigmoid_interval(v)
+    got = 1.0 / (1.0 + torch.exp(-v))                      # fp32, a correctly rounded exponential
+    assert 0.05 < _ok(G.check_interval(got, iv, "sigmoid", None))
+    for end in (-1, 1):
+        _ok(G.check_interval(_sig(v, end), iv, "sigmoid end %d" % end, None))
+    _rejected(lambda: G.check_interval(bf16r(got), iv, "sigmoid rounded to bf16", None))
+    # du = acc * sg * (1 - sg)
+    acc = _u(v.shape, 1)
+    du_iv = G.imul(Interval.exact(acc), G.sig1m_interval(v), 1)
+    for end in (-1, 0, 1):
+        sg = _sig(v, end)
+        _ok(G.check_interval(acc * sg * (1.0 - sg), du_iv, "du end %d" % end, None))
+    _rejected(lambda: G.check_interval(acc * _sig(v), du_iv, "du without 1 - sg", None))
+    sgb = bf16r(_sig(v))
+    _rejected(lambda: G.check_interval(acc * sgb * (1.0 - sgb), du_iv, "du with a bf16 sigmoid", None))
+
+
+class _Se:
+    N, H, W, C = 2, 14, 14, 48
+
+    def __init__(self, amp=2.0):
+        sh = (self.N, self.H, self.W, self.C)
+        self.HW = self.H * self.W
+        self.z = bf16r(_u(sh, 31))
+        self.s, self.t = 1 + 0.3 * _u((self.C,), 32), 0.2 * _u((self.C,), 33)
+        self.u = amp * _u((self.N, self.C), 34)
+        self.gs = bf16r(_u(sh, 35))
+        self.dz = _u((self.N, self.C), 36)
+        self.gate = G.sigmoid_interval(self.u)
+        self.g4 = G.gate_nhwc(self.gate, sh)
+
+    def sg(self, end=0):
+        return _sig(self.u, end).view(self.N, 1, 1, self.C)
+
+
+@pytest.fixture(scope="module", params=[2.0, 12.0])
+def se(request):
+    return _Se(request.param)
+
+
+@pytest.mark.parametrize("virt", [True, False])
+def test_se_scale_emulation_and_faults(se, virt):
+    iv = G.gated_act_interval(se.z, se.s if virt else None, se.t if virt else None, se.g4, bf16=False)
+    a = emu_act(se.z, se.s, se.t, False) if virt else se.z
+    for end in (-1, 0, 1):
+        _ok(G.check_store_bound(bf16r(a * se.sg(end)), iv, "se_scale end %d" % end, None))
+    if virt:            # (a plain input is a bf16 value already: there is no rounding to do twice)
+        _rejected(lambda: G.check_store_bound(bf16r(bf16r(a) * se.sg()), iv, "se_scale: value rounded before the gate", None))
+        _rejected(lambda: G.check_store_bound(bf16r(emu_act(se.z, se.s, se.t, False, "shift_dropped") * se.sg()), iv, "se_scale: shift dropped", None))
+
+
+def test_gated_mfma_operand_emulation_and_faults(se):
+    Co = 16
+    w = bf16r(_u((Co, se.C, 1, 1), 37) * (3.0 / se.C) ** 0.5)
+    bias = 0.1 * _u((Co,), 38)
+    iv = G.gated_act_interval(se.z, se.s, se.t, se.g4, bf16=True)
+    assert iv.split_share() <= G.MAX_ACT_SPLIT
+    ref, slack, S = onload_fwd_terms(iv, w, bias)
+    M = se.N * se.HW
+
+    def run(a):
+        acc = emu_gemm(a.reshape(M, se.C), w.view(Co, se.C), bias).view(se.N, se.H, se.W, Co)
+        return check_onload_bound(bf16r(acc), ref, slack, S, se.C, "gated 1x1 forward", family=None)
+    a = emu_act(se.z, se.s, se.t, False)
+    _ok(run(bf16r(a * se.sg())))
+    _rejected(lambda: run(bf16r(bf16r(a) * se.sg())))                       # two roundings
+    _rejected(lambda: run(bf16r(emu_act(se.z, se.s, se.t, False, "shift_dropped") * se.sg())))
+
+
+def _emu_se_reduce(se, a, fault=None):
+    """k_se_bwd_reduce + k_se_bwd_finish: per split, lane pr walks pixels p0+pr, p0+pr+R, ... with one fma each; lanes, then splits,
+    added in order"""
+    G_, R, chunk, splits = G.se_geom(se.N, se.HW, se.C)
+    assert (R, chunk, splits) == (42, 126, 2)
+    g, a = se.gs.reshape(se.N, se.HW, se.C), a.reshape(se.N, se.HW, se.C)
+    parts = []
+    for sp in range(splits):
+        p0, p1 = sp * chunk, min(se.HW, (sp + 1) * chunk)
+        lanes = torch.zeros(R, se.N, se.C)
+        for pr in range(R):
+            acc = torch.zeros(se.N, se.C)
+            for p in range(p0 + pr, p1, R):
+                if fault == "drop_chunk_last" and p == chunk - 1:
+                    continue
+                acc = acc + g[:, p] * a[:, p]
+                if fault == "acc_bf16":
+                    acc = bf16r(acc)
+                if fault == "double_split_first" and p == chunk:
+                    acc = acc + g[:, p] * a[:, p]
+            lanes[pr] = acc
+        v = torch.zeros(se.N, se.C)
+        for pr in range(R):
+            v = v + lanes[pr]
+        parts.append(v)
+    v = torch.zeros(se.N, se.C)
+    for p_ in parts:
+        v = v + p_
+    sg = _sig(se.u)
+    return v * sg * (1.0 - sg)
+
+
+@pytest.mark.parametrize("virt", [True, False])
+def test_se_bwd_reduce_emulation_and_faults(se, virt):
+    G_, R, chunk, splits = G.se_geom(se.N, se.HW, se.C)
+    aiv = act_interval(se.z, se.s, se.t, bf16=False) if virt else Interval.exact(se.z)
+    ref, S, slack = G.se_reduce_terms(se.gs, aiv, se.HW)
+    iv = G.imul(G.sum_interval(ref, S, se.HW, R + splits, 1, slack), G.sig1m_interval(se.u), 1)
+    a = emu_act(se.z, se.s, se.t, False) if virt else se.z
+    _ok(G.check_interval(_emu_se_reduce(se, a), iv, "se_bwd_reduce", None))
+    for fault in ("drop_chunk_last", "double_split_first", "acc_bf16"):
+        _rejected(lambda: G.check_interval(_emu_se_reduce(se, a, fault), iv, "se_bwd_reduce " + fault, None))
+
+
+def test_se_bwd_apply_emulation_and_faults(se):
+    iv = G.se_apply_interval(se.gs, se.u, se.dz, se.HW)
+    dz4 = se.dz.view(se.N, 1, 1, se.C)
+    inv = torch.tensor(1.0) / torch.tensor(float(se.HW))
+    for end in (-1, 0, 1):
+        _ok(G.check_store_bound(bf16r(se.gs * se.sg(end) + dz4 * inv), iv, "se_bwd_apply end %d" % end, None))
+    _rejected(lambda: G.check_store_bound(bf16r(se.gs * se.sg() + dz4 / (se.HW + 1)), iv, "se_bwd_apply dz/(HW+1)", None))
+    _rejected(lambda: G.check_store_bound(bf16r(se.gs * se.sg()), iv, "se_bwd_apply without dz", None))
+
+
+def _emu_proj(wp, N, kseg, W, u, fault=None):
+    Co, Ci = W.shape
+    wp = wp.view(N, kseg, Co, Ci)
+    p = wp[:, 0].clone()
+    for j in range(1, kseg - (1 if fault == "slab_dropped" else 0)):
+        p = p + wp[:, j]
+    acc = torch.zeros(N, Ci)
+    for o in range(Co):
+        acc = acc + W[o] * p[:, o]
+    sg = _sig(u)
+    du = acc * sg * (1.0 - sg)
+    sgw = sg.clone()
+    if fault == "sigma_last_image":
+        sgw[N - 1] = 1.0
+    dW = torch.zeros(Co, Ci)
+    for n in range(N):
+        dW = dW + p[n] * sgw[n]
+    return du, dW
+
+
+@pytest.mark.parametrize("N,kseg,Co,Ci", [(3, 4, 16, 48), (1, 1, 24, 72), (2, 2, 40, 264)])
+def test_se_proj_finalize_emulation_and_faults(N, kseg, Co, Ci):
+    wp = _u((N * kseg, Co, Ci), 41) * 5
+    W, u = _u((Co, Ci), 42) * 0.3, 2 * _u((N, Ci), 43)
+    du_iv, ref, S, slack, M = G.se_proj_finalize_intervals(wp, N, kseg, W, u)
+    du, dW = _emu_proj(wp, N, kseg, W, u)
+    _ok(G.check_interval(du, du_iv, "se_proj du", None))
+    _ok(check_sum_bound(dW, ref, S, M, 0, 2, "se_proj dW", slack, family=None))
+    if kseg > 1:
+        du, dW = _emu_proj(wp, N, kseg, W, u, "slab_dropped")
+        _rejected(lambda: G.check_interval(du, du_iv, "se_proj du, slab dropped", None))
+        _rejected(lambda: check_sum_bound(dW, ref, S, M, 0, 2, "se_proj dW, slab dropped", slack, family=None))
+    _, dW = _emu_proj(wp, N, kseg, W, u, "sigma_last_image")
+    _rejected(lambda: check_sum_bound(dW, ref, S, M, 0, 2, "se_proj dW without the last image's sigma", slack, family=None))
+
+
+@pytest.mark.parametrize("N,E,R", [(5, 240, 10), (7, 100, 13), (2, 8, 1)])
+def test_se_fc_emulation_and_faults(N, E, R):
+    z = torch.rand(N, E, generator=torch.Generator().manual_seed(51))
+    W1, b1 = torch.randn(R, E, generator=torch.Generator().manual_seed(52)) / E ** 0.5, 0.1 * _u((R,), 53) + 0.3
+    W2, b2 = torch.randn(E, R, generator=torch.Generator().manual_seed(54)) / R ** 0.5, 0.1 * _u((E,), 55)
+    du = _u((N, E), 56)
+    hb_iv, u_iv, gate_iv = G.se_fc_fwd_intervals(z, W1, b1, W2, b2)
+    hb = torch.relu(z @ W1.t() + b1)
+    u = hb @ W2.t() + b2
+    _ok(G.check_interval(hb, hb_iv, "se_fc hb", None))
+    _ok(G.check_interval(u, u_iv, "se_fc u", None))
+    _ok(G.check_interval(_sig(u), gate_iv, "se_fc gate", None))
+    if R % 4:
+        _rejected(lambda: G.check_interval(hb[:, :R - 1] @ W2[:, :R - 1].t() + b2, u_iv, "se_fc u, last hidden unit dropped", None))
+    base = {k: 0.5 * _u(s_, 60 + i) for i, (k, s_) in enumerate((("dW1", (R, E)), ("db1", (R,)), ("dW2", (E, R)), ("db2", (E,))))}
+    for acc in (False, True):
+        dh_iv, dz_iv, terms = G.se_fc_bwd_terms(du, z, hb, W1, W2, base if acc else None)
+        dh = (du @ W2) * (hb > 0)
+        _ok(G.check_interval(dh, dh_iv, "se_fc dh", None))
+        _ok(G.check_interval(dh @ W1, dz_iv, "se_fc dz", None))
+        got = {"dW1": dh.t() @ z, "db1": dh.sum(0), "dW2": du.t() @ hb, "db2": du.sum(0)}
+        for k, (ref, S, slack, c) in terms.items():
+            _ok(check_sum_bound(got[k] + (base[k] if acc else 0), ref, S, N, 16, c, "se_fc " + k, slack, family=None))
+        ref, S, slack, c = terms["dW1"]
+        if acc:
+            _rejected(lambda: check_sum_bound(got["dW1"], ref, S, N, 16, c, "se_fc dW1, accumulate ignored", slack, family=None))
+        else:
+            _rejected(lambda: check_sum_bound(dh[:N - 1].t() @ z[:N - 1], ref, S, N, 16, c, "se_fc dW1, last image dropped", slack, family=None))
+
+
+# ---- stem -----------------------------------------------------------------------------------------------------------------------
+def _emu_stem_wgrad(x, dy, fault=None, rb=4):
+    """x (N,H,W,3), dy (N,Ho,Wo,Co) bf16 values -> (Co,3,3,3), fp32 accumulate"""
+    N, H, W, _ = x.shape
+    _, Ho, Wo, Co = dy.shape
+    if fault == "right_column":
+        x = x.clone()
+        x[:, :, W - 1] = 0
+    if fault == "last_band_row" and Ho % rb:
+        dy = dy.clone()
+        dy[:, Ho - 1] = 0
+    xp = pad_hw(x, 1)
+    if fault == "pad_replicated":
+        xp[:, 0], xp[:, -1] = xp[:, 1], xp[:, -2]
+        xp[:, :, 0], xp[:, :, -1] = xp[:, :, 1], xp[:, :, -2]
+    dw = torch.zeros(Co, 3, 3, 3)
+    d2 = dy.reshape(-1, Co)
+    for kh in range(3):
+        for kw in range(3):
+            sl = xp[:, kh:kh + 2 * (Ho - 1) + 1:2, kw:kw + 2 * (Wo - 1) + 1:2]
+            dw[:, :, kh, kw] = d2.t() @ sl.reshape(-1, 3)
+    return dw
+
+
+def test_stem_wgrad_emulation_and_faults():
+    N, H, W, Co = 2, 20, 32, 32
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    assert G.stem_wgrad_band_rows(W, Wo) == 4 and Ho % 4
+    x = bf16r(_u((N, H, W, 3), 71))
+    cf = _coefs(Co, 72)
+    g, y = bf16r(_u((N, Ho, Wo, Co), 73)), off_hinge(bf16r(_u((N, Ho, Wo, Co), 74)), cf[0], cf[1])
+    div = dy_interval(g, y, cf, bf16=True)
+    ref, S, slack = wgrad_terms(Interval.exact(x), div, 3, 2, 1)
+    dy = emu_dy(g, y, cf, True)
+    M, P = N * Ho * Wo, 4
+    _ok(check_sum_bound(_emu_stem_wgrad(x, dy), ref, S, M, P, 1, "stem wgrad", slack, family=None))
+    for fault in ("right_column", "pad_replicated", "last_band_row"):
+        _rejected(lambda: check_sum_bound(_emu_stem_wgrad(x, dy, fault), ref, S, M, P, 1, "stem wgrad " + fault, slack, family=None))
+
+
+def _emu_stem_dgrad(dy, w, H, W, aff=None, fault=None):
+    """dy (N,Ho,Wo,Co) bf16 values, w (Co,3,3,3) fp32 (rounded to bf16 here, as the kernel does) -> (N,3,H,W) fp32"""
+    N, Ho, Wo, Co = dy.shape
+    wb = w if fault == "weights_fp32" else bf16r(w)
+    if fault == "last_row" and H % 2:
+        dy = dy.clone()
+        dy[:, Ho - 1] = 0
+    gp = torch.zeros(N, max(H + 2, 2 * Ho + 1), max(W + 2, 2 * Wo + 1), 3)
+    for kh in range(3):
+        for kw in range(3):
+            gp[:, kh:kh + 2 * Ho:2, kw:kw + 2 * Wo:2] += dy @ wb[:, :, kh, kw]
+    dx = gp[:, 1:1 + H, 1:1 + W].permute(0, 3, 1, 2)
+    if aff is not None:
+        sc = aff[0].roll(1) if fault == "affine_plane" else aff[0]
+        dx = dx * sc.view(1, 3, 1, 1)
+    return dx.contiguous()
+
+
+@pytest.mark.parametrize("Co", [8, 128])
+def test_stem_dgrad_emulation_and_faults(Co):
+    N, H, W = 2, 9, 11
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    cf = _coefs(Co, 75)
+    g, y = bf16r(_u((N, Ho, Wo, Co), 76)), off_hinge(bf16r(_u((N, Ho, Wo, Co), 77)), cf[0], cf[1])
+    w = _u((Co, 3, 3, 3), 78) * (1.0 / 27) ** 0.5
+    assert not torch.equal(w, bf16r(w))
+    aff = torch.tensor([[2.0, 0.5, 1.25], [0.1, 0.2, 0.3]])
+    div = dy_interval(g, y, cf, bf16=True)
+    dy = emu_dy(g, y, cf, True)
+    for a_ in (None, aff):
+        ref, bound = G.stem_dgrad_terms(div, bf16r(w), H, W, a_)
+        _ok(G._assert_bound(_emu_stem_dgrad(dy, w, H, W, a_), ref, bound, "stem dgrad", None))
+        for fault in ("last_row", "weights_fp32") + (("affine_plane",) if a_ is not None else ()):
+            _rejected(lambda: G._assert_bound(_emu_stem_dgrad(dy, w, H, W, a_, fault), ref, bound, "stem dgrad " + fault, None))
+
+
+# ---- glue -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N,HW,C_", [(2, 49, 320), (1, 1, 8), (3, 9, 8)])
+@pytest.mark.parametrize("virt", [True, False])
+def test_pool_act_emulation_and_faults(N, HW, C_, virt):
+    x = bf16r(_u((N, HW, C_), 81))
+    s, t = 1 + 0.3 * _u((C_,), 82), 0.2 * _u((C_,), 83)
+    aiv = act_interval(x, s, t, bf16=False) if virt else Interval.exact(x)
+    ref, bound = G.pool_act_terms(aiv, HW)
+    a = emu_act(x, s, t, False) if virt else x
+    R = 256 // (C_ // 8)
+    acc = torch.zeros(N, C_)
+    for p in range(HW):
+        acc = acc + a[:, p]
+    _ok(G._assert_bound(acc / HW, ref, bound, "pool_act", None))
+    padded = -(-HW // (8 * R)) * 8 * R
+    _rejected(lambda: G._assert_bound(acc / padded, ref, bound, "pool_act / padded count", None))
+    if HW > 1:
+        _rejected(lambda: G._assert_bound((acc - a[:, HW - 1]) / HW, ref, bound, "pool_act, last pixel dropped", None))
+
+
+def test_add_act_emulation_and_faults():
+    rows, C_ = 98, 320
+    a, b = bf16r(_u((rows, C_), 84)), bf16r(_u((rows, C_), 85))
+    sa, ta, sb, tb = 1 + 0.3 * _u((C_,), 86), 0.2 * _u((C_,), 87), 1 + 0.3 * _u((C_,), 88), 0.2 * _u((C_,), 89)
+    iv = G.add_act_interval(act_interval(a, sa, ta, bf16=False), act_interval(b, sb, tb, bf16=False))
+    v = emu_act(a, sa, ta, False) + emu_act(b, sb, tb, False)
+    _ok(G.check_interval(v, iv, "add_act fp32", None))
+    _ok(G.check_store_bound(bf16r(v), iv, "add_act bf16", None))
+    _rejected(lambda: G.check_interval(bf16r(emu_act(a, sa, ta, False)) + emu_act(b, sb, tb, False), iv, "add_act: a rounded to bf16", None))
+    _rejected(lambda: G.check_store_bound(bf16r(bf16r(emu_act(a, sa, ta, False)) + emu_act(b, sb, tb, False)), iv, "add_act bf16: two roundings", None))
+
+
+# ---- finalizes ------------------------------------------------------------------------------------------------------------------
+def _emu_bn_fwd(partial, count, gamma, beta, rm, rv, mom=0.1, eps=1e-5, fault=None):
+    """k_bn_fwd_finalize: fp32 partial sums per accumulator (exact here: T = 1), then double, one fp32 rounding per output"""
+    dt = torch.float32 if fault == "fp32" else torch.float64
+    mom, eps = torch.tensor(mom, dtype=torch.float32).to(dt), torch.tensor(eps, dtype=torch.float32).to(dt)
+    s1, s2 = partial[0].double().sum(-1).to(dt), partial[1].double().sum(-1).to(dt)
+    cnt = torch.tensor(count, dtype=dt)
+    mean = s1 / cnt
+    var = s2 / cnt - mean * mean
+    if fault != "no_clamp":
+        var = var.clamp_min(0)
+    invstd = 1 / torch.sqrt(var + eps)
+    g, b = gamma.to(dt), beta.to(dt)
+    unb = var if (count <= 1 or fault == "biased") else var * cnt / (cnt - 1)
+    return {"s": g * invstd, "t": b - mean * g * invstd, "mean": mean, "invstd": invstd,
+            "running_mean": (1 - mom) * rm.to(dt) + mom * mean, "running_var": (1 - mom) * rv.to(dt) + mom * unb}
+
+
+@pytest.mark.parametrize("C_,nparts,count", [(16, 7, 100.0), (8, 256, 50176.0), (8, 1024, 802816.0), (8, 1, 1.0), (8, 1, 64.0)])
+def test_bn_fwd_finalize_emulation_and_faults(C_, nparts, count):
+    Ct = C_ + 3
+    partial = G.bn_fwd_partials(_u((2, Ct, nparts), 91), count)
+    gamma, beta = 1 + 0.2 * _u((Ct,), 92), 0.1 * _u((Ct,), 93)
+    rm, rv = 0.1 * _u((Ct,), 94), 1 + 0.3 * _u((Ct,), 95).abs()
+    ivs = G.bn_fwd_finalize_intervals(partial, count, gamma, beta, rm, rv, 0.1, 1e-5)
+    got = _emu_bn_fwd(partial, count, gamma, beta, rm, rv)
+    for k, iv in ivs.items():
+        _ok(G.check_interval(got[k].float(), iv, "bn_fwd_finalize " + k, None))
+    assert float(ivs["invstd"].half[-1]) < 1e-6 * float(ivs["invstd"].mid[-1])          # the clamped channel: both ends at var = 0
+    bad = _emu_bn_fwd(partial, count, gamma, beta, rm, rv, fault="fp32")
+    if count > 1:
+        ch = Ct - 3                                                                       # |mean|/std = 30
+        one = Interval(ivs["invstd"].lo[ch], ivs["invstd"].hi[ch])
+        _rejected(lambda: G.check_interval(bad["invstd"][ch].float(), one, "bn_fwd_finalize in fp32 at |mean|/std = 30", None))
+        bad = _emu_bn_fwd(partial, count, gamma, beta, rm, rv, fault="biased")
+        _rejected(lambda: G.check_interval(bad["running_var"].float(), ivs["running_var"], "biased variance into running_var", None))
+        bad = _emu_bn_fwd(partial, count, gamma, beta, rm, rv, fault="no_clamp")
+        _rejected(lambda: G.check_interval(bad["invstd"].float(), ivs["invstd"], "no clamp on a negative var", None))
+
+
+@pytest.mark.parametrize("nparts", [7, 257, 1025])
+def test_bn_bwd_finalize_emulation_and_faults(nparts):
+    C_, count = 24, 12345.0
+    partial = _u((2, C_, nparts), 96)
+    bn = _coefs(C_, 97)
+    g0, b0, c0 = _u((C_,), 98), _u((C_,), 99), _u((C_,), 100)
+
+    def emu(fault=None):
+        s1, s2 = partial[0].double().sum(-1), partial[1].double().sum(-1)
+        s, mean, inv = bn[0].double(), bn[5].double(), bn[6].double()
+        cnt = count - 1 if fault == "count" else count
+        c3 = s * (mean * inv * s2 / cnt - s1 / cnt)
+        return {"c1": s.float(), "c2": (-s * inv * s2 / cnt).float(), "c3": (-c3 if fault == "sign" else c3).float(),
+                "dgamma": g0 + s2.float(), "dbeta": b0 + s1.float(), "dbias": c0 + (s * s1).float()}
+    ivs = G.bn_bwd_finalize_intervals(partial, count, bn, g0, b0)
+    ivs["dbias"] = G.bn_bwd_finalize_intervals(partial, count, bn, g0, b0, frozen=True, dbias0=c0)["dbias"]
+    got = emu()
+    for k, iv in ivs.items():
+        _ok(G.check_interval(got[k], iv, "bn_bwd_finalize " + k, None))
+    _rejected(lambda: G.check_interval(emu("sign")["c3"], ivs["c3"], "bn_bwd_finalize: sign of row 4", None))
+    if nparts <= 1024:          # (at T = 2 the bracket of the fp32 partial sums is wider than 1/count)
+        _rejected(lambda: G.check_interval(emu("count")["c2"], ivs["c2"], "bn_bwd_finalize: count - 1", None))
+    _rejected(lambda: G.check_interval(got["dgamma"] - g0, ivs["dgamma"], "bn_bwd_finalize: accumulate ignored", None))
+
+
+@pytest.mark.parametrize("nsplit,acc", [(5, 0), (300, 1), (129, 1)])
+def test_wgrad_finalize_emulation_and_faults(nsplit, acc):
+    part, init = _u((nsplit, 24, 16), 101), _u((24, 16), 102)
+    ref = part.double().sum(0) + (init.double() if acc else 0)
+    S = part.double().abs().sum(0) + (init.double().abs() if acc else 0)
+    got = torch.zeros(24, 16)
+    for p in range(nsplit):
+        got = got + part[p]
+    _ok(check_sum_bound(got + (init if acc else 0), ref, S, nsplit, 0, 1, "wgrad finalize", None, family=None))
+    _rejected(lambda: check_sum_bound(got - part[nsplit - 1] + (init if acc else 0), ref, S, nsplit, 0, 1, "wgrad finalize, last split dropped", None, family=None))
+    if acc:
+        _rejected(lambda: check_sum_bound(got, ref, S, nsplit, 0, 1, "wgrad finalize, accumulate ignored", None, family=None))
+
+
+# ---- the condition of the gated MFMA operand, known to hold before anything runs on a GPU ------------------------------------------
+@pytest.mark.parametrize("shape", [(2, 16, 9, 48, 16), (9, 28, 28, 240, 40)])
+def test_gated_operand_straddle_share_of_the_gpu_tests(shape):
+    """the inputs of tests/test_gpu_se.py::test_gated_project_forward where it asserts check_onload_bound over
+    gated_act_interval(..., bf16=True): the share of bf16 elements whose bracket straddles a rounding boundary is <= MAX_ACT_SPLIT"""
+    from cases import O
+    y, s, t, u, w, bias = G.gated_fwd_inputs(shape, O)
+    yn = y.permute(0, 2, 3, 1)
+    iv = G.gated_act_interval(yn, s, t, G.gate_nhwc(G.sigmoid_interval(u), yn.shape), bf16=True)
+    print("gated operand %s: straddle share %.3g" % (shape, iv.split_share()))
+    assert iv.split_share() <= G.MAX_ACT_SPLIT

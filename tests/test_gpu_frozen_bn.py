@@ -136,6 +136,27 @@ def test_bn_bwd_finalize_frozen(Cn, nparts):
     assert lib.mnas_bn_bwd_finalize_frozen(None, nparts, Cn, bnbuf.data_ptr(), None, None, None, 1, L.cur_stream()) == L.EINVAL
 
 
+@pytest.mark.parametrize("nparts", [3, 1024, 1025])
+def test_bn_bwd_finalize_frozen_brackets(nparts):
+    """dgamma, dbeta and dbias inside the brackets of gpu_util.bn_bwd_finalize_intervals (fp64 on the fp32 table as given).  Up to
+    1024 partials every fp32 accumulator of bn_partial_sums holds one term and the bracket is _check_sums' one rounding; 1025 is
+    the first table with two terms in an accumulator, which _check_sums' exact-sum model does not describe."""
+    from gpu_util import bn_bwd_finalize_intervals, check_interval
+    lib = L.load()
+    Cn = 24
+    for acc in (0, 1):
+        partial, bnbuf, old, _ = _post_inputs(Cn, nparts, 500 + acc)
+        outs = [o.clone() if acc else torch.full((Cn,), float("nan"), device="cuda") for o in old]
+        L.check(lib.mnas_bn_bwd_finalize_frozen(partial.data_ptr(), nparts, Cn, bnbuf.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(),
+                                                outs[2].data_ptr(), acc, L.cur_stream()), "finalize_frozen")
+        base = [o.cpu() if acc else None for o in old]
+        ivs = bn_bwd_finalize_intervals(partial.cpu(), 1.0, bnbuf.cpu(), base[0], base[1], frozen=True, dbias0=base[2])
+        for name, got in zip(("dgamma", "dbeta", "dbias"), outs):
+            r = check_interval(got.cpu(), ivs[name], "bn_bwd_finalize_frozen nparts %d accumulate %d %s" % (nparts, acc, name),
+                               "BatchNorm backward finalize")
+            print("bn_bwd_finalize_frozen nparts %d accumulate %d %s error / bound %.3f" % (nparts, acc, name, r))
+
+
 def _wg_task(kind, seed):
     """(MnasPostWgrad fields, partial, grad): a single-level weight-gradient reduction, dense 1x1 or depthwise 3x3"""
     nsplit, Co, Ci, taps, dw = (5, 8, 16, 1, 0) if kind == "pw" else (7, 24, 1, 9, 1)

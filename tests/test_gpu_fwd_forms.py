@@ -808,8 +808,10 @@ def _replay_wgrad(ints, flags, gen):
     x = bf16r(_rand(gen, N, Hi, Wi, Ci)).to(torch.bfloat16)
     sc, sh = 1 + 0.3 * _rand(gen, Ci), 0.2 * _rand(gen, Ci)
     g = bf16r(_rand(gen, N, Ho, Wo, Co)).to(torch.bfloat16)
-    y = bf16r(_rand(gen, N, Ho, Wo, Co)).to(torch.bfloat16) if flags["dy.y"] else None
+    y = bf16r(_rand(gen, N, Ho, Wo, Co)) if flags["dy.y"] else None
     b = _bn(gen, Co) if flags["dy.y"] else None
+    if y is not None:
+        y = _off_hinge(y, b[0], b[1]).to(torch.bfloat16)             # (dy's mask input: the per-element bound below needs the device's mask bits)
     part, pchk = guarded((nsp, Co, k * k * Ci), torch.float32)
     a = L.MnasConvWgrad()
     a.N, a.Hi, a.Wi, a.Ci, a.Ho, a.Wo, a.Co = N, Hi, Wi, Ci, Ho, Wo, Co
@@ -824,14 +826,24 @@ def _replay_wgrad(ints, flags, gen):
     L.check(lib.mnas_wgrad_finalize(L.ptr(part), nsp, Co, Ci, k * k, L.ptr(grad), 0, L.cur_stream()))
     gchk(what + " dW")
     ref = torch.zeros((Co, Ci, k, k), dtype=torch.float64, device="cuda")
+    # check_sum_bound (c = 1) over the operands' bf16 intervals, chunk by chunk: ref over the interval mids, S over the largest
+    # magnitudes, slack = S - sum |mid||mid| (gpu_util.wgrad_terms, accumulated over the image chunks)
+    r64, S, Sm = torch.zeros_like(ref), torch.zeros_like(ref), torch.zeros_like(ref)
     for n0, n1 in _img_chunks(N, max(Hi * Wi * Ci, Ho * Wo * Co)):
         xs = x[n0:n1].float()
         act = bf16r(torch.relu(sc * xs + sh)) if flags["virt"] else xs
         dy = bf16r(ref_dy(g[n0:n1], y[n0:n1], b, device="cuda").float()) if flags["dy.y"] else g[n0:n1].float()
         ref += ref_dense_wgrad(act, dy, k, stride, pad, device="cuda")
+        aiv = act_interval(xs, sc, sh, True, "cuda") if flags["virt"] else Interval.exact(xs, "cuda")
+        div = dy_interval(g[n0:n1].float(), y[n0:n1].float(), b, True, "cuda") if flags["dy.y"] else Interval.exact(g[n0:n1].float(), "cuda")
+        r64 += ref_dense_wgrad(aiv.mid, div.mid, k, stride, pad, device="cuda")
+        S += ref_dense_wgrad(aiv.amax, div.amax, k, stride, pad, device="cuda")
+        Sm += ref_dense_wgrad(aiv.mid.abs(), div.mid.abs(), k, stride, pad, device="cuda")
+        del aiv, div
     e = relerr(grad.double(), ref)
     assert e < TOL_F32, (what, "dW", e)
-    return "nsplit %d x %d slabs  err %.1e" % (nsp, slabs, e)
+    worst = check_sum_bound(grad, r64, S, N * Ho * Wo, nsp, 1, what + " dW", (S - Sm).clamp_min(0), "weight gradient (replayed)")
+    return "nsplit %d x %d slabs  err %.1e  bound x%.3f" % (nsp, slabs, e, worst)
 
 
 def _replay_dw(ints, flags, gen):

@@ -20,6 +20,9 @@ from gpu_util import (Interval, L, act_in, act_interval, bf16r, check_dw_bound, 
                       check_stats_bound, check_sum_bound, conv_gemm, dw_dgrad_terms, dw_elem_err, dw_fwd_terms, dw_wgrad_terms,
                       dy_interval, dy_ref, from_nhwc, grad_in, guarded, nhwc, off_hinge, onload_dgrad_terms, onload_elem_err,
                       onload_fwd_terms, pack, rand_bn_coefs, ref_dense_wgrad, relerr, wgrad_terms)
+from gpu_util import (U32, _assert_bound, add_act_interval, bn_bwd_finalize_intervals, bn_fwd_finalize_intervals, bn_fwd_partials,
+                      check_interval, check_store_bound, pool_act_terms, ref_dense_dgrad, stem_dgrad_terms, stem_wgrad_band_rows,
+                      sum_bound)
 
 pytestmark = pytest.mark.gpu
 TOL_BF16 = 6e-3
@@ -45,41 +48,58 @@ def _xoff(shape, seed, s, t):
 
 # ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("C_,nparts,count", [(16, 7, 100.0), (48, 64, 3211264.0), (1152, 33, 12544.0),
-                                             (24, 1031, 802816.0), (48, 2048, 3211264.0), (1152, 300, 12544.0)])   # block-per-channel path
+                                             (24, 1031, 802816.0), (48, 2048, 3211264.0), (1152, 300, 12544.0),    # block-per-channel path
+                                             # one partial; both sides of the 64 / 256 threads-per-channel switch; the first
+                                             # table with two terms per fp32 accumulator; count = 1 (running_var takes var itself)
+                                             (8, 1, 64.0), (24, 256, 50176.0), (24, 257, 50176.0), (16, 1025, 802816.0), (8, 1, 1.0)])
 def test_bn_fwd_finalize(C_, nparts, count):
+    """C_ channels of the distribution this test always had (mean ~ 0.3 u, var >= 0.5) under the max-normalised 1e-5, plus three
+    appended channels (gpu_util.bn_fwd_partials: |mean|/std = 30 and 300, a constant channel whose var takes the clamp); the table
+    is built in fp64 and rounded once to fp32, and ALL seven outputs of every channel are held to the brackets of
+    gpu_util.bn_fwd_finalize_intervals (fp64 on the fp32 table exactly as given to the kernel)."""
     lib = L.load()
-    u = O.det_uniform((2, C_, nparts), 3)
-    per = count / nparts
-    partial = torch.empty(2, C_, nparts)          # channel-major partial layout
-    mean_p = 0.3 * u[0]
-    partial[0] = per * mean_p
-    partial[1] = per * (mean_p ** 2 + 0.5 + 0.4 * u[1].abs())
-    gamma, beta = 1 + 0.2 * O.det_uniform((C_,), 4), 0.1 * O.det_uniform((C_,), 5)
-    rm, rv = 0.1 * O.det_uniform((C_,), 6), 1 + 0.3 * O.det_uniform((C_,), 7).abs()
+    Ct = C_ + 3
+    partial = bn_fwd_partials(O.det_uniform((2, Ct, nparts), 3), count)          # channel-major partial layout
+    gamma, beta = 1 + 0.2 * O.det_uniform((Ct,), 4), 0.1 * O.det_uniform((Ct,), 5)
+    rm, rv = 0.1 * O.det_uniform((Ct,), 6), 1 + 0.3 * O.det_uniform((Ct,), 7).abs()
     d = lambda t: t.clone().cuda()
     dp, dg, db, drm, drv = d(partial), d(gamma), d(beta), d(rm), d(rv)
     nbt = torch.zeros((), dtype=torch.int64, device="cuda")
-    bn = torch.zeros(8, C_, device="cuda")
-    L.check(lib.mnas_bn_fwd_finalize(dp.data_ptr(), nparts, C_, count, dg.data_ptr(), db.data_ptr(), drm.data_ptr(),
+    bn = torch.zeros(8, Ct, device="cuda")
+    L.check(lib.mnas_bn_fwd_finalize(dp.data_ptr(), nparts, Ct, count, dg.data_ptr(), db.data_ptr(), drm.data_ptr(),
                                      drv.data_ptr(), nbt.data_ptr(), 0.1, 1e-5, 1, bn.data_ptr(), L.cur_stream()))
     S1, S2 = partial[0].double().sum(-1), partial[1].double().sum(-1)
     mean = S1 / count
-    var = S2 / count - mean * mean
+    var = (S2 / count - mean * mean).clamp_min(0)
     invstd = 1 / torch.sqrt(var + 1e-5)
     s = gamma.double() * invstd
     t = beta.double() - mean * s
     bn = bn.cpu().double()
-    assert relerr(bn[0], s) < 1e-5 and relerr(bn[1], t) < 1e-5
-    assert relerr(bn[5], mean) < 1e-5 and relerr(bn[6], invstd) < 1e-5
-    assert relerr(drm.cpu(), 0.9 * rm.double() + 0.1 * mean) < 1e-5
-    assert relerr(drv.cpu(), 0.9 * rv.double() + 0.1 * var * count / (count - 1)) < 1e-5
+    o = slice(0, C_)                                # the ordinary channels, as before
+    assert relerr(bn[0][o], s[o]) < 1e-5 and relerr(bn[1][o], t[o]) < 1e-5
+    assert relerr(bn[5][o], mean[o]) < 1e-5 and relerr(bn[6][o], invstd[o]) < 1e-5
+    assert relerr(drm.cpu()[o], (0.9 * rm.double() + 0.1 * mean)[o]) < 1e-5
+    unb = count / (count - 1) if count > 1 else 1.0
+    assert relerr(drv.cpu()[o], (0.9 * rv.double() + 0.1 * var * unb)[o]) < 1e-5
     assert int(nbt) == 1
+    ivs = bn_fwd_finalize_intervals(partial, count, gamma, beta, rm, rv, 0.1, 1e-5)
+    what = "bn_fwd_finalize C %d nparts %d count %g " % (Ct, nparts, count)
+    got = {"s": bn[0], "t": bn[1], "mean": bn[5], "invstd": bn[6], "running_mean": drm.cpu(), "running_var": drv.cpu()}
+    for k, iv in ivs.items():
+        r = check_interval(got[k], iv, what + k, "BatchNorm forward finalize")
+        print(what + k, "error / bound %.3f" % r)
+    assert float(ivs["invstd"].half[-1]) < 1e-6 * float(ivs["invstd"].mid[-1])     # the constant channel: var < 0, both ends clamped to 0
     # eval mode: coefficients from the running stats, nothing updated
-    bn2 = torch.zeros(8, C_, device="cuda")
-    L.check(lib.mnas_bn_fwd_finalize(0, 0, C_, count, dg.data_ptr(), db.data_ptr(), drm.data_ptr(), drv.data_ptr(),
+    bn2 = torch.zeros(8, Ct, device="cuda")
+    L.check(lib.mnas_bn_fwd_finalize(0, 0, Ct, count, dg.data_ptr(), db.data_ptr(), drm.data_ptr(), drv.data_ptr(),
                                      0, 0.1, 1e-5, 0, bn2.data_ptr(), L.cur_stream()))
     s_e = gamma / torch.sqrt(drv.cpu() + 1e-5)
-    assert relerr(bn2[0].cpu(), s_e) < 1e-5 and relerr(bn2[1].cpu(), beta - drm.cpu() * s_e) < 1e-5
+    assert relerr(bn2[0].cpu()[o], s_e[o]) < 1e-5 and relerr(bn2[1].cpu()[o], (beta - drm.cpu() * s_e)[o]) < 1e-5
+    # every channel, the appended ones included: fp32 arithmetic, four roundings (sum, sqrt, division; product; product, difference)
+    s64 = gamma.double() / torch.sqrt(drv.cpu().double() + float(torch.tensor(1e-5)))
+    t64 = beta.double() - drm.cpu().double() * s64
+    _assert_bound(bn2[0].cpu(), s64, 4 * U32 * s64.abs(), what + "eval s", "BatchNorm forward finalize")
+    _assert_bound(bn2[1].cpu(), t64, 6 * U32 * (beta.double().abs() + (drm.cpu().double() * s64).abs()), what + "eval t", "BatchNorm forward finalize")
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -505,14 +525,22 @@ def test_dw_stride2(shape):
 # (N, H, W[, Co]): W % 4 == 0 with 32 couts runs the band kernels (csrc/mnas_stem.hip; weight gradient also needs Wo % 8 == 0),
 # everything else the im2col staging of k_igemm / k_wgrad; partial last bands, odd heights, more bands than workgroups
 @pytest.mark.parametrize("shape", [(2, 12, 12), (3, 33, 21), (1, 64, 64), (3, 40, 48), (2, 37, 32), (11, 18, 16), (2, 224, 224),
-                                   (2, 24, 24, 16), (1, 34, 80)])
+                                   (2, 24, 24, 16), (1, 34, 80),
+                                   # the smallest band shape (one output row); odd H with a partial last band for the forward's
+                                   # 8-row and the weight gradient's 4-row bands
+                                   (1, 2, 16), (3, 33, 48)])
 def test_stem(shape):
+    """+ check_sum_bound (c = 1) on the weight gradient after mnas_wgrad_finalize -- the image operand is exact (the kernels round
+    it to bf16, the reference takes bf16r(x)), dy the bf16 dy-on-load interval with y off the hinge -- and stem_dgrad_terms on the
+    input gradient, whose weights are handed over in fp32, NOT bf16-representable (the kernel's own rounding is under test)."""
     lib = L.load()
     N, H, W = shape[:3]
     Co = shape[3] if len(shape) > 3 else 32
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     x = O.det_uniform((N, 3, H, W), 1)
-    w = bf16r(O.det_param("t.conv.weight", (Co, 3, 3, 3), 2))
+    w_raw = O.det_param("t.conv.weight", (Co, 3, 3, 3), 2)
+    w = bf16r(w_raw)
+    assert not torch.equal(w, w_raw)
     bias = 0.1 * O.det_uniform((Co,), 3)
     ref = F.conv2d(bf16r(x), w, bias, stride=2, padding=1)
     xd = x.cuda()
@@ -532,8 +560,8 @@ def test_stem(shape):
     assert relerr(st[0], ref.double().sum((0, 2, 3))) < TOL_F32
     assert relerr(st[1], (ref.double() ** 2).sum((0, 2, 3))) < TOL_F32
     # wgrad
-    g, y = _x((N, Co, Ho, Wo), 6), _x((N, Co, Ho, Wo), 7)
     b = rand_bn_coefs(Co, 9, O)
+    g, y = _x((N, Co, Ho, Wo), 6), _xoff((N, Co, Ho, Wo), 7, b[0], b[1])
     dy = dy_ref(g, y, b)
     ref_dw = torch.nn.grad.conv2d_weight(bf16r(x), (Co, 3, 3, 3), dy, stride=2, padding=1)
     gd, yd, bd = nhwc(g), nhwc(y), b.cuda()
@@ -547,9 +575,14 @@ def test_stem(shape):
     L.check(lib.mnas_wgrad_finalize(partial.data_ptr(), nparts, Co, 27, 1, grad.data_ptr(), 0, L.cur_stream()))
     grad_chk("stem dW")
     assert relerr(grad.cpu(), ref_dw) < TOL_F32
+    div = dy_interval(_nh(g), _nh(y), b, True, DEV)
+    r64, S, slack = wgrad_terms(Interval.exact(_nh(bf16r(x)), DEV), div, 3, 2, 1, DEV)
+    r = check_sum_bound(grad, r64, S, N * Ho * Wo, nparts, 1, "stem_wgrad %s" % (shape,), slack, "stem weight gradient")
+    print("stem_wgrad %s error / bound %.3f" % (shape, r))
+    del r64, S, slack
     # input gradient (dL/d image, fp32 NCHW): bf16 dy and weights, fp32 accumulate; with the fused input normalisation's scale
     ref_dx = torch.nn.grad.conv2d_input((N, 3, H, W), w, bf16r(dy), stride=2, padding=1)
-    w32 = w.cuda().contiguous()
+    w32 = w_raw.cuda().contiguous()                # fp32 master weights: the kernel rounds them to bf16 itself
     for aff in (None, torch.tensor([[2.0, 0.5, 1.25], [0.1, 0.2, 0.3]])):
         dx, dx_chk = guarded((N, 3, H, W), torch.float32)
         affd = aff.cuda().contiguous() if aff is not None else None
@@ -559,6 +592,9 @@ def test_stem(shape):
         dx_chk("stem_dgrad dx")
         want = ref_dx if aff is None else ref_dx * aff[0].view(1, 3, 1, 1)
         assert relerr(dx.cpu(), want) < TOL_F32
+        r64, bound = stem_dgrad_terms(div, w, H, W, aff, DEV)
+        r = _assert_bound(dx, r64, bound, "stem_dgrad %s affine %d" % (shape, aff is not None), "stem input gradient")
+        print("stem_dgrad %s error / bound %.3f" % (shape, r))
     assert lib.mnas_stem_dgrad(C.byref(gi), w32.data_ptr(), N, H, W, Ho + 1, Wo, Co, None, dx.data_ptr(), L.cur_stream()) == L.EINVAL
 
 
@@ -584,6 +620,11 @@ def test_bn_bwd(C_, rows):
     L.check(lib.mnas_bn_bwd_finalize(partial.data_ptr(), nparts, C_, float(rows), bd.data_ptr(), dgamma.data_ptr(),
                                      dbeta.data_ptr(), 1, L.cur_stream()))
     assert relerr(dgamma.cpu() - 2.0, S2) < 1e-4 and relerr(dbeta.cpu() - 3.0, S1) < 1e-4
+    # the finalize alone: fp64 on the fp32 table the reduce wrote, brackets of gpu_util.bn_bwd_finalize_intervals
+    ivs = bn_bwd_finalize_intervals(partial.cpu(), float(rows), b, torch.full((C_,), 2.0), torch.full((C_,), 3.0))
+    fin = {"c1": bd[2], "c2": bd[3], "c3": bd[4], "dgamma": dgamma, "dbeta": dbeta}
+    for k, iv in ivs.items():
+        check_interval(fin[k].cpu(), iv, "bn_bwd_finalize C %d rows %d %s" % (C_, rows, k), "BatchNorm backward finalize")
     out = bd.cpu().double()
     sd = s.double()
     assert relerr(out[2], sd) < 1e-6
@@ -611,6 +652,10 @@ def test_add_act_and_layouts(C_, rows, HW):
     L.check(lib.mnas_add_act(C.byref(A), C.byref(B), rows, C_, out.data_ptr(), onchw.data_ptr(), HW, L.cur_stream()))
     assert relerr(out.float().cpu(), ref) < TOL_BF16
     assert relerr(onchw.cpu(), ref.view(N, HW, C_).permute(0, 2, 1)) < 1e-6
+    # per element: the fp32 NCHW output inside the bracket of relu(fma) + relu(fma) and one add; the bf16 output one rounding of it
+    iv = add_act_interval(act_interval(a, sa, ta, False, DEV), act_interval(b, sb, tb, False, DEV))
+    check_store_bound(out, iv, "add_act C %d bf16" % C_, "add_act")
+    check_interval(onchw.permute(0, 2, 1).reshape(rows, C_), iv, "add_act C %d fp32 NCHW" % C_, "add_act")
     # identity + single input
     A2 = act_in(ad)
     L.check(lib.mnas_add_act(C.byref(A2), None, rows, C_, out.data_ptr(), 0, HW, L.cur_stream()))
@@ -671,9 +716,10 @@ def test_run_ops_batch():
     assert lib.mnas_run_ops(ops, 3, L.cur_stream(), C.byref(failed)) != 0 and failed.value == 1
 
 
-@pytest.mark.parametrize("C_,nparts", [(16, 1024), (40, 257), (1152, 64), (1152, 513)])
+@pytest.mark.parametrize("C_,nparts", [(16, 1024), (40, 257), (1152, 64), (1152, 513), (8, 1), (24, 256), (16, 1025)])
 def test_bn_bwd_finalize_long_rows(C_, nparts):
-    """Both finalize shapes (wave per channel / block per channel) against an fp64 sum of the same partial table."""
+    """Both finalize shapes (wave per channel / block per channel) against an fp64 sum of the same partial table; + the brackets of
+    gpu_util.bn_bwd_finalize_intervals on rows 2..4, dgamma and dbeta (1025 partials: two terms per fp32 accumulator)."""
     lib = L.load()
     partial = O.det_uniform((2, C_, nparts), 31)
     b = rand_bn_coefs(C_, 9, O)
@@ -688,6 +734,11 @@ def test_bn_bwd_finalize_long_rows(C_, nparts):
     assert relerr(dbeta.cpu(), S[0]) < 1e-5 and relerr(dgamma.cpu(), S[1]) < 1e-5
     assert relerr(out[3], -s * invstd * S[1] / rows) < 1e-5
     assert relerr(out[4], s * (mean * invstd * S[1] / rows - S[0] / rows)) < 1e-5
+    ivs = bn_bwd_finalize_intervals(partial, rows, b)
+    fin = {"c1": bd[2], "c2": bd[3], "c3": bd[4], "dgamma": dgamma, "dbeta": dbeta}
+    for k, iv in ivs.items():
+        r = check_interval(fin[k].cpu(), iv, "bn_bwd_finalize C %d nparts %d %s" % (C_, nparts, k), "BatchNorm backward finalize")
+        print("bn_bwd_finalize C %d nparts %d %s error / bound %.3f" % (C_, nparts, k, r))
 
 
 @pytest.mark.parametrize("nsplit,Co,Ci,taps,acc", [(5, 24, 16, 1, 0), (300, 16, 48, 1, 1), (300, 16, 48, 1, 0),
@@ -702,6 +753,10 @@ def test_wgrad_finalize_split_ranges(nsplit, Co, Ci, taps, acc):
     L.check(lib.mnas_wgrad_finalize(part.cuda().data_ptr(), nsplit, Co, Ci, taps, grad.data_ptr(), acc, L.cur_stream()))
     ref = part.double().sum(0).view(Co, taps, Ci).permute(0, 2, 1) + (init.double() if acc else 0)
     assert relerr(grad.cpu(), ref) < 1e-5
+    # check_sum_bound: M = nsplit terms in some fixed tree (nsplit - 1 adds however it is cut), the accumulate target is the +1; c = 1
+    lay = lambda t: t.double().abs().sum(0).view(Co, taps, Ci).permute(0, 2, 1)
+    r = check_sum_bound(grad.cpu(), ref, lay(part) + (init.double().abs() if acc else 0), nsplit, 0, 1,
+                        "wgrad_finalize nsplit %d acc %d" % (nsplit, acc), None, "weight-gradient finalize")
     k = 3
     dpart = O.det_uniform((nsplit, k * k, Co), 43)
     dinit = O.det_uniform((Co, k * k), 44)
@@ -709,6 +764,9 @@ def test_wgrad_finalize_split_ranges(nsplit, Co, Ci, taps, acc):
     L.check(lib.mnas_dw_wgrad_finalize(dpart.cuda().data_ptr(), nsplit, Co, k, dgrad.data_ptr(), acc, L.cur_stream()))
     dref = dpart.double().sum(0).t() + (dinit.double() if acc else 0)
     assert relerr(dgrad.cpu(), dref) < 1e-5
+    r2 = check_sum_bound(dgrad.cpu(), dref, dpart.double().abs().sum(0).t() + (dinit.double().abs() if acc else 0), nsplit, 0, 1,
+                         "dw_wgrad_finalize nsplit %d acc %d" % (nsplit, acc), None, "weight-gradient finalize")
+    print("wgrad finalizes nsplit %d acc %d: error / bound %.3f, %.3f" % (nsplit, acc, r, r2))
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1009,3 +1067,142 @@ def test_sparse_probe_dw_fwd_statistics():
     r64, S = dw_fwd_terms(Interval.exact(x, DEV), w.view(C_, k, k), None, 1, DEV)
     check_dw_bound(out, r64, S, k, "sparse dw_fwd", "sparse probes: elements")
     check_stats_bound(st, r64, dw_elem_err(S, k), N * H * W, "sparse dw_fwd", "sparse probes")
+
+
+# ---------------------------------------------------------------------------------------------------
+# stem input gradient on its own (no forward / weight-gradient launch: those take 16 and 32 couts here), pooling glue, and the
+# sparse probes of the stem gradients and of mnas_pool_act
+def _stem_dgrad(g, yd, bd, w32, N, H, W, Co, aff):
+    lib = L.load()
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    dx, chk = guarded((N, 3, H, W), torch.float32)
+    affd = aff.cuda().contiguous() if aff is not None else None
+    gi = grad_in(g, yd, bd)
+    L.check(lib.mnas_stem_dgrad(C.byref(gi), w32.data_ptr(), N, H, W, Ho, Wo, Co, L.ptr(affd), dx.data_ptr(), L.cur_stream()), "stem_dgrad")
+    chk("stem_dgrad dx")
+    return dx
+
+
+@pytest.mark.parametrize("shape", [(2, 9, 11, 8), (1, 10, 12, 128), (6, 1, 1, 16), (3, 2, 7, 32)])
+def test_stem_dgrad(shape):
+    """mnas_stem_dgrad at 8 and 128 couts (the ends of what it takes), a 1x1 image (one contributing pixel, one tap) and odd /
+    even sizes, fp32 weights that are not bf16 values: every element inside stem_dgrad_terms' bound, with and without in_affine"""
+    N, H, W, Co = shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    b = rand_bn_coefs(Co, 9, O)
+    g, y = _x((N, Co, Ho, Wo), 6), _xoff((N, Co, Ho, Wo), 7, b[0], b[1])
+    w_raw = O.det_param("t.conv.weight", (Co, 3, 3, 3), 2)
+    w = bf16r(w_raw)
+    assert not torch.equal(w, w_raw)
+    gd, yd, bd, w32 = nhwc(g), nhwc(y), b.cuda(), w_raw.cuda().contiguous()
+    div = dy_interval(_nh(g), _nh(y), b, True, DEV)
+    for aff in (None, torch.tensor([[2.0, 0.5, 1.25], [0.1, 0.2, 0.3]])):
+        dx = _stem_dgrad(gd, yd, bd, w32, N, H, W, Co, aff)
+        r64, bound = stem_dgrad_terms(div, w, H, W, aff, DEV)
+        r = _assert_bound(dx, r64, bound, "stem_dgrad %s affine %d" % (shape, aff is not None), "stem input gradient")
+        print("stem_dgrad %s error / bound %.3f" % (shape, r))
+
+
+def test_sparse_probe_stem_dgrad():
+    """dy live at the four corners of the output plane of both images and at one interior pixel of each row / column parity (dy = g
+    through the identity coefficients); odd H (the last output row's footprint ends at the last image row), even W.  dx inside
+    stem_dgrad_terms' bound, exactly zero outside the live pixels' 3x3 footprints, and each live pixel visible."""
+    N, H, W, Co = 2, 9, 10, 16
+    Ho, Wo = 5, 5
+    at = lambda n, h, w_: (n * Ho + h) * Wo + w_
+    px = sorted({at(n, h, w_) for n in range(N) for h in (0, Ho - 1) for w_ in (0, Wo - 1)} | {at(0, 1, 2), at(0, 2, 1), at(1, 1, 1), at(1, 2, 2)})
+    g = _live((N, Ho, Wo, Co), px, 2)
+    b = _ident_bn(Co)
+    w_raw = O.det_param("t.conv.weight", (Co, 3, 3, 3), 2)
+    w = bf16r(w_raw)
+    gd, yd = g.to(torch.bfloat16).cuda(), torch.ones((N, Ho, Wo, Co), dtype=torch.bfloat16, device="cuda")
+    dx = _stem_dgrad(gd, yd, b.cuda(), w_raw.cuda().contiguous(), N, H, W, Co, None)
+    d = Interval.exact(g, DEV)
+    r64, bound = stem_dgrad_terms(d, w, H, W, None, DEV)
+    _assert_bound(dx, r64, bound, "sparse stem_dgrad", "sparse probes: elements")
+    foot = ref_dense_dgrad((g.abs().sum(-1, keepdim=True) > 0).double(), torch.ones(1, 1, 3, 3), H, W, 2, 1, DEV)[..., 0] > 0
+    assert 0 < int(foot.sum()) < foot.numel()
+    assert not bool(dx.permute(0, 2, 3, 1)[~foot].any()), "dx is not exactly zero outside the live pixels' footprints"
+    def one(p):
+        d1 = torch.zeros_like(g)
+        d1.view(-1, Co)[p] = g.view(-1, Co)[p]
+        return ref_dense_dgrad(d1, w, H, W, 2, 1, DEV).permute(0, 3, 1, 2)
+    _each_pixel_visible([(p, one(p)) for p in px], bound, "sparse stem_dgrad")
+
+
+@pytest.mark.parametrize("Co", [32, 16])
+def test_sparse_probe_stem_wgrad(Co):
+    """mnas_stem_wgrad, 32 couts: the band kernel (bands of RB = 4 output rows, band i on workgroup i % nparts, the last band of
+    each image 2 rows); 16 couts: the im2col staging of k_wgrad (workgroup b owns pixels [b*128, (b+1)*128): 128-pixel blocks).
+    Dense image, dy = g (identity coefficients) live at the four corners of both images' output planes (the image boundary among
+    them, and column Wo-1), on both sides of the first band resp. block boundary (which is also the first workgroup boundary) --
+    across the row end and within one column -- and of the 64-pixel mark.  check_sum_bound, c = 1, zero slack; each pixel visible."""
+    lib = L.load()
+    N, H, W, nparts = 2, 20, 32, 4
+    Ho, Wo = 10, 16
+    M = N * Ho * Wo
+    at = lambda n, h, w_: (n * Ho + h) * Wo + w_
+    if Co == 32:
+        assert lib.mnas_stem_parts(1, N, H, W, Co) == 6           # a band shape: 2 x ceil(10 / 4) bands, more than nparts
+        RB = stem_wgrad_band_rows(W, Wo)
+        assert RB == 4 and Ho % RB
+        bnd = RB * Wo
+    else:
+        assert lib.mnas_stem_parts(1, N, H, W, Co) == -1
+        bnd = ((M + nparts - 1) // nparts + 127) // 128 * 128
+        assert bnd == 128 and 2 * bnd < M
+    px = {at(n, h, w_) for n in range(N) for h in (0, Ho - 1) for w_ in (0, Wo - 1)}
+    px |= {bnd - 1, bnd, bnd - Wo + 5, bnd + 5, 63, 64, at(0, Ho - 1, 7), at(1, Ho - 2, 9)}
+    px = sorted(px)
+    x = bf16r(O.det_uniform((N, 3, H, W), 1))
+    g = _live((N, Ho, Wo, Co), px, 2)
+    gd, yd, bd = g.to(torch.bfloat16).cuda(), torch.ones((N, Ho, Wo, Co), dtype=torch.bfloat16, device="cuda"), _ident_bn(Co).cuda()
+    xd = x.cuda()
+    partial, pchk = guarded((nparts, Co, 27), torch.float32)
+    s = L.MnasStemWgrad()
+    s.N, s.H, s.W, s.Ho, s.Wo, s.Co, s.nparts = N, H, W, Ho, Wo, Co, nparts
+    s.x, s.dy, s.partial = xd.data_ptr(), grad_in(gd, yd, bd), partial.data_ptr()
+    L.check(lib.mnas_stem_wgrad(C.byref(s), L.cur_stream()), "stem_wgrad")
+    pchk("sparse stem_wgrad partial")
+    grad = torch.full((Co, 3, 3, 3), float("nan"), device="cuda")
+    L.check(lib.mnas_wgrad_finalize(partial.data_ptr(), nparts, Co, 27, 1, grad.data_ptr(), 0, L.cur_stream()))
+    r64, S, slack = wgrad_terms(Interval.exact(_nh(x), DEV), Interval.exact(g, DEV), 3, 2, 1, DEV)
+    assert float(slack.max()) == 0.0
+    what = "sparse stem_wgrad Co %d" % Co
+    check_sum_bound(grad, r64, S, M, nparts, 1, what, None, "sparse probes")
+    def one(p):
+        d1 = torch.zeros_like(g)
+        d1.view(M, Co)[p] = g.view(M, Co)[p]
+        return ref_dense_wgrad(_nh(x), d1, 3, 2, 1, DEV)
+    _each_pixel_visible([(p, one(p)) for p in px], sum_bound(S, M, nparts, 1), what)
+
+
+@pytest.mark.parametrize("shape", [(2, 49, 320), (1, 1, 8), (2, 196, 1152), (3, 9, 8)])     # (N, HW, C)
+@pytest.mark.parametrize("virt", [True, False])
+def test_pool_act(shape, virt):
+    """mnas_pool_act: R = 256 / (C / 8) row lanes, 8 loads per lane and batch pass.  (2, 49, 320): R = 6, the second pass holds one
+    pixel; (1, 1, 8); (2, 196, 1152): R = 1; (3, 9, 8): R = 256 > HW.  Dense: every output inside pool_act_terms' bound
+    (check_sum_bound's sum, then the division).  Sparse: pixels 0, R-1, R, 8R-1, 8R, HW-1 live where they exist -- virtual through
+    the identity (1, 0), under which relu(0) = 0 keeps the others silent -- and each live pixel visible."""
+    lib = L.load()
+    N, HW, C_ = shape
+    R = 256 // (C_ // 8)
+    x = bf16r(O.det_uniform((N, HW, C_), 61))
+    s, t = 1 + 0.3 * O.det_uniform((C_,), 62), 0.2 * O.det_uniform((C_,), 63)
+    px = sorted({p for p in (0, R - 1, R, 8 * R - 1, 8 * R, HW - 1) if 0 <= p < HW})
+    xs = torch.zeros_like(x)
+    xs[:, px] = x[:, px]
+    one, zero = torch.ones(C_), torch.zeros(C_)
+    for what, xin, sc, sh in (("dense", x, s, t), ("sparse", xs, one, zero)):
+        xd, sd, td = xin.to(torch.bfloat16).cuda(), sc.cuda(), sh.cuda()
+        A = act_in(xd, sd, td) if virt else act_in(xd)
+        out, chk = guarded((N, C_), torch.float32)
+        L.check(lib.mnas_pool_act(C.byref(A), N, HW, C_, L.ptr(out), L.cur_stream()), "pool_act")
+        what = "pool_act %s virt %d %s" % (shape, virt, what)
+        chk(what)
+        aiv = act_interval(xin, sc, sh, False, DEV) if virt else Interval.exact(xin, DEV)
+        ref, bound = pool_act_terms(aiv, HW)
+        r = _assert_bound(out, ref, bound, what, "pool_act" if xin is x else "sparse probes")
+        print(what, "error / bound %.3f" % r)
+    a = torch.relu(xs) if virt else xs
+    _each_pixel_visible([(p, (a[:, p] / HW).to(DEV)) for p in px], bound, what)

@@ -11,9 +11,30 @@ import torch
 import cases as C
 from cases import O
 from gpu_util import L, act_in, bf16r, from_nhwc, nhwc, relerr
+from gpu_util import (Interval, act_interval, check_interval, check_onload_bound, check_sigmoid, check_red_bound, check_stats_bound, check_store_bound,
+                      check_sum_bound, gate_nhwc, gated_act_interval, gated_fwd_inputs, imul, off_hinge, onload_elem_err,
+                      onload_fwd_terms, se_apply_interval, se_fc_bwd_terms, se_fc_fwd_intervals, se_geom, se_proj_finalize_intervals,
+                      se_reduce_terms, sig1m_interval, sigmoid_interval, sum_interval)
 from oracle import bf16_mirror as M
 
 pytestmark = pytest.mark.gpu
+DEV = "cuda"            # where the fp64 terms of the per-element bounds are computed
+
+
+def test_se_gate_against_fp64_sigmoid():
+    """mnas_se_gate = se_sigmoid, the function every squeeze-excite kernel evaluates: v in [-30, 30] in steps of 1/64 and +-0, every
+    element inside gpu_util.sigmoid_interval -- the check of that bracket's one assumption (the hardware exponential within one
+    ulp); v = +-100 gives finite values in [0, 1]"""
+    lib = L.load()
+    v = torch.cat([torch.arange(-30 * 64, 30 * 64 + 1).float() / 64, torch.tensor([0.0, -0.0, 100.0, -100.0])])
+    n = v.numel()
+    vd = v.cuda()
+    gate = torch.full((n,), float("nan"), device="cuda")
+    L.check(lib.mnas_se_gate(vd.data_ptr(), 1, n, gate.data_ptr(), L.cur_stream()), "se_gate")
+    g = gate.cpu()
+    r = check_sigmoid(g[:-2], v[:-2], "mnas_se_gate")
+    print("mnas_se_gate against the fp64 sigmoid: error / bracket %.3f" % r)
+    assert bool(torch.isfinite(g[-2:]).all()) and bool(((g[-2:] >= 0) & (g[-2:] <= 1)).all()), g[-2:]
 
 
 def rl2(a, b):
@@ -21,11 +42,29 @@ def rl2(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
-@pytest.mark.parametrize("N,E,R", [(256, 48, 8), (5, 240, 10), (33, 576, 24), (256, 1152, 48), (1, 72, 8), (7, 100, 13)])
+def _flat_views(tensors):
+    """{name: tensor} -> {name: view}: the tensors laid out back to back in ONE device buffer starting 4 bytes into it, as the
+    trainer's flat parameter / gradient buffers hand them over: 4-byte aligned, the first one not 16-byte aligned"""
+    total = sum(v.numel() for v in tensors.values())
+    flat = torch.empty(total + 1, device="cuda")
+    out, off = {}, 1
+    for k, v in tensors.items():
+        out[k] = flat[off:off + v.numel()].view(v.shape)
+        out[k].copy_(v)
+        off += v.numel()
+    first = next(iter(out.values()))
+    assert first.data_ptr() % 16 == 4
+    return out, flat
+
+
+@pytest.mark.parametrize("N,E,R", [(256, 48, 8), (5, 240, 10), (33, 576, 24), (256, 1152, 48), (1, 72, 8), (7, 100, 13),
+                                   (3, 1280, 48), (2, 8, 1)])         # + the largest supported shape, and one hidden unit
 def test_se_fused_mlp(N, E, R):
     """mnas_se_fc_fwd / mnas_se_fc_bwd (the excitation MLP in 1 + 2 kernels) against fp32 torch math; accumulate on and off, gate on
-    and off.  fp32 sums in another order: <= 1e-5 of max |ref| (measured 1e-6)."""
+    and off.  fp32 sums in another order: <= 1e-5 of max |ref| (measured 1e-6).  + the brackets of gpu_util.se_fc_fwd_intervals /
+    se_fc_bwd_terms on every output.  Parameters and gradients are views at a 4-byte (not 16-byte) aligned offset of one buffer."""
     lib = L.load()
+    assert lib.mnas_se_fc_supported(E, R) == 1
     g = torch.Generator().manual_seed(N * 1000 + E)
     z = torch.rand(N, E, generator=g)
     W1, b1 = torch.randn(R, E, generator=g) / E ** 0.5, 0.1 * torch.randn(R, generator=g)
@@ -37,15 +76,22 @@ def test_se_fused_mlp(N, E, R):
     dh_ref = (du.double() @ W2.double()) * (hb_ref > 0)
     dz_ref = dh_ref @ W1.double()
     refs = {"dW1": dh_ref.t() @ z.double(), "db1": dh_ref.sum(0), "dW2": du.double().t() @ hb_ref, "db2": du.double().sum(0)}
-    d = {k: v.cuda().contiguous() for k, v in dict(z=z, W1=W1, b1=b1, W2=W2, b2=b2, du=du).items()}
+    d = {k: v.cuda().contiguous() for k, v in dict(z=z, du=du).items()}
+    params, _keep = _flat_views(dict(W1=W1, b1=b1, W2=W2, b2=b2))
+    d.update(params)
+    hb_iv, u_iv, gate_iv = se_fc_fwd_intervals(z, W1, b1, W2, b2)
+    what = "se_fc N %d E %d R %d " % (N, E, R)
     nan = lambda *sh: torch.full(sh, float("nan"), device="cuda")
     for with_gate in (True, False):
         hb, u, gate = nan(N, R), nan(N, E), nan(N, E)
         L.check(lib.mnas_se_fc_fwd(d["z"].data_ptr(), d["W1"].data_ptr(), d["b1"].data_ptr(), d["W2"].data_ptr(), d["b2"].data_ptr(), N, E, R,
                                    hb.data_ptr(), u.data_ptr(), gate.data_ptr() if with_gate else None, L.cur_stream()), "se_fc_fwd")
         assert relerr(hb.cpu(), hb_ref) < 1e-5 and relerr(u.cpu(), u_ref) < 1e-5
+        check_interval(hb.cpu(), hb_iv, what + "hb", "excite MLP")
+        check_interval(u.cpu(), u_iv, what + "u", "excite MLP")
         if with_gate:
             assert relerr(gate.cpu(), torch.sigmoid(u_ref)) < 1e-5
+            check_interval(gate.cpu(), gate_iv, what + "gate", "excite MLP")
         else:
             assert bool(torch.isnan(gate).all())
     # the hidden row the backward masks with is the one the forward stored (a pre-activation at +-1e-7 may round either way)
@@ -56,7 +102,7 @@ def test_se_fused_mlp(N, E, R):
     for acc in (0, 1):
         dh, dz = nan(N, R), nan(N, E)
         base = {k: (0.5 * torch.randn(v.shape, generator=g)) for k, v in refs.items()}
-        out = {k: (base[k].cuda().contiguous() if acc else nan(*v.shape)) for k, v in refs.items()}
+        out, _keep_g = _flat_views({k: (base[k] if acc else torch.full(v.shape, float("nan"))) for k, v in refs.items()})
         L.check(lib.mnas_se_fc_bwd(d["du"].data_ptr(), d["z"].data_ptr(), hb.data_ptr(), d["W1"].data_ptr(), d["W2"].data_ptr(), N, E, R,
                                    dh.data_ptr(), dz.data_ptr(), out["dW1"].data_ptr(), out["db1"].data_ptr(), out["dW2"].data_ptr(),
                                    out["db2"].data_ptr(), acc, L.cur_stream()), "se_fc_bwd")
@@ -64,20 +110,57 @@ def test_se_fused_mlp(N, E, R):
         for k, v in refs.items():
             want = v + (base[k].double() if acc else 0)
             assert relerr(out[k].cpu(), want) < 1e-5, (k, acc)
+        dh_iv, dz_iv, terms = se_fc_bwd_terms(du, z, hb.cpu(), W1, W2, base if acc else None)
+        check_interval(dh.cpu(), dh_iv, what + "dh", "excite MLP")
+        check_interval(dz.cpu(), dz_iv, what + "dz", "excite MLP")
+        for k, (r64, S, slack, c) in terms.items():
+            check_sum_bound(out[k].cpu(), r64, S, N, 16, c, what + "%s accumulate %d" % (k, acc), slack, "excite MLP")
     assert lib.mnas_se_fc_fwd(d["z"].data_ptr(), d["W1"].data_ptr(), d["b1"].data_ptr(), d["W2"].data_ptr(), d["b2"].data_ptr(), N, E, 49,
                               hb.data_ptr(), u.data_ptr(), None, L.cur_stream()) != 0          # more hidden units than the kernels hold
 
 
-@pytest.mark.parametrize("shape", [(3, 14, 14, 48), (2, 7, 7, 1152), (5, 28, 28, 240), (2, 5, 9, 72), (4, 112, 112, 48)])
+def _geom(lib, N, HW, Cc):
+    """(G, R, chunk, splits) of csrc/mnas_se.hip::se_geom, derived on the host and asserted against the library's two answers"""
+    G_, R, chunk, splits = se_geom(N, HW, Cc)
+    assert lib.mnas_se_scratch_bytes(N, HW, Cc) == splits * N * Cc * 4, (N, HW, Cc, R, chunk, splits)
+    assert lib.mnas_se_bwd_apply_cols(N, HW, Cc) == N * splits
+    assert chunk % R == 0 and (splits - 1) * chunk < HW <= splits * chunk
+    return G_, R, chunk, splits
+
+
+SE_SHAPES = [(3, 14, 14, 48), (2, 7, 7, 1152), (5, 28, 28, 240), (2, 5, 9, 72), (4, 112, 112, 48),
+             # the corners of se_geom: G = 1 and R = 256 > HW; G = 9 does not divide 256 (four idle threads), HW < R = 28; R = 1;
+             # two splits with a ragged second one (chunk 126 of 196 pixels); N > 2048 (one split per image)
+             (3, 5, 9, 8), (2, 3, 3, 72), (2, 2, 2, 2048), (2, 14, 14, 48), (2049, 2, 2, 8)]
+
+
+@pytest.mark.parametrize("shape", SE_SHAPES)
 @pytest.mark.parametrize("virt", [True, False])
 def test_se_kernels(shape, virt):
+    """+ per element: mnas_se_scale in the bf16 bracket of the gated operand (check_store_bound over gated_act_interval),
+    mnas_se_bwd_reduce in the bracket of (sum of HW fma terms, R row lanes and `splits` partial rows) x s(1-s), mnas_se_bwd_apply
+    in the bf16 bracket of fma(gs, s, dz/HW), its fused reduce under check_red_bound (y off the ReLU hinge)."""
+    _se_kernels(shape, virt, 2.0)
+
+
+@pytest.mark.parametrize("shape", [(2, 14, 14, 48), (2, 5, 9, 72)])
+@pytest.mark.parametrize("virt", [True, False])
+def test_se_kernels_gate_near_0_and_1(shape, virt):
+    """the same with |u| <= 12: the sigmoid within 6e-6 of 0 or 1, where 1 - s cancels"""
+    _se_kernels(shape, virt, 12.0)
+
+
+def _se_kernels(shape, virt, amp):
     N, H, W, Cc = shape
     lib = L.load()
     HW = H * W
-    y = bf16r(O.det_uniform((N, Cc, H, W), 800))
+    G_, R, chunk, splits = _geom(lib, N, HW, Cc)
+    if shape == (2, 14, 14, 48):
+        assert (R, chunk, splits) == (42, 126, 2)
     s, t = 1 + 0.3 * O.det_uniform((Cc,), 801), 0.2 * O.det_uniform((Cc,), 802)
+    y = off_hinge(bf16r(O.det_uniform((N, Cc, H, W), 800)).permute(0, 2, 3, 1), s, t).permute(0, 3, 1, 2).contiguous()
     a = torch.relu(y * s.view(1, -1, 1, 1) + t.view(1, -1, 1, 1)) if virt else y
-    u = 2.0 * O.det_uniform((N, Cc), 803)
+    u = amp * O.det_uniform((N, Cc), 803)
     sg = torch.sigmoid(u)
     gs = bf16r(O.det_uniform((N, Cc, H, W), 804))
     dz = O.det_uniform((N, Cc), 805)
@@ -86,16 +169,25 @@ def test_se_kernels(shape, virt):
     out = torch.full((N, H, W, Cc), float("nan"), dtype=torch.bfloat16, device="cuda")
     L.check(lib.mnas_se_scale(C_.byref(ai), ud.data_ptr(), N, HW, Cc, out.data_ptr(), L.cur_stream()), "se_scale")
     assert relerr(from_nhwc(out), a * sg[:, :, None, None]) < 6e-3
+    what = "se %s |u| <= %g virt %d: " % (shape, amp, virt)
+    yn, gsn = y.permute(0, 2, 3, 1), gs.permute(0, 2, 3, 1)
+    g4 = gate_nhwc(sigmoid_interval(u, DEV), yn.shape)
+    check_store_bound(out, gated_act_interval(yn, s if virt else None, t if virt else None, g4, False, DEV), what + "se_scale", "se_scale")
     du = torch.full((N, Cc), float("nan"), device="cuda")
     scr = torch.full((lib.mnas_se_scratch_bytes(N, HW, Cc) // 4,), float("nan"), device="cuda")
     L.check(lib.mnas_se_bwd_reduce(gsd.data_ptr(), C_.byref(ai), ud.data_ptr(), N, HW, Cc, du.data_ptr(), scr.data_ptr(),
                                    L.cur_stream()), "se_bwd_reduce")
     assert relerr(du.cpu(), (gs * a).sum((2, 3)) * sg * (1 - sg)) < 2e-3
+    aiv = act_interval(yn, s, t, False, DEV) if virt else Interval.exact(yn, DEV)
+    r64, S, slack = se_reduce_terms(gsn, aiv, HW)
+    check_interval(du, imul(sum_interval(r64, S, HW, R + splits, 1, slack), sig1m_interval(u, DEV), 1), what + "se_bwd_reduce", "se_bwd_reduce")
+    del aiv, r64, S, slack
     ga = torch.full((N, H, W, Cc), float("nan"), dtype=torch.bfloat16, device="cuda")
     L.check(lib.mnas_se_bwd_apply(gsd.data_ptr(), ud.data_ptr(), dzd.data_ptr(), N, HW, Cc, ga.data_ptr(), None, None, None,
                                   L.cur_stream()), "se_bwd_apply")
     ga_ref = gs * sg[:, :, None, None] + dz[:, :, None, None] / HW
     assert relerr(from_nhwc(ga), ga_ref) < 6e-3
+    check_store_bound(ga, se_apply_interval(gsn, u, dz, HW, DEV), what + "se_bwd_apply", "se_bwd_apply")
     # ... with the fused BatchNorm-backward reduce of the conv that produced y (bnbuf rows 0,1,5,6)
     ncols = lib.mnas_se_bwd_apply_cols(N, HW, Cc)
     bn = torch.zeros(8, Cc)
@@ -112,10 +204,72 @@ def test_se_kernels(shape, virt):
     xh = ((y - v(5)) * v(6)).double()
     st = part.cpu().double().sum(-1)
     assert relerr(st[0], dzr.sum((0, 2, 3))) < 2e-3 and relerr(st[1], (dzr * xh).sum((0, 2, 3))) < 2e-3
+    assert ncols == N * splits
+    check_red_bound(part, ga2.float(), yd.float(), bn, N * HW, what + "se_bwd_apply", "fused reduce (squeeze-excite)")
+
+
+@pytest.mark.parametrize("shape", [(2, 14, 14, 48), (3, 28, 28, 240)])
+def test_sparse_probe_se_reduce(shape):
+    """mnas_se_bwd_reduce and the fused reduce of mnas_se_bwd_apply with gs live at pixels 0, R-1, R, chunk-1, chunk and HW-1 of the
+    first and the last image only (R, chunk from se_geom, asserted against the library): a dropped, doubled or misplaced pixel of a
+    row-lane or split boundary leaves the bound, which holds six terms per sum.  Plain dense y (exact operand); dz = 0, so the
+    apply output is gs*s at the live pixels and exactly zero elsewhere.  Each live pixel's own contribution is asserted visible."""
+    N, H, W, Cc = shape
+    lib = L.load()
+    HW = H * W
+    G_, R, chunk, splits = _geom(lib, N, HW, Cc)
+    assert splits >= 2 and R < chunk < HW
+    live = sorted({0, R - 1, R, chunk - 1, chunk, HW - 1})
+    s, t = torch.ones(Cc), torch.zeros(Cc)
+    y = off_hinge(bf16r(O.det_uniform((N, H, W, Cc), 830)), s, t)
+    gs = torch.zeros(N, HW, Cc)
+    for n in (0, N - 1):
+        gs[n, live] = bf16r(O.det_uniform((len(live), Cc), 831 + n))
+    gs = gs.view(N, H, W, Cc)
+    u = 2.0 * O.det_uniform((N, Cc), 832)
+    yd, gsd, ud = y.to(torch.bfloat16).cuda(), gs.to(torch.bfloat16).cuda(), u.cuda()
+    ai = act_in(yd)
+    du = torch.full((N, Cc), float("nan"), device="cuda")
+    scr = torch.full((splits * N * Cc,), float("nan"), device="cuda")
+    L.check(lib.mnas_se_bwd_reduce(gsd.data_ptr(), C_.byref(ai), ud.data_ptr(), N, HW, Cc, du.data_ptr(), scr.data_ptr(),
+                                   L.cur_stream()), "se_bwd_reduce")
+    r64, S, slack = se_reduce_terms(gs, Interval.exact(y, DEV), HW)
+    assert float(slack.max()) == 0.0
+    f = sig1m_interval(u, DEV)
+    iv = imul(sum_interval(r64, S, HW, R + splits, 1), f, 1)
+    what = "sparse se_bwd_reduce %s" % (shape,)
+    check_interval(du, iv, what, "sparse probes")
+    if N > 2:
+        assert not bool(du[1:N - 1].any()), "du of an image without a live pixel is not zero"
+    for n in (0, N - 1):
+        for p in live:
+            c = (gs.view(N, HW, Cc)[n, p] * y.view(N, HW, Cc)[n, p]).double().to(DEV) * f.lo[n]
+            assert bool((c.abs() > 2 * iv.half[n]).any()), "%s: the probe could not see pixel %d of image %d dropped" % (what, p, n)
+    # the fused reduce of the apply kernel: same geometry, one table column per (image, split)
+    dzd = torch.zeros(N, Cc, device="cuda")
+    bn = torch.zeros(8, Cc)
+    bn[0], bn[1], bn[5], bn[6] = s, t, 0.1 * O.det_uniform((Cc,), 833), 1.0 + 0.2 * O.det_uniform((Cc,), 834).abs()
+    bnd = bn.cuda().contiguous()
+    ga = torch.full((N, H, W, Cc), float("nan"), dtype=torch.bfloat16, device="cuda")
+    part = torch.full((2, Cc, N * splits), float("nan"), device="cuda")
+    L.check(lib.mnas_se_bwd_apply(gsd.data_ptr(), ud.data_ptr(), dzd.data_ptr(), N, HW, Cc, ga.data_ptr(), yd.data_ptr(), bnd.data_ptr(),
+                                  part.data_ptr(), L.cur_stream()), "se_bwd_apply+reduce")
+    dead = (gs == 0).cuda()
+    assert not bool(ga[dead].any()), "apply output of an element with gs = 0 and dz = 0 is not zero"
+    check_store_bound(ga, se_apply_interval(gs, u, torch.zeros(N, Cc), HW, DEV), "sparse se_bwd_apply %s" % (shape,), "sparse probes: elements")
+    check_red_bound(part, ga.float(), yd.float(), bn, N * HW, "sparse se_bwd_apply %s" % (shape,), "sparse probes")
+    # visible: sum dz of a channel holds at most 12 terms; its bound is (M + P + 1) 2^-22 of their magnitudes' sum
+    gq = ga.float().view(N, HW, Cc)
+    dzq = (gq * (y.view(N, HW, Cc).cuda() > 0)).double()
+    bound = (N * HW + N * splits + 1) * 2.0 ** -22 * dzq.abs().sum((0, 1))
+    for n in (0, N - 1):
+        for p in live:
+            assert bool((dzq[n, p].abs() > 2 * bound).any()), "sparse se_bwd_apply: the probe could not see pixel %d of image %d dropped" % (p, n)
 
 
 GATE_SHAPES = [  # (N, H, W, Ci, Co): the project convs of the 112x112 / 56x56 / 28x28 stages (k_igemm and the K-streaming kernel)
     (3, 112, 112, 48, 16), (5, 56, 56, 72, 24), (9, 28, 28, 240, 40), (2, 16, 9, 48, 16), (70, 28, 28, 240, 40)]
+GATE_BOUND_SHAPES = [(2, 16, 9, 48, 16), (9, 28, 28, 240, 40)]      # ... of which these are also held to the per-element bound
 
 
 @pytest.mark.parametrize("shape", GATE_SHAPES)
@@ -128,15 +282,12 @@ def test_gated_project_forward(shape):
     N, H, W, Ci, Co = shape
     lib = L.load()
     assert lib.mnas_conv_gemm_gate_ok(N, H * W, Ci, Co) == 1
-    y = bf16r(O.det_uniform((N, Ci, H, W), 810))
-    s, t = 1 + 0.3 * O.det_uniform((Ci,), 811), 0.2 * O.det_uniform((Ci,), 812)
-    u = 2.0 * O.det_uniform((N, Ci), 813)
-    w = bf16r(O.det_param("g.conv.weight", (Co, Ci, 1, 1), 3))
-    bias = O.det_uniform((Co,), 814) * 0.1
+    y, s, t, u, w, bias = gated_fwd_inputs(shape, O)
     yd, sd, td, ud = nhwc(y), s.cuda(), t.cuda(), u.cuda()
     gate = torch.full((N, Ci), float("nan"), device="cuda")
     L.check(lib.mnas_se_gate(ud.data_ptr(), N, Ci, gate.data_ptr(), L.cur_stream()), "se_gate")
     assert relerr(gate.cpu(), torch.sigmoid(u)) < 1e-6
+    check_sigmoid(gate.cpu(), u, "se_gate %s" % (shape,))
     a2s = torch.empty((N, H, W, Ci), dtype=torch.bfloat16, device="cuda")
     ai = act_in(yd, sd, td)
     L.check(lib.mnas_se_scale(C_.byref(ai), ud.data_ptr(), N, H * W, Ci, a2s.data_ptr(), L.cur_stream()), "se_scale")
@@ -152,12 +303,22 @@ def test_gated_project_forward(shape):
     a = bf16r(torch.relu(y * s.view(1, -1, 1, 1) + t.view(1, -1, 1, 1)) * torch.sigmoid(u)[:, :, None, None])
     ref = F.conv2d(a, w, bias)
     assert relerr(from_nhwc(out_g), ref) < 6e-3
+    if shape in GATE_BOUND_SHAPES:
+        # per element: the gated operand as an interval (the sigmoid's bracket times the activation's, one more rounding, both ends
+        # rounded to bf16; its straddle share is known from tests/test_bounds_cpu.py), K = Ci; the statistics sum the accumulator
+        yn = y.permute(0, 2, 3, 1)
+        iv = gated_act_interval(yn, s, t, gate_nhwc(sigmoid_interval(u, DEV), yn.shape), True, DEV)
+        r64, slack, S = onload_fwd_terms(iv, w, bias, device=DEV)
+        what = "gated 1x1 forward %s" % (shape,)
+        r = check_onload_bound(out_g, r64, slack, S, Ci, what, "gated 1x1 forward")
+        r2 = check_stats_bound(st_g, r64, onload_elem_err(slack, S, Ci), M, what, "forward statistics (gated)")
+        print(what, "error / bound %.3f, statistics %.3f, straddle share %.3g" % (r, r2, iv.split_share()))
     # a gate without the virtual activation, or on a shape without a gated kernel, is refused
     conv_gemm(0, N, H, W, Ci, H, W, Co, 1, 1, 0, wp, act=act_in(yd), nparts=nparts, gate=gate, expect=10001)
 
 
 @pytest.mark.parametrize("shape,kseg", [((3, 112, 112, 48, 16), 4), ((4, 56, 56, 72, 24), 2), ((6, 28, 28, 240, 40), 1),
-                                        ((5, 56, 56, 72, 24), 7), ((2, 28, 28, 240, 40), 4)])
+                                        ((5, 56, 56, 72, 24), 7), ((2, 28, 28, 240, 40), 4), ((1, 28, 28, 240, 40), 1)])
 def test_se_project_backward_segments(shape, kseg):
     """mnas_pw_bwd in segment mode (ABI 5: MnasPwBwd.seg_px) on the ungated activation + mnas_se_proj_finalize against fp32 math:
     gs = dy . W (the same bits as the strided launch), dW = sum_n s[n] * (per-image dy^T a2), du = (sum_pix gs*a2) s (1-s)."""
@@ -202,8 +363,15 @@ def test_se_project_backward_segments(shape, kseg):
     assert lib.mnas_pw_bwd(C_.byref(c), L.cur_stream()) == 10001
     dW = torch.full((Co, Ci), float("nan"), device="cuda")
     du = torch.full((N, Ci), float("nan"), device="cuda")
+    table = wpart.clone()                                         # the finalize's input: it folds the slabs in place
     L.check(lib.mnas_se_proj_finalize(wpart.data_ptr(), N, kseg, Co, Ci, ud.data_ptr(), wd.data_ptr(), dW.data_ptr(), 0,
                                       du.data_ptr(), L.cur_stream()), "se_proj_finalize")
+    # the finalize alone, per element, from the table the (separately bounded and probed) segment-mode launch wrote
+    du_iv, r64, S, slack, Msum = se_proj_finalize_intervals(table, N, kseg, w.view(Co, Ci), u)
+    what = "se_proj_finalize %s kseg %d" % (shape, kseg)
+    r = check_interval(du, du_iv, what + " du", "se_proj_finalize")
+    r2 = check_sum_bound(dW, r64, S, Msum, 0, 2, what + " dW", slack, "se_proj_finalize")
+    print(what, "error / bound: du %.3f dW %.3f" % (r, r2))
     a2b = bf16r(a2)                                               # the MFMA operand
     Pn = torch.einsum("nohw,nchw->noc", dy.double(), a2b.double())
     assert relerr(dW.cpu(), (Pn * sg[:, None, :].double()).sum(0)) < 2e-3
