@@ -56,7 +56,7 @@ typedef struct MnasGradIn {
     const float* coef;    /* float[5][C] */
 } MnasGradIn;
 
-int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, and + mnas_grad_sqnorm / mnas_*_step_ex, all additive: no layout or opcode changed, so still 8; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
+int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, and + mnas_grad_sqnorm / mnas_*_step_ex, and + mnas_head_cross_entropy_soft / mnas_img_mix, all additive: no layout or opcode changed, so still 8; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
                                          * 5 = squeeze-excite on load: MnasConvGemm.gate, MnasPwBwd.seg_px -- and in round 5: 6 = the opt-in
                                          * forms that lost their A/B are gone (MnasPwBwd.dy_out / red4, MnasDwBwd.src_* / g_gate / g_bias,
                                          * mnas_dw_exp_*, mnas_irb_*, mnas_gram*, mnas_se_bn_assemble); their opcode numbers stay retired) */
@@ -486,6 +486,26 @@ int mnas_head_cross_entropy_metrics(const void* logits, const void* target, int 
 int mnas_head_metrics(const void* logits, const void* target, int N, int C, const int* ks, int nk, const void* loss,
                       void* rank_rows, MnasMeters* meters, void* stream);
 
+/* ---- soft-target cross-entropy (csrc/mnas_head.hip; additive within ABI 8, outside the launch lists): label smoothing and batch
+ * mixing (Mixup / CutMix) in the loss of the step.  Every row has two labels a = target_a[n], b = target_b[n] and a weight
+ * l = lam[n] on a; its target row is
+ *     q = (1 - eps) (l e[a] + (1 - l) e[b]) + eps / C                          eps = label_smoothing in [0, 1]
+ * and, with lse = logsumexp(z[n]),
+ *     loss_rows[n]  = (1 - eps) (l (lse - z[n][a]) + (1 - l) (lse - z[n][b])) + eps (lse - mean_c z[n][c])
+ *     *loss         = sum(loss_rows) / count,   dlogits[n][c] = (softmax(z[n])[c] - q[c]) / count      (NULL: forward only)
+ * which is F.cross_entropy(z, a, label_smoothing=eps) and ..(z, b, ..) combined per row as l CE(a) + (1 - l) CE(b).
+ * target_b NULL: no mixing (b = a, l = 1; lam is not read).  lam NULL: l = 1 (device fp32 [N] otherwise).
+ * A row is ignored when a == ignore_index or, with mixing, b == ignore_index: it contributes 0 and is not counted; count = rows
+ * not ignored, 0/0 = NaN.  A label outside [0, C), or an l that is NaN or outside [0, 1], sets *bad_flag (int32, device) and
+ * poisons the loss with NaN; such a row indexes no memory.  Two launches, fixed summation order, no float atomics.
+ * meters non-NULL (then ks, nk, rank_rows as for mnas_head_cross_entropy_metrics): the same launches move the block; a row is
+ * ranked against the label that carries the larger weight, a when l >= 0.5, else b; ignored and refused rows are wrong for every
+ * k.  label_smoothing outside [0, 1]: MNAS_EINVAL, no launch. */
+int mnas_head_cross_entropy_soft(const void* logits, const void* target_a, const void* target_b, const float* lam,
+                                 float label_smoothing, int N, int C, int64_t ignore_index, void* loss_rows, void* loss,
+                                 void* dlogits, void* bad_flag, const int* ks, int nk, void* rank_rows, MnasMeters* meters,
+                                 void* stream);
+
 /* ---- the multi-label branch of the step (csrc/mnas_mlabel.hip): MultiClassBCELoss (src/models/multi_class_loss.py), HardDice
  * and the per-sample macro-F1 of batch_metrics (src/utils/metric.py) as train.py:274-279, 453-463, 577-587 use them, with the three
  * AverageMeters of that branch in one MnasMultiLabelMeters block in device memory.  logits z, target t, weights w: fp32 [N][C].
@@ -847,6 +867,35 @@ int64_t mnas_img_color_workspace_bytes(int n, int H, int W);
  * descriptor they read and write nothing for one they refuse (a CONTRAST item without a workspace included). */
 int mnas_img_color(const MnasImgColor* items, int n, int H, int W, int in_layout, const void* in, int out_layout, void* out,
                    void* workspace, void* stream);
+
+/* ---- batch mixing on uint8 images (csrc/mnas_imgm.hip; additive within ABI 8, outside the launch lists): Mixup and CutMix of
+ * every image of an (n, 3, H, W) uint8 NCHW batch -- the layout the stem's uint8 input path reads -- with a partner image of the
+ * same batch, so that a mixed batch stays a byte batch on the device:
+ *     NONE    out = x
+ *     MIXUP   out = (w x + (65536 - w) partner + 32768) >> 16 per byte, w = w16: integer arithmetic, defined byte for byte; at most
+ *             0.5 away from the real-valued blend with weight w / 65536 (correct rounding)
+ *     CUTMIX  out = partner inside rows [y0, y1) x columns [x0, x1) of every plane, x elsewhere
+ * The weight of x that the loss needs is w16 / 65536 for MIXUP and 1 - (y1 - y0) (x1 - x0) / (H W) for CUTMIX. */
+#define MNAS_IMGM_NONE   0             /* copy */
+#define MNAS_IMGM_MIXUP  1             /* integer blend with the partner, w16 in [0, 65536] on x */
+#define MNAS_IMGM_CUTMIX 2             /* the partner's bytes inside the box */
+typedef struct MnasImgMix {            /* 32 bytes */
+    int32_t mode;                      /* MNAS_IMGM_* */
+    int32_t partner;                   /* index of the other image, in [0, n); the image itself is allowed */
+    int32_t w16;                       /* 0..65536 (read by MIXUP) */
+    int32_t y0, x0, y1, x1;            /* 0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W (read by CUTMIX); empty boxes are allowed */
+    int32_t reserved;                  /* 0 */
+} MnasImgMix;
+/* Host-side validation, no launch: every item's mode known, partner in [0, n), w16 in [0, 65536], box ordered and inside the
+ * image, reserved 0 -- every field of every item, whatever its mode; n in [0, 65535], H, W in [1, MNAS_IMGX_MAX_OUT].  0 or
+ * MNAS_EINVAL.  items_host: HOST. */
+int mnas_img_mix_check(const MnasImgMix* items_host, int n, int H, int W);
+/* items (n descriptors), in and out (n*3*H*W bytes each, contiguous): device.  Out of place only: partner is any index of the
+ * batch, so a pass in place would read bytes it has already overwritten; in and out that overlap (in == out included) return
+ * MNAS_EINVAL with no launch.  One launch; 16-byte loads and stores when H*W % 16 == 0 and both buffers are 16-byte aligned, byte
+ * by byte otherwise.  Run the host check first; the kernel re-checks each descriptor it reads and writes nothing for one it
+ * refuses. */
+int mnas_img_mix(const MnasImgMix* items, int n, int H, int W, const void* in, void* out, void* stream);
 
 #ifdef __cplusplus
 }

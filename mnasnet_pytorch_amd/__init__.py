@@ -12,9 +12,10 @@ from .sampler import ClusterRandomSampler, DistributedClusterSampler  # noqa: F4
 from .transforms import (DeviceColorJitter, DevicePipeline, DeviceRandomGrayscale, DeviceTransform, ImageBatch,  # noqa: F401
                          collate_decoded)
 from .metrics import DeviceMeters, MultiLabelMeters, accuracy  # noqa: F401
-from .losses import HardDice, MultiClassBCELoss  # noqa: F401
+from .losses import HardDice, MixCrossEntropyLoss, MultiClassBCELoss  # noqa: F401
+from .mixing import DeviceMix, MixedTarget  # noqa: F401
 
 __all__ = ["Mnasnet", "ConvBlock", "SepConv", "MBConv_block", "MBConv", "load_model", "FineTuneModelPool",
            "ClusterRandomSampler", "DistributedClusterSampler", "DeviceTransform", "ImageBatch", "collate_decoded",
            "DevicePipeline", "DeviceColorJitter", "DeviceRandomGrayscale", "DeviceMeters", "accuracy",
-           "MultiLabelMeters", "MultiClassBCELoss", "HardDice"]
+           "MultiLabelMeters", "MultiClassBCELoss", "HardDice", "MixCrossEntropyLoss", "DeviceMix", "MixedTarget"]

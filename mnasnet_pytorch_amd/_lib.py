@@ -118,6 +118,14 @@ IMGC_MAX_OPS = 5
 IMGC_NCHW, IMGC_NHWC = 0, 1
 
 
+class MnasImgMix(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("partner", C.c_int32), ("w16", C.c_int32), ("y0", C.c_int32), ("x0", C.c_int32),
+                ("y1", C.c_int32), ("x1", C.c_int32), ("reserved", C.c_int32)]
+
+
+IMGM_NONE, IMGM_MIXUP, IMGM_CUTMIX = 0, 1, 2         # MNAS_IMGM_*
+
+
 class MnasOp(C.Structure):
     _fields_ = [("opcode", C.c_int32), ("i", C.c_int32 * 15), ("d", C.c_double * 4), ("p", c_void_p * 16)]
 
@@ -315,6 +323,8 @@ SYMBOLS = {
                                                 C.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
     "mnas_head_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, C.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
                                   c_void_p]),
+    "mnas_head_cross_entropy_soft": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int64, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, C.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
     "mnas_mlabel_scratch_bytes": (c_int64, [c_int]),
     "mnas_mlabel_bce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_int64, c_int64, c_int64, c_void_p]),
@@ -407,6 +417,8 @@ SYMBOLS = {
     "mnas_img_color_check": (c_int, [C.POINTER(MnasImgColor), c_int, c_int, c_int]),
     "mnas_img_color_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "mnas_img_color": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "mnas_img_mix_check": (c_int, [C.POINTER(MnasImgMix), c_int, c_int, c_int]),
+    "mnas_img_mix": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -445,6 +445,124 @@ extern "C" int mnas_head_cross_entropy_metrics(const void* logits, const void* t
     return MNAS_OK;
 }
 
+// ---- soft-target cross-entropy: label smoothing eps and batch mixing (Mixup / CutMix: two labels a, b per row, weight lam on a) --
+// target row  q = (1 - eps) (lam e[a] + (1 - lam) e[b]) + eps / C;  with lse = logsumexp(z):
+//   loss_rows[n] = (1 - eps) (lam (lse - z[a]) + (1 - lam) (lse - z[b])) + eps (lse - mean_c z)
+//   dlogits[n][c] = (softmax(z)[c] - q[c]) / count
+// tb == NULL: no mixing (b = a, lam = 1, lam[] is not read); lam == NULL: 1.  A row is ignored when a or (with mixing) b is
+// ignore_index; count = rows not ignored.  A label outside [0, C) or a lam that is NaN or outside [0, 1] raises *bad and poisons
+// the loss; such a row indexes nothing.  The same launch shape as k_head_ce / k_head_loss_mean; sum_c z rides on the max pass.
+// METRICS: the row is ranked against the label with the larger weight, a when lam >= 0.5.
+__device__ __forceinline__ bool head_soft_counts(const long long* ta, const long long* tb, int i, long long ignore_index) {
+    return ta[i] != ignore_index && (tb == nullptr || tb[i] != ignore_index);
+}
+
+template <bool METRICS>
+__global__ __launch_bounds__(256) void k_head_ce_soft(const float* x, const long long* ta, const long long* tb, const float* lam,
+                                                      float eps, int N, int C, long long ignore_index, float* loss_rows,
+                                                      float* dlogits, int* bad, int* rank_rows) {
+    __shared__ float red[4];
+    __shared__ int redi[4];
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const float* row = x + (size_t)n * C;
+    float cnt = 0.f;
+    for (int i = tid; i < N; i += 256) cnt += head_soft_counts(ta, tb, i, ignore_index) ? 1.f : 0.f;
+    cnt = head_wg_reduce(cnt, red, false);
+    const long long a = ta[n], b = tb ? tb[n] : a;
+    const float l = (tb && lam) ? lam[n] : 1.f;
+    const bool ignored = a == ignore_index || b == ignore_index;
+    const bool valid = !ignored && a >= 0 && a < C && b >= 0 && b < C && l >= 0.f && l <= 1.f;     // a NaN lam fails both
+    if (!ignored && !valid) {
+        if (tid == 0) atomicExch(bad, 1);
+    }
+    float mx = -INFINITY, sz = 0.f;
+    if (METRICS) {
+        const int ti = (int)(l >= 0.5f ? a : b);
+        const float zt = valid ? row[ti] : 0.f;
+        int above = 0;
+        for (int c = tid; c < C; c += 256) {
+            const float z = row[c];
+            mx = fmaxf(mx, z);
+            sz += z;
+            above += (z > zt || (z == zt && c < ti)) ? 1 : 0;
+        }
+        above = head_wg_reduce_int(above, redi);
+        if (tid == 0) rank_rows[n] = (valid && isfinite(zt)) ? above : HEAD_RANK_WRONG;
+    } else {
+        for (int c = tid; c < C; c += 256) {
+            const float z = row[c];
+            mx = fmaxf(mx, z);
+            sz += z;
+        }
+    }
+    mx = head_wg_reduce(mx, red, true);
+    sz = head_wg_reduce(sz, red, false);
+    float se = 0.f;
+    for (int c = tid; c < C; c += 256) se += expf(row[c] - mx);
+    se = head_wg_reduce(se, red, false);
+    const float inv = valid && cnt > 0.f ? 1.f / cnt : 0.f, rse = 1.f / se;
+    // weights of e[a], e[b] and of every class.  A row whose two labels coincide has the target it would have without mixing,
+    // whatever its lam: (1 - eps) on the one label, not two rounded shares of it
+    const bool same = a == b;
+    const float wa = same ? 1.f - eps : (1.f - eps) * l, wb = same ? 0.f : (1.f - eps) - wa, u = eps / (float)C;
+    if (dlogits)
+        for (int c = tid; c < C; c += 256) {
+            const float p = expf(row[c] - mx) * rse;
+            const float q = (c == (int)a ? wa : 0.f) + (c == (int)b && !same ? wb : 0.f) + u;
+            dlogits[(size_t)n * C + c] = valid ? (p - q) * inv : 0.f;
+        }
+    if (tid == 0) {
+        float r = ignored ? 0.f : NAN;                      // a refused row poisons the loss
+        if (valid) {
+            const float lse = logf(se) + mx;
+            r = wa * (lse - row[a]) + wb * (lse - row[b]) + eps * (lse - sz / (float)C);
+        }
+        loss_rows[n] = r;
+    }
+}
+
+template <bool METRICS>
+__global__ __launch_bounds__(256) void k_head_loss_mean_soft(const float* loss_rows, const long long* ta, const long long* tb, int N,
+                                                             long long ignore_index, float* loss, const int* rank_rows, HeadKs ks,
+                                                             MnasMeters* meters) {
+    __shared__ float red[4];
+    __shared__ int redi[4];
+    float s = 0.f, cnt = 0.f;
+    for (int i = threadIdx.x; i < N; i += 256) { s += loss_rows[i]; cnt += head_soft_counts(ta, tb, i, ignore_index) ? 1.f : 0.f; }
+    s = head_wg_reduce(s, red, false);
+    cnt = head_wg_reduce(cnt, red, false);
+    if (threadIdx.x == 0) *loss = s / cnt;       // 0/0 = nan when every row is ignored
+    if (METRICS) head_meters_update(rank_rows, N, ks, loss, meters, redi);   // thread 0 reads back its own store
+}
+
+extern "C" int mnas_head_cross_entropy_soft(const void* logits, const void* target_a, const void* target_b, const float* lam,
+                                            float label_smoothing, int N, int C, int64_t ignore_index, void* loss_rows, void* loss,
+                                            void* dlogits, void* bad_flag, const int* ks, int nk, void* rank_rows, MnasMeters* meters,
+                                            void* stream) {
+    if (!logits || !target_a || !loss_rows || !loss || !bad_flag || N < 1 || C < 1) return MNAS_EINVAL;
+    if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return MNAS_EINVAL;
+    HeadKs k = {};
+    if (meters && (!rank_rows || head_ks(ks, nk, C, &k) != MNAS_OK)) return MNAS_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const float* x = (const float*)logits;
+    const long long *ta = (const long long*)target_a, *tb = (const long long*)target_b;
+    if (meters) {
+        hipLaunchKernelGGL(k_head_ce_soft<true>, dim3(N), dim3(256), 0, s, x, ta, tb, lam, label_smoothing, N, C, (long long)ignore_index,
+                           (float*)loss_rows, (float*)dlogits, (int*)bad_flag, (int*)rank_rows);
+        MNAS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_head_loss_mean_soft<true>, dim3(1), dim3(256), 0, s, (const float*)loss_rows, ta, tb, N,
+                           (long long)ignore_index, (float*)loss, (const int*)rank_rows, k, meters);
+    } else {
+        hipLaunchKernelGGL(k_head_ce_soft<false>, dim3(N), dim3(256), 0, s, x, ta, tb, lam, label_smoothing, N, C,
+                           (long long)ignore_index, (float*)loss_rows, (float*)dlogits, (int*)bad_flag, (int*)nullptr);
+        MNAS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_head_loss_mean_soft<false>, dim3(1), dim3(256), 0, s, (const float*)loss_rows, ta, tb, N,
+                           (long long)ignore_index, (float*)loss, (const int*)nullptr, HeadKs{}, (MnasMeters*)nullptr);
+    }
+    MNAS_CHECK_LAUNCH();
+    return MNAS_OK;
+}
+
 // ---- the same counts for logits from anywhere (module path, another criterion, no loss at all): one workgroup per row for the
 // ranks, one workgroup for the block.  No ignore_index here: a target outside [0, C) is a wrong row.
 __global__ __launch_bounds__(256) void k_head_rank(const float* x, const long long* target, int C, int* rank_rows) {

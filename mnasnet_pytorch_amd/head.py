@@ -201,6 +201,24 @@ class NativeHead:
                 "head_cross_entropy")
         return loss, dl
 
+    def cross_entropy_soft(self, logits, target, label_smoothing=0.0, ignore_index=-100, need_grad=True, meters=None):
+        """-> (loss 0-d tensor, dlogits or None) of a losses.MixCrossEntropyLoss: cross-entropy with label smoothing over an int64
+        class vector or a mixing.MixedTarget (two labels and a weight per row).  ``meters`` (a metrics.DeviceMeters): the same two
+        launches move its block, every row ranked against its heavier label.  A plain class vector without smoothing runs
+        :meth:`cross_entropy`'s launches (same arithmetic, bit for bit what nn.CrossEntropyLoss() steps)."""
+        from .losses import soft_cross_entropy, split_target
+        a, b, lam = split_target(target)
+        if b is None and float(label_smoothing) == 0.0:
+            return self.cross_entropy(logits, a, ignore_index, need_grad=need_grad, meters=meters)
+        N, dev = logits.shape[0], logits.device
+        if b is not None:
+            target.check_device(dev)
+        key = (N, dev)
+        if key not in self._scratch:
+            self._scratch[key] = (torch.empty(N, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+        rows, bad = self._scratch[key]
+        return soft_cross_entropy(logits, a, b, lam, label_smoothing, ignore_index, rows=rows, bad=bad, need_grad=need_grad, meters=meters)
+
     def bce(self, logits, target, criterion, weights=None, need_grad=True, meters=None, f1_n=None):
         """-> (loss 0-d tensor, dlogits or None) of a losses.MultiClassBCELoss ``criterion`` (csrc/mnas_mlabel.hip).  target: (N, C),
         converted with .float() as train.py:429 does.  ``meters`` (a metrics.MultiLabelMeters): the same launches also update its
@@ -222,7 +240,8 @@ class NativeHead:
         for (N, dev), (_, bad) in self._scratch.items():
             if int(bad.item()) != 0:
                 bad.zero_()
-                raise ValueError("cross_entropy: a target index was outside [0, num_classes) and not ignore_index")
+                raise ValueError("cross_entropy: a target index was outside [0, num_classes) and not ignore_index "
+                                 "(or, for a mixed batch, a weight outside [0, 1])")
 
     # ---- entry points -----------------------------------------------------------------------------------------------
     def apply(self, x):
@@ -231,12 +250,15 @@ class NativeHead:
     def loss_and_grad(self, x, target, ignore_index=-100, need_dx=True, meters=None, criterion=None, f1_n=None):
         """Forward, loss and full backward of the head without autograd.  Parameter gradients are ACCUMULATED into
         ``p.grad`` (which must exist: Trainer points them into its flat gradient buffer).  -> (logits, loss, dx).
-        ``criterion``: None / an nn.CrossEntropyLoss -> cross-entropy with ``ignore_index``; a losses.MultiClassBCELoss -> :meth:`bce`."""
-        from .losses import MultiClassBCELoss
+        ``criterion``: None / an nn.CrossEntropyLoss -> cross-entropy with ``ignore_index``; a losses.MultiClassBCELoss -> :meth:`bce`;
+        a losses.MixCrossEntropyLoss -> :meth:`cross_entropy_soft` (``target``: a class vector or a mixing.MixedTarget)."""
+        from .losses import MixCrossEntropyLoss, MultiClassBCELoss
         seeds = self.next_seeds()
         us, logits = self.forward_layers(x, seeds)
         if type(criterion) is MultiClassBCELoss:             # the class itself, as Trainer routes it
             loss, dl = self.bce(logits, target, criterion, meters=meters, f1_n=f1_n)
+        elif type(criterion) is MixCrossEntropyLoss:
+            loss, dl = self.cross_entropy_soft(logits, target, criterion.label_smoothing, criterion.ignore_index, meters=meters)
         else:
             loss, dl = self.cross_entropy(logits, target, ignore_index, meters=meters)
         grads = []

@@ -6,6 +6,9 @@ builds ``MultiClassBCELoss()`` and ``HardDice(threshold=0.5)`` when ``--multi_cl
   optional element weights, optional focal transform of the MEAN (as the reference applies it).  Differentiable with respect to
   ``outputs``.  ``Trainer`` recognises this class and runs the whole step without autograd (head.NativeHead.bce).
 * :class:`HardDice` -- same constructor; returns a 0-d fp32 device tensor without a host sync.
+* :class:`MixCrossEntropyLoss` -- not from the reference: cross-entropy with label smoothing over class indices or over the two
+  labels per row of a mixed batch (mixing.MixedTarget; csrc/mnas_head.hip, include/mnas.h "soft-target cross-entropy").  ``Trainer``
+  recognises this class too (head.NativeHead.cross_entropy_soft).
 
 Deviations: the Dice prediction is ``outputs > logit(threshold)`` instead of ``sigmoid(outputs) > threshold`` (equal except where
 the fp32 sigmoid rounds onto the threshold), so the threshold must lie inside (0, 1); ``focus_param < 1`` is refused (the gradient
@@ -106,6 +109,96 @@ class MultiClassBCELoss(nn.Module):
     def forward(self, outputs, targets, weights=None):
         targets, weights = self.prepare(outputs, targets, weights)
         return _BCEFn.apply(outputs, targets, weights, bool(self.use_focal_weights), self.focus_param, self.balance_param)
+
+
+def soft_cross_entropy(logits, a, b=None, lam=None, label_smoothing=0.0, ignore_index=-100, rows=None, bad=None, need_grad=True,
+                       meters=None):
+    """mnas_head_cross_entropy_soft on (N, C) fp32 contiguous device logits -> (loss 0-d tensor, dlogits or None).  ``a``: int64 (N,);
+    ``b`` / ``lam``: the second label and the weight of ``a`` per row (int64 / fp32 (N,)), or None for no mixing.  ``rows`` / ``bad``:
+    the fp32 (N,) scratch and the int32 "target refused" flag (allocated when not given).  ``meters`` (a metrics.DeviceMeters): the
+    same two launches also move its block, every row ranked against its heavier label."""
+    lib = L.load()
+    N, Cn = logits.shape
+    dev = logits.device
+    for name, t, dt in (("target", a, torch.int64), ("second target", b, torch.int64), ("lam", lam, torch.float32)):
+        if t is None:
+            continue
+        _on_device(name, t, dev)
+        if t.dtype != dt or t.shape != (N,):
+            raise ValueError("%s must be %s of shape (N,) = (%d,), got %s %s" % (name, dt, N, t.dtype, tuple(t.shape)))
+    eps = float(label_smoothing)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError("label_smoothing must lie in [0, 1], got %r" % (label_smoothing,))
+    if rows is None:
+        rows = torch.empty(N, dtype=torch.float32, device=dev)
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dl = torch.empty_like(logits) if need_grad else None
+    ks, nk, ranks, blk = (None, 0, 0, 0) if meters is None else meters.kernel_args(N, dev)
+    L.check(lib.mnas_head_cross_entropy_soft(logits.data_ptr(), a.contiguous().data_ptr(), L.ptr(None if b is None else b.contiguous()),
+                                             L.ptr(None if lam is None else lam.contiguous()), eps, N, Cn, int(ignore_index),
+                                             rows.data_ptr(), loss.data_ptr(), L.ptr(dl), bad.data_ptr(), ks, nk, ranks, blk,
+                                             L.cur_stream()), "head_cross_entropy_soft")
+    return loss, dl
+
+
+def split_target(target):
+    """a class vector or a mixing.MixedTarget -> (a, b or None, lam or None)"""
+    from .mixing import MixedTarget
+    if isinstance(target, MixedTarget):
+        return target.a, target.b, target.lam
+    return target, None, None
+
+
+class _SoftCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, a, b, lam, label_smoothing, ignore_index, bad):
+        loss, dl = soft_cross_entropy(logits.detach().float().contiguous(), a, b, lam, label_smoothing, ignore_index, bad=bad,
+                                      need_grad=ctx.needs_input_grad[0])
+        ctx.dl, ctx.dtype = dl, logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return (ctx.dl * grad_output).to(ctx.dtype), None, None, None, None, None, None
+
+
+class MixCrossEntropyLoss(nn.Module):
+    """Mean cross-entropy with label smoothing over class indices (int64 ``(N,)``) or over a mixed batch's two labels per row (a
+    ``mixing.MixedTarget``): per row ``lam CE(a) + (1 - lam) CE(b)`` with ``CE = F.cross_entropy(..., label_smoothing)``, averaged
+    over the rows whose labels are not ``ignore_index``.  Differentiable with respect to the logits.  ``Trainer`` recognises this
+    class and runs the whole step without autograd.  No class weights.  No CPU path."""
+
+    def __init__(self, label_smoothing: float = 0.0, ignore_index: int = -100):
+        super().__init__()
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError("label_smoothing must lie in [0, 1], got %r" % (label_smoothing,))
+        self.label_smoothing = float(label_smoothing)
+        self.ignore_index = int(ignore_index)
+        self._bad = {}                   # device -> int32 flag raised by a refused label or weight
+
+    def forward(self, logits, target):
+        _on_device("logits", logits)
+        if logits.dim() != 2:
+            raise ValueError("logits must be (N, C), got %s" % (tuple(logits.shape),))
+        a, b, lam = split_target(target)
+        _on_device("target", a, logits.device)
+        bad = self._bad.get(logits.device)
+        if bad is None:
+            bad = self._bad[logits.device] = torch.zeros(1, dtype=torch.int32, device=logits.device)
+        return _SoftCEFn.apply(logits, a, b, lam, self.label_smoothing, self.ignore_index, bad)
+
+    def check_targets(self):
+        """Host check of the device-side flag a label outside [0, C) or a weight outside [0, 1] raises (the loss is NaN from that
+        call on).  Synchronises; resets the flag."""
+        for bad in self._bad.values():
+            if int(bad.item()) != 0:
+                bad.zero_()
+                raise ValueError("MixCrossEntropyLoss: a label was outside [0, num_classes) and not ignore_index, or a weight outside [0, 1]")
+
+    def extra_repr(self):
+        return "label_smoothing=%g, ignore_index=%d" % (self.label_smoothing, self.ignore_index)
 
 
 class HardDice(nn.Module):

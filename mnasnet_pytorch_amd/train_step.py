@@ -517,12 +517,26 @@ class Trainer:
         from .losses import MultiClassBCELoss
         return type(self.criterion) is MultiClassBCELoss
 
+    def _mixce(self):
+        """the criterion is this package's MixCrossEntropyLoss itself (label smoothing, mixed batches); a subclass keeps the module
+        path, as for the other criteria"""
+        from .losses import MixCrossEntropyLoss
+        return type(self.criterion) is MixCrossEntropyLoss
+
+    def _check_target(self, target):
+        """a mixing.MixedTarget goes to a MixCrossEntropyLoss (or a subclass of it) only: refused before anything is launched"""
+        from .losses import MixCrossEntropyLoss
+        from .mixing import MixedTarget
+        if isinstance(target, MixedTarget) and not isinstance(self.criterion, MixCrossEntropyLoss):
+            raise TypeError("a MixedTarget (two labels and a weight per row) needs criterion=MixCrossEntropyLoss(...); %s takes no "
+                            "mixed batch" % type(self.criterion).__name__)
+
     def _check_meters(self, meters):
         """the meters' kind against the criterion's, before anything is launched (the constructor, every forward_backward and
         validate call it: ``criterion`` and ``meters`` are plain attributes)"""
-        from .losses import MultiClassBCELoss
+        from .losses import MixCrossEntropyLoss, MultiClassBCELoss
         from .metrics import MultiLabelMeters
-        if isinstance(meters, MultiLabelMeters) and isinstance(self.criterion, nn.CrossEntropyLoss):
+        if isinstance(meters, MultiLabelMeters) and isinstance(self.criterion, (nn.CrossEntropyLoss, MixCrossEntropyLoss)):
             raise ValueError("MultiLabelMeters count (N, C) multi-label targets; a cross-entropy criterion takes class indices "
                              "(use DeviceMeters)")
         if meters is not None and isinstance(self.criterion, MultiClassBCELoss) and not isinstance(meters, MultiLabelMeters):
@@ -530,7 +544,8 @@ class Trainer:
 
     def _native_head(self):
         """The model's NativeHead when the whole step can bypass autograd: FineTuneModelPool-like model in training mode
-        (fused pool, Dropout/Linear/ReLU classifier) and a plain mean-reduced nn.CrossEntropyLoss (train.py:277).  The features may
+        (fused pool, Dropout/Linear/ReLU classifier) and a plain mean-reduced nn.CrossEntropyLoss (train.py:277), this package's
+        MultiClassBCELoss or its MixCrossEntropyLoss.  The features may
         be entirely in eval mode under a training model (FineTuneModelPool.freeze_bn): forward_backward then runs the engine's
         frozen-statistics program; a subtree in mixed modes is refused by Engine._check_modes."""
         m = self.model
@@ -562,8 +577,9 @@ class Trainer:
         m, c = self.model, self.criterion
         if not self.native_step:
             return None
-        if self._multilabel():
-            pass                   # losses.MultiClassBCELoss: every setting of it is covered (head.NativeHead.bce)
+        if self._multilabel() or self._mixce():
+            pass                   # losses.MultiClassBCELoss / MixCrossEntropyLoss: every setting is covered (head.NativeHead.bce,
+                                   # .cross_entropy_soft)
         elif type(c) is not nn.CrossEntropyLoss:
             return None
         elif c.weight is not None or c.reduction != "mean" or getattr(c, "label_smoothing", 0.0) != 0.0:
@@ -588,7 +604,9 @@ class Trainer:
             dist.broadcast(b, src=0, group=self.buckets.group)
 
     def step(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        """One iteration of train.py:427-440.  Returns the loss tensor (no host sync)."""
+        """One iteration of train.py:427-440.  Returns the loss tensor (no host sync).  ``target``: what the criterion takes -- class
+        indices, an (N, C) label matrix (MultiClassBCELoss) or a mixing.MixedTarget (MixCrossEntropyLoss, on either path)."""
+        self._check_target(target)                           # before zero_grad: a refused target leaves the step untouched
         self.optimizer.zero_grad()                           # train.py:438
         if self.schedule is not None:
             eng = self.engine
@@ -603,7 +621,9 @@ class Trainer:
         """train.py:427-439 without the optimizer: forward, loss, backward INTO the flat gradient buffer (accumulating into what is
         already there: two calls between ``optimizer.zero_grad()`` and ``optimizer.step()`` sum their gradients, which is what
         the world-2 test uses to emulate two data-parallel ranks in one process).  Fires the engine's stage-done callback."""
+        from .mixing import MixedTarget
         self._check_meters(self.meters)                      # before any launch, on either path
+        self._check_target(target)
         head = self._native_head()
         if head is not None:
             # features -> pool -> head -> cross-entropy -> head backward -> features backward as plain launch lists: no
@@ -612,7 +632,7 @@ class Trainer:
             if hasattr(self.model, "_sync_input_norm"):
                 self.model._sync_input_norm()
             eng.check_input(x)                               # same checks as Engine.forward: the launch lists take raw pointers
-            if not isinstance(target, torch.Tensor) or target.device != x.device:
+            if not isinstance(target, (torch.Tensor, MixedTarget)) or target.device != x.device:
                 raise RuntimeError("target must be a tensor on the input's device (%s)" % (x.device,))
             u8 = x.dtype == torch.uint8 and eng._in_norm is not None
             x = x.contiguous() if u8 else x.float().contiguous()
@@ -629,9 +649,9 @@ class Trainer:
                 # input.size(1) for F1 (train.py:447, 454, 463)
                 self.last_logits, loss, df = head.loss_and_grad(f.view(f.size(0), -1), target, meters=self._ml_meters(),
                                                                 criterion=self.criterion, f1_n=x.shape[1])
-            else:
+            else:                                            # (a MixCrossEntropyLoss: its smoothing and a MixedTarget's two labels)
                 self.last_logits, loss, df = head.loss_and_grad(f.view(f.size(0), -1), target, self.criterion.ignore_index,
-                                                                meters=self.meters)
+                                                                meters=self.meters, criterion=self.criterion)
             accumulate = eng.prepare_grads()
             prog.run_backward(df, eng.on_stage_done, static_io=True)
             eng.finish_grads(accumulate)
@@ -642,6 +662,8 @@ class Trainer:
             if self._ml_meters() is not None:
                 if self._label_matrix(out, target):
                     self.meters.update(out.detach(), target, loss.detach(), f1_n=x.shape[1])
+            elif self.meters is not None and isinstance(target, MixedTarget):
+                self.meters.update(out.detach(), target.dominant(), loss.detach())      # the label with the larger weight
             elif self.meters is not None and self._class_vector(out, target):
                 self.meters.update(out.detach(), target, loss.detach())
         return loss.detach()
@@ -669,7 +691,8 @@ class Trainer:
         transforms.DevicePipeline / DeviceTransform over an ImageBatch), the engine's eval-mode forward with the fused pool, the
         native head without dropout, and the cross-entropy kernels that also move ``meters`` (default: a fresh DeviceMeters with
         top-1 / top-5).  With this package's MultiClassBCELoss as the criterion it is the multi-label pass (train.py:575-587): (N, C)
-        targets, the BCE kernels, and a MultiLabelMeters (loss, HardDice(0.5), macro-F1; the default is a fresh one).  Any input shape works: the engine keeps one eval program per shape.  A model or criterion the native head
+        targets, the BCE kernels, and a MultiLabelMeters (loss, HardDice(0.5), macro-F1; the default is a fresh one).  With this package's
+        MixCrossEntropyLoss it is the single-label pass with the smoothed loss, on plain int64 targets.  Any input shape works: the engine keeps one eval program per shape.  A model or criterion the native head
         does not cover runs as ``model(x)`` / ``criterion`` / ``meters.update``.  Distributed trainers broadcast rank 0's
         BatchNorm statistics first and sum the meters over the ranks at the end (``reduce=False``: neither).  The modules'
         train/eval flags are restored on the way out, also when a batch raises.  Returns ``meters.read()``.  The same pass under the
@@ -703,6 +726,9 @@ class Trainer:
                         _, logits = head.forward_layers(f.view(f.size(0), -1), [0] * len(head.layers))   # eval: the seeds are unused
                         if multilabel:                                     # train.py:575-587: weights N, N and input.size(1)
                             head.bce(logits, target, self.criterion, need_grad=False, meters=meters, f1_n=x.shape[1])
+                        elif self._mixce():                                # the smoothed loss on plain class indices
+                            head.cross_entropy_soft(logits, target, self.criterion.label_smoothing, self.criterion.ignore_index,
+                                                    need_grad=False, meters=meters)
                         else:
                             head.cross_entropy(logits, target, self.criterion.ignore_index, need_grad=False, meters=meters)
                     else:
