@@ -494,6 +494,8 @@ int mnas_head_metrics(const void* logits, const void* target, int N, int C, cons
  *     loss_rows[n]  = (1 - eps) (l (lse - z[n][a]) + (1 - l) (lse - z[n][b])) + eps (lse - mean_c z[n][c])
  *     *loss         = sum(loss_rows) / count,   dlogits[n][c] = (softmax(z[n])[c] - q[c]) / count      (NULL: forward only)
  * which is F.cross_entropy(z, a, label_smoothing=eps) and ..(z, b, ..) combined per row as l CE(a) + (1 - l) CE(b).
+ * eps == 0: there is no smoothing term -- a -inf logit at a class that is no label (a masked class) leaves the row's loss finite,
+ * as in mnas_head_cross_entropy; with eps > 0 such a row's loss is +inf (its gradient stays finite).
  * target_b NULL: no mixing (b = a, l = 1; lam is not read).  lam NULL: l = 1 (device fp32 [N] otherwise).
  * A row is ignored when a == ignore_index or, with mixing, b == ignore_index: it contributes 0 and is not counted; count = rows
  * not ignored, 0/0 = NaN.  A label outside [0, C), or an l that is NaN or outside [0, 1], sets *bad_flag (int32, device) and

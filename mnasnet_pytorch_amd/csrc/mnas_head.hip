@@ -515,7 +515,10 @@ __global__ __launch_bounds__(256) void k_head_ce_soft(const float* x, const long
         float r = ignored ? 0.f : NAN;                      // a refused row poisons the loss
         if (valid) {
             const float lse = logf(se) + mx;
-            r = wa * (lse - row[a]) + wb * (lse - row[b]) + eps * (lse - sz / (float)C);
+            // eps == 0: no smoothing term.  A -inf logit at a class that is no label (a masked class) makes sz -inf, and 0 * inf
+            // would poison a row that k_head_ce gives a finite loss; the expression itself is unchanged (0 * 0 adds nothing)
+            const float sm = eps != 0.f ? lse - sz / (float)C : 0.f;
+            r = wa * (lse - row[a]) + wb * (lse - row[b]) + eps * sm;
         }
         loss_rows[n] = r;
     }

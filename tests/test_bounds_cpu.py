@@ -743,3 +743,390 @@ def test_gated_operand_straddle_share_of_the_gpu_tests(shape):
     iv = G.gated_act_interval(yn, s, t, G.gate_nhwc(G.sigmoid_interval(u), yn.shape), bf16=True)
     print("gated operand %s: straddle share %.3g" % (shape, iv.split_share()))
     assert iv.split_share() <= G.MAX_ACT_SPLIT
+
+
+# ---- the fp32 tail of the step: head GEMMs, cross-entropy, optimizers ----------------------------------------------------------------
+# fp32 torch arithmetic in the kernels' operation order; `fused` swaps every multiply-and-add a compiler may contract (and the
+# source's own fmaf) between one rounding (through fp64: a product of two fp32 numbers is exact there) and two.
+def _fma(a, b, c):
+    return (a.double() * b.double() + c.double()).float()
+
+
+def _trunc10(t):
+    return (t.contiguous().view(torch.int32) & ~0x1FFF).view(torch.float32)
+
+
+def emu_head_gemm(A, B, bias=None, C0=None, relu=False, post=None, mask_src=None, fused=True, fault=None):
+    """k_head_gemm: wave w of 8 takes k = 128 t + 16 w + j of every K step t, the eight partial tiles are added in wave order"""
+    M, K = A.shape
+    N = B.shape[1]
+    if fault == "operand_bf16":
+        A, B = bf16r(A), bf16r(B)
+    if fault == "trunc10":
+        A, B = _trunc10(A), _trunc10(B)
+    T = -(-K // 128)
+    Ap, Bp = torch.zeros(M, T * 128), torch.zeros(T * 128, N)
+    Ap[:, :K], Bp[:K] = A, B
+    acc = torch.zeros(8, M, N)
+    for t in range(T):
+        for j in range(16):
+            ks = t * 128 + torch.arange(8) * 16 + j
+            a, b = Ap[:, ks].t()[:, :, None], Bp[ks][:, None, :]
+            acc = _fma(a, b, acc) if fused else acc + a * b
+    v = torch.zeros(M, N)
+    for w in range(8):
+        v = bf16r(v + acc[w]) if fault == "partials_bf16" else v + acc[w]
+    if bias is not None:
+        b = bias.clone()
+        if fault == "bias_missing":
+            b[int(b.abs().argmax())] = 0.0
+        v = v + b
+    if relu:
+        v = torch.relu(v)
+    if post is not None:
+        v = v * post
+    if mask_src is not None:
+        v = v * ((mask_src >= 0) if fault == "mask_ge" else (mask_src > 0))
+    return v if C0 is None else C0 + v
+
+
+def emu_head_rowsum(A, r0=None):
+    M, K = A.shape
+    T = -(-K // 128)
+    Ap = torch.zeros(M, T * 128)
+    Ap[:, :K] = A
+    s = torch.zeros(8, M)
+    for t in range(T):
+        for j in range(0, 16, 4):
+            ks = t * 128 + torch.arange(8)[:, None] * 16 + j + torch.arange(4)[None, :]
+            a = Ap[:, ks]                                        # (M, 8, 4)
+            s = s + ((a[..., 0] + a[..., 1]) + (a[..., 2] + a[..., 3])).t()
+    v = torch.zeros(M)
+    for w in range(8):
+        v = v + s[w]
+    return v if r0 is None else r0 + v
+
+
+def _head_case(N, I, O_, p, scaled):
+    x, w, b, dz, u_prev, c0w, c0b = G.head_inputs(N, I, O_, scaled)
+    keep = (_u((N, I), 99) > 2 * p - 1) if p else torch.ones(N, I, dtype=torch.bool)
+    xd = G.head_dropped(x, keep, p)
+    post = keep * G.head_drop_scale(p) if p else None
+    return x, w, b, dz, u_prev, c0w, c0b, keep, xd, post
+
+
+@pytest.mark.parametrize("scaled", [False, True])
+@pytest.mark.parametrize("N,I,O_", [(5, 512, 10), (130, 70, 65), (1, 1, 1), (1, 129, 1), (33, 128, 33), (32, 127, 32)])
+def test_head_gemm_emulations_inside_bound(N, I, O_, scaled):
+    for p in (0.0, 0.5, 0.999):
+        x, w, b, dz, u_prev, c0w, c0b, keep, xd, post = _head_case(N, I, O_, p, scaled)
+        for fused in (True, False):
+            for relu in (False, True):
+                _ok(G.check_interval(emu_head_gemm(xd, w.t(), b, relu=relu, fused=fused),
+                                     G.head_gemm_interval(xd, w.t(), b, relu=relu), "head fwd", None))
+            _ok(G.check_interval(emu_head_gemm(xd, w.t(), fused=fused), G.head_gemm_interval(xd, w.t()), "head fwd, no bias", None))
+            _ok(G.check_interval(emu_head_gemm(dz.t(), xd, C0=c0w, fused=fused), G.head_gemm_interval(dz.t(), xd, C0=c0w), "head dW", None))
+            mask = u_prev > 0
+            _ok(G.check_interval(emu_head_gemm(dz, w, post=post, mask_src=u_prev, fused=fused),
+                                 G.head_gemm_interval(dz, w, post=post, mask=mask), "head dx", None))
+        _ok(G.check_interval(emu_head_rowsum(dz.t(), c0b), G.head_rowsum_interval(dz.t(), c0b), "head db", None))
+
+
+@pytest.mark.parametrize("fault", ["operand_bf16", "trunc10", "partials_bf16", "bias_missing", "mask_ge"])
+@pytest.mark.parametrize("N,I,O_", [(130, 70, 65), (33, 128, 33)])
+def test_head_gemm_faults_rejected(N, I, O_, fault):
+    x, w, b, dz, u_prev, c0w, c0b, keep, xd, post = _head_case(N, I, O_, 0.2, True)
+    if fault == "mask_ge":
+        iv = G.head_gemm_interval(dz, w, post=post, mask=u_prev > 0)
+        _rejected(lambda: G.check_interval(emu_head_gemm(dz, w, post=post, mask_src=u_prev, fault=fault), iv, "head dx " + fault, None))
+        return
+    iv = G.head_gemm_interval(xd, w.t(), b)
+    _rejected(lambda: G.check_interval(emu_head_gemm(xd, w.t(), b, fault=fault), iv, "head fwd " + fault, None))
+    if fault != "bias_missing":
+        iv = G.head_gemm_interval(dz.t(), xd, C0=c0w)
+        _rejected(lambda: G.check_interval(emu_head_gemm(dz.t(), xd, C0=c0w, fault=fault), iv, "head dW " + fault, None))
+
+
+def test_head_sparse_probe_sees_a_dropped_and_a_doubled_term():
+    N, I, O_ = 130, 133, 131
+    x, w, b, dz, u_prev, c0w, c0b = G.head_inputs(N, I, O_, False)
+    cases = {"fwd": (G.head_sparse(x, 1, I), w.t()), "dW": (G.head_sparse(dz.t(), 1, N), x), "dx": (G.head_sparse(dz, 1, O_), w)}
+    for name, (A, B) in cases.items():
+        iv = G.head_gemm_interval(A, B)
+        G.head_probe_visible(A, B, iv, name)
+        _ok(G.check_interval(emu_head_gemm(A, B), iv, "sparse " + name, None))
+        for k in G.HEAD_LIVE_K(A.shape[1]):
+            for f in (0.0, 2.0):
+                A2 = A.clone()
+                A2[:, k] *= f
+                _rejected(lambda: G.check_interval(emu_head_gemm(A2, B), iv, "sparse %s k %d x%g" % (name, k, f), None))
+    A = G.head_sparse(dz.t(), 1, N)
+    iv = G.head_rowsum_interval(A)
+    _ok(G.check_interval(emu_head_rowsum(A), iv, "sparse db", None))
+    for k in G.HEAD_LIVE_K(N):
+        A2 = A.clone()
+        A2[:, k] = 0
+        _rejected(lambda: G.check_interval(emu_head_rowsum(A2), iv, "sparse db k %d dropped" % k, None))
+
+
+def _wg_sum(v):
+    """head_wg_reduce over the last dimension: lane t of 256 adds elements t, t + 256, ... in order, a 64-lane xor butterfly, then
+    ((w0 + w1) + w2) + w3"""
+    n = v.shape[-1]
+    T = -(-n // 256)
+    pad = torch.zeros(v.shape[:-1] + (T * 256,), dtype=v.dtype)
+    pad[..., :n] = v
+    pad = pad.view(v.shape[:-1] + (T, 256))
+    s = torch.zeros(v.shape[:-1] + (256,), dtype=v.dtype)
+    for t in range(T):
+        s = s + pad[..., t, :]
+    s = s.view(v.shape[:-1] + (4, 64))
+    lane = torch.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        s = s + s[..., lane ^ o]
+    r = s[..., 0]
+    return ((r[..., 0] + r[..., 1]) + r[..., 2]) + r[..., 3]
+
+
+def emu_ce(x, ta, tb=None, lam=None, eps=None, fused=False, fault=None, ignore_index=-100):
+    """k_head_ce (eps None) / k_head_ce_soft and their mean stage -> (dlogits, loss_rows, loss)"""
+    N, Cn = x.shape
+    b = ta if tb is None else tb
+    l = torch.ones(N) if (tb is None or lam is None) else lam.float()
+    ignored = (ta == ignore_index) | (b == ignore_index)
+    cnt = (~ignored).float().sum()
+    a0, b0 = torch.where(ignored, torch.zeros_like(ta), ta), torch.where(ignored, torch.zeros_like(b), b)
+    rowi = torch.arange(N)
+    mx = x.max(1, keepdim=True).values
+    e = torch.exp(x - mx)
+    es = e.clone()
+    if fault == "se_skips_last" and Cn % 256 == 1:
+        es[:, -1] = 0.0
+    se = _wg_sum(es)[:, None]
+    rse = 1.0 / se
+    inv = torch.where(ignored, torch.zeros(N), 1.0 / (torch.tensor(float(N)) if fault == "grad_div_N" else cnt))[:, None]
+    ep = torch.tensor(0.0 if eps is None else eps, dtype=torch.float32)
+    same = ta == b
+    if eps is None:
+        wa, wb, u = torch.ones(N), torch.zeros(N), torch.tensor(0.0)
+    else:
+        ome = 1.0 - ep
+        wa = torch.where(same, ome.expand(N), ome * l)
+        wb = torch.where(same, torch.zeros(N), _fma(-ome.expand(N), l, ome.expand(N)) if fused else ome - wa)
+        if fault == "wb_on_same":
+            wb = torch.where(same, ome * (1.0 - l), wb)
+        u = ep / float(Cn)
+    qa, qb = torch.zeros(N, Cn), torch.zeros(N, Cn)
+    qa[rowi, a0] = wa
+    nb = ~same if fault != "wb_on_same" else torch.ones(N, dtype=torch.bool)
+    qb[rowi[nb], b0[nb]] = wb[nb]
+    q = (qa + qb) + u
+    if fault == "u_missing_at_labels":
+        q[rowi, a0] = (qa + qb)[rowi, a0]
+        q[rowi, b0] = (qa + qb)[rowi, b0]
+    if fault == "p_bf16":
+        d = bf16r(e * rse) - q
+    else:
+        d = _fma(e, rse.expand_as(e), -q) if fused else e * rse - q
+    dl = torch.where(ignored[:, None], torch.zeros(N, Cn), d * inv)
+    lse = torch.log(se[:, 0]) + mx[:, 0]
+    za, zb = x[rowi, a0], x[rowi, b0]
+    if eps is None:
+        rows = lse - za
+    else:
+        t1, t2 = lse - za, lse - zb
+        r = _fma(wb, t2, wa * t1) if fused else wa * t1 + wb * t2
+        if float(ep) != 0.0:
+            t3 = lse - _wg_sum(x) / float(Cn)
+            r = _fma(ep.expand(N), t3, r) if fused else r + ep * t3
+        rows = r
+    rows = torch.where(ignored, torch.zeros(N), rows)
+    loss = _wg_sum(rows) / (torch.tensor(float(N)) if fault == "mean_over_N" else cnt)
+    return dl, rows, loss
+
+
+def _ce_check(x, ta, tb, lam, eps, fused=False, fault=None):
+    dl, rows, loss = emu_ce(x, ta, tb, lam, eps, fused, fault)
+    iv = G.ce_intervals(x, ta, tb, lam, eps)
+    r = [G.check_iv(dl, iv["dl"], "ce dlogits", None), G.check_iv(rows, iv["rows"], "ce loss rows", None)]
+    r.append(G.check_ce_mean(loss, rows, iv["count"], "ce mean", None))
+    if iv["count"] == 0:
+        assert bool((dl == 0).all())
+    return max(r)
+
+
+def _soft_args(N, Cn, how):
+    a, b = G.ce_targets(N, Cn)
+    lam = torch.tensor([0.0, 0.5, 1.0, 0.3, 0.8125, 0.49999997])[torch.arange(N) % 6]
+    b = torch.where(torch.arange(N) % 4 == 1, a, b)                      # rows with a == b among the others
+    return G.ce_ignore(a, how), b, lam
+
+
+@pytest.mark.parametrize("N,Cn", G.CE_SIZES)
+def test_cross_entropy_emulations_inside_bracket(N, Cn):
+    worst = 0.0
+    for i, kind in enumerate(G.CE_ROWS):
+        x = G.ce_logits(kind, N, Cn)
+        for how in (G.CE_IGNORE if N * Cn <= 10000 else G.CE_IGNORE[i % 4:i % 4 + 1]):
+            a, b, lam = _soft_args(N, Cn, how)
+            for fused in (False, True):
+                worst = max(worst, _ce_check(x, a, None, None, None, fused))
+                for eps in (0.0, 0.1, 1.0):
+                    worst = max(worst, _ce_check(x, a, b, lam, eps, fused), _ce_check(x, a, None, None, eps, fused))
+    print("N %d C %d: worst emulation / bracket %.3f" % (N, Cn, worst))
+    assert worst <= 1.0
+
+
+@pytest.mark.parametrize("fault,N,Cn,how,eps", [("grad_div_N", 257, 10, "third", None), ("grad_div_N", 7, 255, "all_but_one", 0.1),
+                                                ("mean_over_N", 257, 10, "third", None), ("mean_over_N", 7, 255, "third", 0.1),
+                                                ("u_missing_at_labels", 7, 255, "none", 0.1), ("u_missing_at_labels", 257, 10, "third", 1.0),
+                                                ("se_skips_last", 7, 513, "none", None), ("se_skips_last", 7, 513, "none", 0.1),
+                                                ("p_bf16", 7, 256, "none", None), ("p_bf16", 257, 10, "third", 0.1),
+                                                ("wb_on_same", 7, 255, "none", 0.1), ("wb_on_same", 257, 10, "third", 0.0)])
+def test_cross_entropy_faults_rejected(fault, N, Cn, how, eps):
+    """wb_on_same: the label of a row with a == b gets wa = 1 - eps AND a share wb on top.  (The milder variant -- such a row
+    treated as any other, two rounded shares that add up to 1 - eps within one ulp -- moves q by at most u and lies inside any
+    bracket that allows the kernel's own roundings of p - q: it cannot be separated and is not claimed.)"""
+    x = G.ce_logits("uniform4", N, Cn)
+    a, b, lam = _soft_args(N, Cn, how)
+    tb, l = (None, None) if eps is None else (b, lam)
+    _ok(_ce_check(x, a, tb, l, eps))
+    _rejected(lambda: _ce_check(x, a, tb, l, eps, fault=fault))
+
+
+def _opt_state(n):
+    return G.opt_data(n, seed=n)
+
+
+def emu_adam(p, g, m, v, lr, b1, b2, eps, wd, step, gscale, coef=None, fused=False, fault=None):
+    f = lambda c: torch.tensor(c, dtype=torch.float32)
+    lr, b1, b2, eps, wd, gscale = (f(c) for c in (lr, b1, b2, eps, wd, gscale))
+    bc1, bc2s = (f(c) for c in G.adam_bias(float(b1), float(b2), step))
+    gi = g * gscale
+    if coef is not None:
+        gi = gi * f(coef)
+    if float(wd) != 0.0 and fault != "decoupled_wd":
+        gi = _fma(wd.expand_as(p), p, gi)
+    mi = _fma(b1.expand_as(m), m, (1.0 - b1) * gi)
+    gv = gi * gscale if fault == "gscale_twice_v" else gi
+    vi = _fma(b2.expand_as(v), v, (1.0 - b2) * gv * gv)
+    if fault == "v_bf16":
+        vi = bf16r(vi)
+    if fault == "eps_in_sqrt":
+        denom = torch.sqrt(vi + eps) / bc2s
+    elif fault == "no_bc2":
+        denom = torch.sqrt(vi) + eps
+    else:
+        denom = torch.sqrt(vi) / bc2s + eps
+    ss, r = lr / bc1, mi / denom
+    pn = _fma(-ss.expand_as(p), r, p) if fused else p - ss * r
+    if fault == "decoupled_wd":
+        pn = pn - lr * wd * p
+    return dict(p=pn, m=mi, v=vi)
+
+
+def emu_rmsprop(p, g, sq, buf, lr, alpha, eps, wd, momentum, gscale, fused=False, fault=None):
+    f = lambda c: torch.tensor(c, dtype=torch.float32)
+    lr, alpha, eps, wd, momentum, gscale = (f(c) for c in (lr, alpha, eps, wd, momentum, gscale))
+    gi = g * gscale
+    if float(wd) != 0.0:
+        gi = _fma(wd.expand_as(p), p, gi)
+    s = _fma(alpha.expand_as(sq), sq, (1.0 - alpha) * gi * gi)
+    if fault == "v_bf16":
+        s = bf16r(s)
+    avg = torch.sqrt(s + eps) if fault == "eps_in_sqrt" else torch.sqrt(s) + eps
+    r = gi / avg
+    out = dict(sq=s)
+    if float(momentum) > 0:
+        r = _fma(momentum.expand_as(buf), buf, r)
+        out["buf"] = r
+    out["p"] = _fma(-lr.expand_as(p), r, p) if fused else p - lr * r
+    return out
+
+
+def emu_sgd(p, g, buf, lr, momentum, dampening, wd, nesterov, step, gscale, fused=False, fault=None):
+    f = lambda c: torch.tensor(c, dtype=torch.float32)
+    lr, momentum, dampening, wd, gscale = (f(c) for c in (lr, momentum, dampening, wd, gscale))
+    gi = g * gscale
+    if float(wd) != 0.0:
+        gi = _fma(wd.expand_as(p), p, gi)
+    out = {}
+    if float(momentum) != 0.0:
+        if step == 1 and fault != "damp_first":
+            b = gi
+        elif step == 1:
+            b = (1.0 - dampening) * gi
+        else:
+            b = _fma(momentum.expand_as(buf), buf, (1.0 - dampening) * gi)
+        out["buf"] = b
+        gi = _fma(momentum.expand_as(b), b, gi) if (nesterov and fault != "no_nesterov") else b
+    out["p"] = _fma(-lr.expand_as(p), gi, p) if fused else p - lr * gi
+    return out
+
+
+def _opt_check(got, ivs, what):
+    return max(_ok(G.check_interval(got[k], ivs[k], "%s %s" % (what, k), None)) for k in ivs)
+
+
+ADAM = dict(lr=1e-3, b1=0.9, b2=0.999, eps=1e-8)
+
+
+@pytest.mark.parametrize("n", [1, 255, 257])
+def test_optimizer_emulations_inside_bracket(n):
+    p, g, m, v, buf = _opt_state(n)
+    for fused in (False, True):
+        for step in (1, 2, 1000, 100000):
+            for wd in (0.0, 1e-2):
+                for gs in (1.0, 0.125, 1.0 / 3):
+                    _opt_check(emu_adam(p, g, m, v, wd=wd, step=step, gscale=gs, fused=fused, **ADAM),
+                               G.adam_intervals(p, g, m, v, wd=wd, step=step, gscale=gs, **ADAM), "adam")
+        _opt_check(emu_adam(p, g, m, v, wd=1e-2, step=2, gscale=0.125, coef=0.37, fused=fused, **ADAM),
+                   G.adam_intervals(p, g, m, v, wd=1e-2, step=2, gscale=0.125, coef=G._iv(G.f32(0.37)), **ADAM), "adam_ex")
+        for mom in (0.0, 0.9):
+            for wd in (0.0, 1e-2):
+                a = dict(lr=1e-2, alpha=0.99, eps=1e-8, wd=wd, momentum=mom, gscale=1.0 / 3)
+                _opt_check(emu_rmsprop(p, g, v, buf, fused=fused, **a), G.rmsprop_intervals(p, g, v, buf, **a), "rmsprop")
+            for damp in (0.0, 0.5):
+                for nest in (0, 1):
+                    for step in (1, 2):
+                        if nest and (mom == 0.0 or damp != 0.0):
+                            continue
+                        a = dict(lr=1e-2, momentum=mom, dampening=damp, wd=1e-2, nesterov=nest, step=step, gscale=0.125)
+                        _opt_check(emu_sgd(p, g, buf, fused=fused, **a), G.sgd_intervals(p, g, buf, **a), "sgd")
+
+
+@pytest.mark.parametrize("n", [255, 257])
+@pytest.mark.parametrize("fault", ["v_bf16", "eps_in_sqrt", "no_bc2", "decoupled_wd", "gscale_twice_v"])
+def test_adam_and_rmsprop_faults_rejected(n, fault):
+    p, g, m, v, buf = _opt_state(n)
+    a = dict(wd=1e-2, step=2, gscale=0.125, **ADAM)
+    iv = G.adam_intervals(p, g, m, v, **a)
+    _rejected(lambda: _opt_check(emu_adam(p, g, m, v, fault=fault, **a), iv, "adam " + fault))
+    if fault in ("v_bf16", "eps_in_sqrt"):
+        a = dict(lr=1e-2, alpha=0.99, eps=1e-8, wd=0.0, momentum=0.9, gscale=1.0)
+        iv = G.rmsprop_intervals(p, g, v, buf, **a)
+        _rejected(lambda: _opt_check(emu_rmsprop(p, g, v, buf, fault=fault, **a), iv, "rmsprop " + fault))
+
+
+@pytest.mark.parametrize("n", [255, 257])
+@pytest.mark.parametrize("fault,step", [("damp_first", 1), ("no_nesterov", 1), ("no_nesterov", 2)])
+def test_sgd_faults_rejected(n, fault, step):
+    p, g, m, v, buf = _opt_state(n)
+    nest = fault == "no_nesterov"
+    a = dict(lr=1e-2, momentum=0.9, dampening=0.0 if nest else 0.5, wd=0.0, nesterov=int(nest), step=step, gscale=1.0)
+    iv = G.sgd_intervals(p, g, buf, **a)
+    _opt_check(emu_sgd(p, g, buf, **a), iv, "sgd")
+    _rejected(lambda: _opt_check(emu_sgd(p, g, buf, fault=fault, **a), iv, "sgd " + fault))
+
+
+def test_ema_bound_and_the_old_p_fault():
+    p, g, m, v, buf = _opt_state(257)
+    ema = p * 0.9 + 0.01
+    pn = emu_sgd(p, g, buf, lr=1e-2, momentum=0.0, dampening=0.0, wd=0.0, nesterov=0, step=1, gscale=1.0)["p"]
+    for d in (0.0, 0.999):
+        dd = torch.tensor(d, dtype=torch.float32)
+        for fused in (False, True):
+            got = _fma(dd.expand_as(ema), ema, (1.0 - dd) * pn) if fused else dd * ema + (1.0 - dd) * pn
+            _ok(G.check_ema(got, d, ema, pn, "ema", None))
+        old = dd * ema + (1.0 - dd) * p
+        _rejected(lambda: G.check_ema(old, d, ema, pn, "ema from the old p", None))

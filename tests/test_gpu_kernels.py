@@ -685,6 +685,42 @@ def test_adam_matches_torch():
     assert relerr(pd.cpu(), p.detach()) < 1e-5
 
 
+def _opt_state(n):
+    import gpu_util as G
+    p, g, m, v, buf = G.opt_data(n, seed=n)
+    return dict(p=p, g=g, m=m, v=v, buf=buf)
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 10007, 2048 * 256 + 300])
+def test_optimizer_per_element_bracket(n):
+    """ONE launch of mnas_adam_step / mnas_rmsprop_step / mnas_sgd_step from a given non-zero state (gpu_util.opt_case): every
+    element of every output inside the bracket propagated through the kernel's own roundings, with per-element scales 2^-20 .. 2^4
+    in p and g, exact zeros, elements with v = 0 and g = 0 (denom = eps) and with a tiny v; the runs start at element offsets 0, 1
+    and 3 of guarded buffers.  The last size exceeds opt_blocks' grid of 2048 workgroups of 256, so a lane takes the grid-stride
+    loop's second trip.  Adam: step 1 / 2 / 1000 / 100000, weight decay, grad_scale 1, 1/8, 1/3; RMSprop with and without momentum;
+    SGD with momentum, dampening, Nesterov, first and second step."""
+    import gpu_util as G
+    assert G.OPT_SIZES[-1] > G.OPT_GRID_CAP == 2048 * 256 and n in G.OPT_SIZES
+    st = _opt_state(n)
+    worst, k = 0.0, 0
+    for step in (1, 2, 1000, 100000):
+        for wd in (0.0, 1e-2):
+            for gs in (1.0, 0.125, 1.0 / 3):
+                a = dict(lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, wd=wd, step=step, gscale=gs)
+                worst, k = max(worst, G.opt_case("adam", st, a, (0, 1, 3)[k % 3])), k + 1
+    for mom in (0.0, 0.9):
+        for wd in (0.0, 1e-2):
+            a = dict(lr=1e-2, alpha=0.99, eps=1e-8, wd=wd, momentum=mom, gscale=1.0 / 3)
+            worst, k = max(worst, G.opt_case("rmsprop", st, a, (0, 1, 3)[k % 3])), k + 1
+        for damp in (0.0, 0.5):
+            for nest in (0, 1):
+                for step in (1, 2):
+                    a = dict(lr=1e-2, momentum=mom, dampening=damp, wd=1e-2 * nest, nesterov=nest, step=step, gscale=0.125)
+                    worst, k = max(worst, G.opt_case("sgd", st, a, (0, 1, 3)[k % 3])), k + 1
+    print("optimizers n %d: %d launches, worst error / bracket %.4f" % (n, k, worst), {"optimizers": G.WORST.get("optimizers")})
+    assert worst <= 1.0
+
+
 def test_run_ops_batch():
     """The batched launcher reproduces the individual calls (pack -> pw fwd -> bn finalize)."""
     lib = L.load()

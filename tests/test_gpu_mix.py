@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 import cases as C
+import gpu_util as G
 import metrics_ref as MR
 import mix_ref as R
 from cases import O
@@ -158,6 +159,90 @@ def test_soft_cross_entropy_meters_rank_the_dominant_label(eps):
     print(rec)
     log.check(rec)
     assert 0 < rec.correct[1] < rec.correct[5] < rec.samples
+
+
+# ---- per-element brackets (gpu_util.ce_intervals: interval propagation through k_head_ce_soft's own roundings) ----------------------
+def _lam_variants(N):
+    i = torch.arange(N)
+    per_row = torch.tensor([0.0, 0.5, 1.0, 0.3, 0.8125, 0.49999997])[i % 6]
+    out = [("lam %g" % v, True, torch.full((N,), v)) for v in (0.0, 1.0, 0.5, 0.3)]
+    return out + [("lam per row", True, per_row), ("tb null", False, None), ("lam null", True, None)]
+
+
+def _soft_labels(N, Cn, how):
+    a, b = G.ce_targets(N, Cn)
+    b = torch.where(torch.arange(N) % 4 == 1, a, b)                  # rows with a == b among the others
+    return G.ce_ignore(a, how), b
+
+
+def _plain(z, t):
+    N, Cn = z.shape
+    rows, loss = torch.empty(N, device="cuda"), torch.empty((), device="cuda")
+    dl = torch.full((N, Cn), float("nan"), device="cuda")
+    bad = torch.zeros(1, dtype=torch.int32, device="cuda")
+    L.check(L.load().mnas_head_cross_entropy(z.data_ptr(), t.data_ptr(), N, Cn, -100, rows.data_ptr(), loss.data_ptr(), dl.data_ptr(),
+                                             bad.data_ptr(), L.cur_stream()))
+    return rows.cpu(), dl.cpu(), loss.cpu()
+
+
+@pytest.mark.parametrize("N,Cn", G.CE_SIZES)
+def test_soft_cross_entropy_per_element_bracket(N, Cn):
+    """EVERY dlogits element, every loss row and the mean of k_head_ce_soft inside gpu_util.ce_intervals' bracket: eps 0 / 0.1 / 1
+    x lam 0 / 1 / 0.5 / 0.3 / per row / tb NULL / lam NULL for every kind of logit row and every way of ignoring rows (at
+    N C > 10000 the way rows are ignored cycles over the 21 settings instead), rows with a == b in every batch; the same call
+    with meters gives the same bits."""
+    from mnasnet_pytorch_amd.metrics import DeviceMeters
+    meters = DeviceMeters((1, 5))
+    ce = _Soft(N, Cn)
+    settings = [(eps, v) for eps in (0.0, 0.1, 1.0) for v in _lam_variants(N)]
+    if N * Cn > 10000:
+        runs = [(k, G.CE_IGNORE[(i + j) % 4], s) for i, k in enumerate(G.CE_ROWS) for j, s in enumerate(settings)]
+    else:
+        runs = [(k, h, s) for k in G.CE_ROWS for h in G.CE_IGNORE for s in settings]
+    worst = 0.0
+    for kind, how, (eps, (name, mixing, lam)) in runs:
+        z = G.ce_logits(kind, N, Cn)
+        a, b = _soft_labels(N, Cn, how)
+        b = b if mixing else None
+        what = "soft ce %s / %s / eps %g / %s (%d, %d)" % (kind, how, eps, name, N, Cn)
+        dev = [None if t is None else t.cuda() for t in (a, b, lam)]
+        loss, dl, bad = ce.run(z.cuda(), *dev, eps)
+        rows, loss_t = ce.rows.cpu(), ce.loss.cpu()
+        iv = G.ce_intervals(z, a, b, lam, eps)
+        assert bad == 0, what
+        assert bool((dl[~iv["valid"]] == 0).all()) and bool((rows[~iv["valid"]] == 0).all()), what
+        r = [G.check_iv(dl, iv["dl"], what + " dlogits", "soft cross-entropy"), G.check_iv(rows, iv["rows"], what + " rows", "soft cross-entropy"),
+             G.check_ce_mean(loss_t, rows, iv["count"], what + " mean", "cross-entropy mean")]
+        if iv["count"] == 0:
+            assert loss != loss and bool((dl == 0).all()), what
+        worst = max(worst, *r)
+        loss2, dl2, bad2 = ce.run(z.cuda(), *dev, eps, meters=meters)
+        G.bits_equal(dl2, dl, what + " dlogits with meters")
+        G.bits_equal(ce.rows.cpu(), rows, what + " rows with meters")
+        G.bits_equal(ce.loss.cpu(), loss_t, what + " loss with meters")
+    print("soft cross-entropy (%d, %d): %d runs, worst error / bracket %.3f" % (N, Cn, len(runs), worst),
+          {k: round(v, 4) for k, v in G.WORST.items() if "entropy" in k})
+    assert worst <= 1.0
+
+
+@pytest.mark.parametrize("N,Cn", G.CE_SIZES)
+def test_soft_cross_entropy_without_smoothing_is_the_plain_kernel(N, Cn):
+    """eps = 0, tb NULL: loss_rows, dlogits and the mean equal k_head_ce's bit for bit -- for finite logits, and for rows with
+    -inf at classes that are not labels (a masked class): without smoothing such a row has the plain kernel's finite loss."""
+    ce = _Soft(N, Cn)
+    for kind in G.CE_ROWS:
+        z = G.ce_logits(kind, N, Cn).cuda()
+        for how in G.CE_IGNORE:
+            t = G.ce_ignore(G.ce_targets(N, Cn)[0], how).cuda()
+            rows_p, dl_p, loss_p = _plain(z, t)
+            loss, dl, bad = ce.run(z, t, None, None, 0.0)
+            what = "%s / %s (%d, %d)" % (kind, how, N, Cn)
+            assert bad == 0, what
+            G.bits_equal(ce.rows.cpu(), rows_p, what + " loss rows")
+            G.bits_equal(dl, dl_p, what + " dlogits")
+            G.bits_equal(ce.loss.cpu(), loss_p, what + " loss")
+            if int((t != -100).sum()) > 0:
+                assert bool(torch.isfinite(loss_p)) and bool(torch.isfinite(rows_p).all()), what
 
 
 # ---- the mix kernel ----------------------------------------------------------------------------------------------------------------
