@@ -569,7 +569,10 @@ typedef struct MnasMultiLabelMeters {
 } MnasMultiLabelMeters;
 /* All calls: stream-ordered, no allocation, no host read of device memory, no float atomics (results do not depend on the run),
  * capturable in a hipGraph.  scratch: mnas_mlabel_scratch_bytes(N) bytes of device memory, 16-byte aligned, owned by the call until
- * it has run.  Zero the block (hipMemsetAsync) to reset it.  The meters' Dice threshold is 0.5 without deduct_intersection
+ * it has run.  Its layout after a call (24 N + 16 bytes; the tests read the row sums and s from it): double f1_rows[N] at byte 0,
+ * float loss_rows[N] (the sum of each row's loss elements, mnas_mlabel_bce only) at byte 8 N, int cI[N], cP[N], cT[N] (the Dice
+ * rule's counts per row) at bytes 12 N, 16 N and 20 N, and one float `scale` (focal: the gradient's factor s) at byte 24 N.
+ * Zero the block (hipMemsetAsync) to reset it.  The meters' Dice threshold is 0.5 without deduct_intersection
  * (train.py:279).  n_loss / n_dice / n_f1: the weights of the three meters (train.py:447-463: N, N and the number of classes).
  *   mnas_mlabel_bce       : *loss (device fp32) and dlogits (NULL: forward only); weights NULL: none; focal != 0: the focal
  *                           transform with focus_param (>= 1) and balance_param.  meters != NULL: the same launches also update the

@@ -3,6 +3,7 @@
 condition of the helpers met; the same emulation with one fault -- a precision loss or a dropped / misplaced term of the kind an
 optimisation of the kernels can introduce -- must be rejected.  Nothing here touches a kernel: the faults live in the emulation.
 Shapes and input distributions are those of tests/test_gpu_kernels.py (5x5 depthwise 3x14x14x96, 1x1 600 pixels 96 -> 40)."""
+import numpy as np
 import pytest
 import torch
 
@@ -1130,3 +1131,196 @@ def test_ema_bound_and_the_old_p_fault():
             _ok(G.check_ema(got, d, ema, pn, "ema", None))
         old = dd * ema + (1.0 - dd) * p
         _rejected(lambda: G.check_ema(old, d, ema, pn, "ema from the old p", None))
+
+
+# ---- the multi-label loss and HardDice (csrc/mnas_mlabel.hip) ---------------------------------------------------------------------------
+# A numpy float32 emulation of k_mlabel_row in the kernel's lane order (scalar: lane l adds l, l + 256, ...; vector: the quads at
+# 4 l + 1024 k, x y z w in turn), the 64-lane butterfly, ((w0 + w1) + w2) + w3; `fused` swaps `- z*t +` and `ls += e*w` between one
+# rounding (through fp64: the product of two fp32 numbers is exact there) and two; the batch stage and the focal transform in
+# float64, k_mlabel_scale as one fp32 product.
+F32, F64 = np.float32, np.float64
+ML_CAP = 4096 * 256
+
+
+def _ml_order(C_, vec):
+    T = G.mlabel_trips(C_, vec)
+    k, l = np.arange(T)[:, None], np.arange(256)[None, :]
+    idx = 1024 * (k // 4) + 4 * l + k % 4 if vec else 256 * k + l
+    return np.where(idx < C_, idx, -1)
+
+
+def emu_mlabel(z, t, w, focal, gamma, balance, vec, fused, fault=None):
+    """-> dict(dl, rows, loss, s) of torch tensors; every `fault` is one of the issue's list"""
+    z, t = z.numpy().astype(F32), t.numpy().astype(F32)
+    N, C_ = z.shape
+    ww = np.ones_like(z) if w is None else w.numpy().astype(F32)
+    with np.errstate(over="ignore", under="ignore"):
+        ea = np.exp(-np.abs(z))
+        l1 = np.log(F32(1) + ea) if fault == "log_not_log1p" else np.log1p(ea)
+        m = np.maximum(z, F32(0))
+        A = (m.astype(F64) - z.astype(F64) * t.astype(F64)).astype(F32) if fused else m - z * t
+        e = A + l1
+        d = F32(1) + ea
+        if fault == "other_sigmoid":
+            sg = F32(1) / (F32(1) + np.exp(-z))
+        else:
+            sg = np.where(z >= 0, F32(1) / d, ea / d)
+        inv = F32(1.0 / float(N)) if fault == "inv_N" else F32(G.mlabel_inv(N, C_))
+        df = sg - t
+        dl = (ww * (ww * df)) * inv if fault == "w_twice" else df * inv if fault == "w_none" else (ww * df) * inv
+    es, ws = e.copy(), ww
+    if fault == "last_elem_dropped":
+        es[:, -1] = 0
+    if fault == "last_quad_dropped":
+        es[:, -4:] = 0
+    ls = np.zeros((N, 256), F32)
+    for row in _ml_order(C_, vec):
+        ok, ii = row >= 0, np.clip(row, 0, None)
+        ev, wv = es[:, ii], ws[:, ii]
+        new = (ls.astype(F64) + ev.astype(F64) * wv.astype(F64)).astype(F32) if fused else ls + ev * wv
+        ls = np.where(ok[None, :], new, ls)
+    s_ = ls.reshape(N, 4, 64)
+    lane = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        s_ = s_ + s_[..., lane ^ o]
+    r = s_[..., 0]
+    rows = (r[:, 0] + r[:, 1]) + r[:, 3] if fault == "skip_wave" else ((r[:, 0] + r[:, 1]) + r[:, 2]) + r[:, 3]
+    b = F32(rows.astype(F64).sum() / (float(N) if fault == "mean_N" else float(N) * float(C_)))
+    loss, s = b, None
+    if focal:
+        bd, g, bal = F64(b), F64(F32(gamma)), F64(F32(balance))
+        pt = np.exp(-bd)
+        om = 1.0 - pt
+        loss = F32(bal * np.power(om, g) * bd)
+        s = F32(bal * np.power(om, g if fault == "focal_gamma_exp" else g - 1.0) * (om + g * pt * bd))
+        flat = dl.reshape(-1)
+        sc = flat * s
+        if fault == "scale_none_beyond":
+            sc[ML_CAP:] = flat[ML_CAP:]
+        if fault == "scale_twice_beyond":
+            sc[ML_CAP:] = sc[ML_CAP:] * s
+        dl = sc.reshape(N, C_)
+    tt = lambda v: None if v is None else torch.from_numpy(np.asarray(v, dtype=F32))
+    return dict(dl=tt(dl), rows=tt(rows), loss=tt(loss), s=tt(s))
+
+
+def _ml_check(z, t, w, focal, gamma, balance, vec, fused=False, fault=None, only=None):
+    got = emu_mlabel(z, t, w, focal, gamma, balance, vec, fused, fault)
+    N, C_ = z.shape
+    iv = G.mlabel_intervals(z, t, w, N, C_, focal, gamma, balance, vec, rows_dev=got["rows"])
+    r = 0.0
+    for k in ("dl", "rows", "loss", "s"):
+        if got[k] is not None and (only is None or k in only):
+            r = max(r, G.check_iv(got[k], iv[k], "mlabel " + k, None))
+    return r
+
+
+ML_VARIANTS = (("plain", False, False), ("weighted", True, False), ("focal", False, True), ("weighted_focal", True, True))
+
+
+@pytest.mark.parametrize("N,Cn", G.ML_SHAPES)
+def test_mlabel_emulations_inside_bracket(N, Cn):
+    worst = 0.0
+    for ki, kind in enumerate(G.ML_KINDS):
+        z, t, w = G.mlabel_inputs(kind, N, Cn)
+        gamma, balance = G.ML_FOCAL[ki % 3]
+        for name, weighted, focal in ML_VARIANTS:
+            for vec in ((False, True) if Cn % 4 == 0 else (False,)):
+                for fused in (False, True):
+                    worst = max(worst, _ml_check(z, t, w if weighted else None, focal, gamma, balance, vec, fused))
+        if kind == "sparse":
+            G.mlabel_probe_visible(G.mlabel_intervals(z, t, w, N, Cn, False, 2.0, 0.25, Cn % 4 == 0), G.mlabel_live(N, Cn), "sparse")
+    print("N %d C %d: worst emulation / bracket %.3f" % (N, Cn, worst))
+    assert worst <= 1.0
+
+
+@pytest.mark.parametrize("fault,N,Cn,kind,weighted,focal,vec,only", [
+    ("last_elem_dropped", 3, 1027, "scale8", True, False, False, "rows"), ("last_elem_dropped", 2, 1000, "scale0.5", False, True, False, "rows"),
+    ("last_quad_dropped", 3, 1028, "scale8", True, False, True, "rows"), ("last_quad_dropped", 2, 2052, "scale0.5", False, False, True, "rows"),
+    ("w_twice", 5, 257, "scale0.5", True, False, False, "dl"), ("w_twice", 3, 1024, "pow2w", True, True, True, "dl"),
+    ("w_none", 5, 257, "scale0.5", True, False, False, "dl"), ("w_none", 3, 1024, "pow2w", True, True, True, "dl"),
+    ("inv_N", 3, 5, "scale8", False, False, False, "dl"), ("inv_N", 513, 4, "scale30", True, True, True, "dl"),
+    ("log_not_log1p", 2, 1000, "confident", False, False, True, "rows"), ("log_not_log1p", 3, 1027, "confident", True, True, False, "rows"),
+    ("other_sigmoid", 3, 5, "edges", False, False, False, "dl"), ("other_sigmoid", 2, 1000, "edges", True, False, True, "dl"),
+    ("focal_gamma_exp", 3, 5, "scale0.5", False, True, False, "s"), ("focal_gamma_exp", 2, 1000, "scale8", True, True, True, "dl"),
+    ("skip_wave", 2, 1000, "scale8", False, False, True, "rows"), ("skip_wave", 3, 1027, "scale0.5", True, False, False, "rows"),
+    ("mean_N", 3, 5, "scale8", False, False, False, "loss"), ("mean_N", 257, 3, "scale0.5", True, True, False, "loss")])
+def test_mlabel_faults_rejected(fault, N, Cn, kind, weighted, focal, vec, only):
+    """each fault on the inputs of tests/test_gpu_multilabel.py::test_bounds; `only`: the output that must show it.  log_not_log1p
+    on the confident batch gives rows of exactly 0, which also pass every max-normalised tolerance.  other_sigmoid:
+    1 / (1 + expf(-z)) at z = -90 is 1 / inf = 0 where ea / (1 + ea) is 8.2e-40."""
+    z, t, w = G.mlabel_inputs(kind, N, Cn)
+    gamma, balance = G.ML_FOCAL[1]
+    for fused in (False, True):
+        _ok(_ml_check(z, t, w if weighted else None, focal, gamma, balance, vec, fused))
+        _rejected(lambda: _ml_check(z, t, w if weighted else None, focal, gamma, balance, vec, fused, fault, only=(only,)))
+
+
+def test_mlabel_confident_focal_smallest_b():
+    """the confident batch under focal at gamma 1, 2 and 3.5: 1 - exp(-b) cancels, the bracket of the loss and of s widens to
+    about 2^-52 / b relative and still admits the emulation; prints the smallest b and the bracket's relative width there"""
+    small = (1.0, 0.0)
+    for (N, Cn) in ((2, 1000), (3, 1027)):
+        z, t, w = G.mlabel_inputs("confident", N, Cn)
+        for gamma, balance in G.ML_FOCAL:
+            got = emu_mlabel(z, t, None, True, gamma, balance, Cn % 4 == 0, False)
+            iv = G.mlabel_intervals(z, t, None, N, Cn, True, gamma, balance, Cn % 4 == 0, rows_dev=got["rows"])
+            for k in ("dl", "rows", "loss", "s"):
+                _ok(G.check_iv(got[k], iv[k], "confident focal " + k, None))
+            b = float(iv["b"].mid)
+            small = min(small, (b, float(iv["s"].half / iv["s"].mid.abs())))
+    print("smallest b %.3g, relative half width of s there %.3g" % small)
+    assert small[0] < 1e-8
+
+
+@pytest.mark.parametrize("fault", ["scale_none_beyond", "scale_twice_beyond"])
+def test_mlabel_scale_second_trip_faults_rejected(fault):
+    """the (1100, 1000) focal batch: the factor s not applied, and applied twice, from element 4096*256 on"""
+    N, Cn = G.ML_BIG
+    z, t, w = G.mlabel_inputs("scale8", N, Cn)
+    gamma, balance = G.ML_FOCAL[1]
+    _ok(_ml_check(z, t, w, True, gamma, balance, True, False, only=("dl",)))
+    _rejected(lambda: _ml_check(z, t, w, True, gamma, balance, True, False, fault, only=("dl",)))
+
+
+def emu_dice(I, P, T, deduct, fault=None):
+    if I <= 0:
+        return torch.tensor(0.0)
+    U = P + T - (I if (deduct and fault != "no_deduct") else 0)
+    a = F32(2 * I)
+    if fault == "2I_exact":
+        a = F64(2 * I)
+    elif fault in ("2I_trunc24", "2I_trunc23"):                       # the conversion cuts to 24 / 23 significant bits
+        k = max((2 * I).bit_length() - int(fault[-2:]), 0)
+        a = F32(((2 * I) >> k) << k)
+    v = F32(1) + np.log(F32(F64(a) / F64(F32(U))))                    # (the quotient of two fp32 numbers through fp64: one rounding)
+    return torch.from_numpy(np.asarray(min(max(v, F32(0)), F32(1)), dtype=F32))
+
+
+DICE_COUNTS = [(7, 7, 7), (18394, 50000, 50000), (18394, 50000, 50001), (40, 90, 130), (0, 5, 9), (1, 1, 1),
+               (4100 * 4100 - 5, 4100 * 4100 - 3, 4100 * 4100 - 2)]
+
+
+def test_dice_emulation_and_faults():
+    """(I, P, T) of the GPU cases.  U not reduced under deduct is rejected wherever the value is not clamped to 1 either way.
+    NOT separable and not claimed: (float)(2 I) taken as exact above 2^25 -- the conversion moves 2 I by at most u relative, and
+    the bracket allows the division alone one ulp = 2u; no bracket that admits the kernel's own quotient can tell the two.  The
+    same holds for a conversion that truncates to 24 bits where the kernel's rounds (at most 2u): both are shown to lie INSIDE
+    the bracket, on the GPU case's counts and on 2I = 2^25 + 14 against a U that puts the value at 1e-3, where nothing but the
+    quotient and logf round.  The nearest fault that can be told apart is narrowed to: a conversion that keeps 23 bits (up to
+    4u; here 6 / 2^25 and 14 / 2^25 of 2I) -- rejected on both."""
+    for (I, P, T) in DICE_COUNTS:
+        for deduct in (0, 1):
+            _ok(G.check_iv(emu_dice(I, P, T, deduct), G.dice_interval(I, P, T, deduct), "dice %r" % ((I, P, T, deduct),), None))
+    assert float(emu_dice(7, 7, 7, 0)) == 1.0 and float(G.dice_interval(7, 7, 7, 0).hi) == 1.0
+    assert float(G.dice_interval(7, 7, 7, 1).lo) == 1.0                                         # deduct pushes it above 1: clamped
+    assert float(G.dice_interval(18394, 50000, 50000, 0).lo) > 0.0 and float(G.dice_interval(18394, 50000, 50001, 0).hi) == 0.0
+    for (I, P, T) in ((18394, 50000, 50000), (40, 90, 130)):
+        _rejected(lambda: G.check_iv(emu_dice(I, P, T, 1, "no_deduct"), G.dice_interval(I, P, T, 1), "dice, U not reduced", None))
+    n = 4100 * 4100
+    for (I, P, T) in ((n - 5, n - 3, n - 2), (2 ** 24 + 7, 2 ** 24 + 7 + 28782777, 2 ** 24 + 7 + 28782777)):
+        assert 2 * I > 2 ** 25 and float(F32(2 * I)) != 2 * I
+        iv = G.dice_interval(I, P, T, 0)
+        for fault in ("2I_exact", "2I_trunc24"):
+            _ok(G.check_iv(emu_dice(I, P, T, 0, fault), iv, "dice, %s (not separable)" % fault, None))
+        _rejected(lambda: G.check_iv(emu_dice(I, P, T, 0, "2I_trunc23"), iv, "dice, (float)(2I) cut to 23 bits", None))

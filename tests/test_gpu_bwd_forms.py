@@ -9,7 +9,8 @@ replayed standalone with the production integers against fp64 references compute
 Every output and partial table lives in a guarded buffer (tests/gpu_util.py): a write outside it, or an element never written,
 fails the test.  On top of the max-normalised tolerances every launch is held to the derived bounds of tests/gpu_util.py: the
 input gradients element by element (check_onload_bound over the dy-on-load interval, check_dw_bound for the sweeps), the weight
-gradients and fused reduces per element / channel (check_sum_bound, check_red_bound).  Where include/mnas.h promises bit-identical results (RECOMP vs the stored y, masked vs plain gradients, grid
+gradients and fused reduces per element / channel (check_sum_bound, check_red_bound), the merged finalize launch per channel and
+per weight (bn_bwd_finalize_intervals, check_sum_bound) and bit for bit to the standalone finalizes on the same tables.  Where include/mnas.h promises bit-identical results (RECOMP vs the stored y, masked vs plain gradients, grid
 size), the comparison is bit for bit and names the first differing element."""
 import ctypes as C
 
@@ -17,8 +18,8 @@ import pytest
 import torch
 
 from cases import O
-from gpu_util import (HINGE, Interval, L, act_in, act_interval, bf16r, bits_equal, check_dw_bound, check_onload_bound,
-                      check_red_bound, check_sum_bound, conv_gemm, dw_dgrad_terms, dw_wgrad_terms, dy_interval, grad_in, guarded,
+from gpu_util import (HINGE, Interval, L, act_in, act_interval, bf16r, bits_equal, bn_bwd_finalize_intervals, check_dw_bound,
+                      check_interval, check_onload_bound, check_red_bound, check_sum_bound, conv_gemm, dw_dgrad_terms, dw_wgrad_terms, dy_interval, grad_in, guarded,
                       off_hinge, onload_dgrad_terms, pack, rand_bn_coefs, ref_dense_s2_dgrad, ref_dw_dgrad, ref_dw_wgrad,
                       ref_dy, relerr, relu_mask, zero_on_hinge)
 from test_gpu_kernels import DW, PWB, TOL_BF16, TOL_F32
@@ -214,33 +215,101 @@ def _post(lib, bn=None, w1=None, w2=None, expect=0):
         L.check(rc, "bwd_post")
 
 
+FAMILY_POST = "fused finalize launch"
+
+
+def _pow2_scale(n, lo=-20, hi=4, step=7):
+    """n exact powers of two 2^lo .. 2^hi, in an order that puts unlike magnitudes next to each other"""
+    k = (torch.arange(n) * step) % (hi - lo + 1) + lo
+    return torch.pow(torch.tensor(2.0), k.float())
+
+
+def _wg_live_rows(nsplit):
+    """the sparse probe of the two-level reduction: the first row, the last, and both sides of every 128-row chunk boundary"""
+    return sorted({r for r in [0, nsplit - 1] + [b + d for b in range(128, nsplit, 128) for d in (-1, 0)] if 0 <= r < nsplit})
+
+
 class _Wg:
-    """one weight-gradient reduction task: guarded partial table and accumulation target; fp64 expectation"""
-    def __init__(self, nsplit, Co, Ci, taps, dw, seed):
-        self.nsplit, self.Co, self.Ci, self.taps, self.dw = nsplit, Co, Ci, taps, dw
+    """one weight-gradient reduction task: guarded partial table and accumulation target; fp64 expectation.  table: "uniform"
+    (det_uniform); "scaled": rows and columns times powers of two 2^-20..2^4; "sparse": zero but for the rows of _wg_live_rows,
+    whose entries are bounded away from zero (0.5..1 in magnitude), so that every live term exceeds twice the bound."""
+    def __init__(self, nsplit, Co, Ci, taps, dw, seed, table="uniform"):
+        self.nsplit, self.Co, self.Ci, self.taps, self.dw, self.table = nsplit, Co, Ci, taps, dw, table
         shape = (nsplit, taps, Co) if dw else (nsplit, Co, taps * Ci)
         gshape = (Co, taps) if dw else (Co, Ci, taps)
         self.part_host = O.det_uniform(shape, seed)
         self.init = O.det_uniform(gshape, seed + 1)
+        if table == "scaled":
+            cols = shape[1] * shape[2]
+            self.part_host = self.part_host * _pow2_scale(nsplit).view(-1, 1, 1) * _pow2_scale(cols, step=11).view(1, shape[1], shape[2])
+            self.init = self.init * _pow2_scale(self.init.numel(), step=3).view(gshape)
+        elif table == "sparse":
+            live = torch.zeros(nsplit, dtype=torch.bool)
+            live[_wg_live_rows(nsplit)] = True
+            u = self.part_host
+            self.part_host = torch.where(live.view(-1, 1, 1), torch.sign(u + 1e-9) * (0.5 + 0.5 * u.abs()), torch.zeros_like(u))
+            self.init = torch.zeros(gshape)
+        else:
+            assert table == "uniform"
         self.part, self.pchk = guarded(shape, torch.float32)
         self.part.copy_(self.part_host.cuda())
         self.grad, self.gchk = guarded(gshape, torch.float32)
         self.grad.copy_(self.init.cuda())
         S = self.part_host.double().sum(0)
-        self.want = (S.t() if dw else S.view(Co, taps, Ci).permute(0, 2, 1)) + self.init.double()
+        self.want = self._lay(S) + self.init.double()
+        self.mag = self._lay(self.part_host.double().abs().sum(0)) + self.init.double().abs()
+
+    def _lay(self, S):
+        return S.t() if self.dw else S.view(self.Co, self.taps, self.Ci).permute(0, 2, 1)
 
     def slot(self, level):
         return (self.part, self.grad, self.nsplit, self.Co, 1 if self.dw else self.Ci, self.taps, self.dw, level)
 
     def check(self, what):
+        """+ check_sum_bound: M = nsplit terms, c = 1, the accumulate target is the +1; level 2 then 3 (more than 256 rows): P =
+        the number of 128-row chunks the second level adds.  + bit equality with the standalone finalize on the same table (the same template
+        instances: k_wgrad_finalize<DW, false> up to 256 rows, <DW, true> then <DW, false> above)."""
         self.pchk(what + " partial")
         self.gchk(what + " grad")
         assert relerr(self.grad.cpu(), self.want) < 1e-5, (what, relerr(self.grad.cpu(), self.want))
+        P = _cdiv(self.nsplit, 128) if self.nsplit > 256 else 0
+        r = check_sum_bound(self.grad.cpu(), self.want, self.mag, self.nsplit, P, 1, what + " (%s table)" % self.table, None, FAMILY_POST)
+        if self.table == "sparse":
+            bound = (self.nsplit + P + 1) * 2.0 ** -22 * self.mag
+            for row in _wg_live_rows(self.nsplit):
+                assert bool((self._lay(self.part_host[row].double().abs()) > 2 * bound).all()), (what, "live row %d would not be seen" % row)
+            print("%s: sparse probe error / bound %.3f" % (what, r))
+        lib = L.load()
+        p2, g2 = self.part_host.clone().cuda(), self.init.clone().cuda()
+        if self.dw:
+            k = int(round(self.taps ** 0.5))
+            L.check(lib.mnas_dw_wgrad_finalize(L.ptr(p2), self.nsplit, self.Co, k, L.ptr(g2), 1, L.cur_stream()), "dw_wgrad_finalize")
+        else:
+            L.check(lib.mnas_wgrad_finalize(L.ptr(p2), self.nsplit, self.Co, self.Ci, self.taps, L.ptr(g2), 1, L.cur_stream()), "wgrad_finalize")
+        bits_equal(self.grad, g2, what + ": fused launch vs the standalone finalize")
+        return r
 
 
-def _bn_task(C_, nparts, seed):
-    partial = O.det_uniform((2, C_, nparts), seed)
+def _bn_table(C_, nparts, seed, b, table):
+    """the [2][C][nparts] table of (sum dz, sum dz*xhat) partials.  "uniform": det_uniform.  "hard": every channel times a power
+    of two 2^-20..2^4 and every partial column times 2^0..2^-7; in channels c % 3 == 1 the sum dz partials are mean*invstd times
+    the sum dz*xhat ones (rounded to fp32), so that row 4 = s (mean invstd S2 - S1) / count cancels; the last channel (C > 1) is
+    exact zeros."""
+    p = O.det_uniform((2, C_, nparts), seed)
+    if table == "uniform":
+        return p
+    assert table == "hard"
+    p = p * _pow2_scale(C_).view(1, -1, 1) * _pow2_scale(nparts, -7, 0, 3).view(1, 1, -1)
+    c = torch.arange(C_) % 3 == 1
+    p[0, c] = ((b[5] * b[6])[c].double().view(-1, 1) * p[1, c].double()).float()
+    if C_ > 1:
+        p[:, C_ - 1] = 0.0
+    return p
+
+
+def _bn_task(C_, nparts, seed, table="uniform"):
     b = rand_bn_coefs(C_, seed + 1, O)
+    partial = _bn_table(C_, nparts, seed, b, table)
     bp, pchk = guarded((2, C_, nparts), torch.float32)
     bp.copy_(partial.cuda())
     bnbuf, bchk = guarded((8, C_), torch.float32)
@@ -266,6 +335,15 @@ def _bn_task(C_, nparts, seed):
             assert relerr(got[r], bn2[r].cpu().double()) < 1e-6, (what, "bnbuf row", r)
         for r in (0, 1, 5, 6):
             assert torch.equal(got[r], b[r].double()), (what, "bnbuf row %d changed" % r)
+        # every channel inside the brackets of the table as given (fp64 on the fp32 partials; gpu_util.bn_bwd_finalize_intervals)
+        ivs = bn_bwd_finalize_intervals(partial, count, b, g0, b0)
+        fin = {"c1": bnbuf[2], "c2": bnbuf[3], "c3": bnbuf[4], "dgamma": dg, "dbeta": db}
+        worst = max(check_interval(fin[k].cpu(), iv, "%s %s (%s table)" % (what, k, table), FAMILY_POST) for k, iv in ivs.items())
+        # ... and the standalone's bits: bn_bwd_finalize_body<64> up to 256 partials, <256> above, in both launches
+        bits_equal(bnbuf[2:5], bn2[2:5], what + ": rows 2..4, fused launch vs mnas_bn_bwd_finalize")
+        bits_equal(dg, dg2, what + ": dgamma, fused launch vs mnas_bn_bwd_finalize")
+        bits_equal(db, db2, what + ": dbeta, fused launch vs mnas_bn_bwd_finalize")
+        return worst
     return (bp, bnbuf, dg, db, nparts, C_, count), check, (bnbuf, dg, db)
 
 
@@ -335,6 +413,63 @@ def test_bwd_post_level0_slots_and_rejects():
     _post(lib, w2=bad.slot(1), expect=L.EINVAL)
     bad.pchk("rejected launches: partial", written=True)
     assert torch.equal(bad.grad.cpu(), bad.init), "a rejected launch wrote the gradient"
+
+
+@pytest.mark.parametrize("C_", [1, 3, 4, 5])
+@pytest.mark.parametrize("bn_nparts", [1, 256, 257, 1025])
+def test_bwd_post_mapping(C_, bn_nparts):
+    """the mapping of workgroups to the three parts, with tables that can go wrong.  The BatchNorm part (a hard table: scales
+    2^-20..2^4, cancelling channels, a channel of zeros; C = 1, 3, 4, 5: a partial last workgroup of the four-channels-per-
+    workgroup form, one workgroup per channel above 256 partials; 1025 partials: two terms per fp32 accumulator) runs beside
+    w1 alone, beside w2 alone (w1 at level 0), and beside both -- three parts of different sizes (108, 5 and 24 x 3 workgroups)
+    -- at level 1 and at level 2 then 3 with the two-level task in either slot.  Every output inside its bracket and bit-equal
+    to the standalone finalize's."""
+    lib = L.load()
+    what = "mapping C=%d nparts=%d" % (C_, bn_nparts)
+    empty = (None, None, 0, 0, 0, 0, 0, 0)
+    A = lambda tab="scaled": _Wg(5, 24, 16, 9, 0, 110, tab)             # 3456 outputs: 108 workgroups
+    B = lambda tab="scaled": _Wg(130, 16, 1, 9, 1, 112, tab)            # 144 outputs: 5 workgroups
+    T2 = lambda tab="sparse": _Wg(300, 16, 48, 1, 0, 114, tab)          # 768 outputs: 24 x 3 workgroups at level 2, 24 at level 3
+    worst = 0.0
+    for name, slots in (("w1 only", lambda a, b: dict(w1=a.slot(1))), ("w2 only", lambda a, b: dict(w1=empty, w2=b.slot(1))),
+                        ("w1 + w2", lambda a, b: dict(w1=a.slot(1), w2=b.slot(1))), ("w2 + w1", lambda a, b: dict(w1=b.slot(1), w2=a.slot(1)))):
+        a, b = A(), B()
+        bn, check, _ = _bn_task(C_, bn_nparts, 120, "hard")
+        kw = slots(a, b)
+        _post(lib, bn=bn, **kw)
+        worst = max(worst, check("%s, %s: bn" % (what, name)))
+        for w in (a, b):
+            if any(v is not None and v is not empty and v[0] is w.part for v in kw.values()):
+                worst = max(worst, w.check("%s, %s: %s" % (what, name, "A" if w is a else "B")))
+    for slot2, slot3 in (("w1", "w2"), ("w2", "w1")):
+        for tab in ("sparse", "scaled"):
+            w, a, b = T2(tab), A(), B()
+            bn, check, _ = _bn_task(C_, bn_nparts, 122, "hard")
+            _post(lib, bn=bn, **{slot2: w.slot(2), ("w2" if slot2 == "w1" else "w1"): a.slot(1)})
+            worst = max(worst, check("%s, level 2 in %s: bn" % (what, slot2)), a.check("%s, level 2 in %s: A" % (what, slot2)))
+            bn, check, _ = _bn_task(C_, bn_nparts, 124, "hard")
+            _post(lib, bn=bn, **{slot3: w.slot(3), ("w2" if slot3 == "w1" else "w1"): b.slot(1)})
+            worst = max(worst, check("%s, level 3 in %s: bn" % (what, slot3)), b.check("%s, level 3 in %s: B" % (what, slot3)),
+                        w.check("%s, level 2 in %s then 3 in %s (%s)" % (what, slot2, slot3, tab)))
+    print("%s: worst error / bound %.3f" % (what, worst))
+
+
+@pytest.mark.parametrize("dw", [0, 1], ids=["dense", "dw"])
+@pytest.mark.parametrize("nsplit", [1, 128, 129, 256, 257, 384, 385, 1025])
+@pytest.mark.parametrize("table", ["scaled", "sparse"])
+def test_bwd_post_tables(dw, nsplit, table):
+    """the weight-gradient tasks alone on tables that can go wrong: rows and columns scaled by 2^-20..2^4, and the sparse probe (one
+    live row first, last and on both sides of every 128-row chunk boundary); single level up to 256 rows, level 2 then 3 above"""
+    lib = L.load()
+    Co, Ci, taps = (40, 1, 25) if dw else (16, 12, 9)
+    w = _Wg(nsplit, Co, Ci, taps, dw, 130, table)
+    if nsplit <= 256:
+        _post(lib, w2=w.slot(1))
+    else:
+        _post(lib, w1=w.slot(2))
+        _post(lib, w1=w.slot(3))
+    r = w.check("tables %s nsplit %d dw %d" % (table, nsplit, dw))
+    print("bwd_post %s table nsplit %d dw %d: error / bound %.3f" % (table, nsplit, dw, r))
 
 
 # =====================================================================================================================================

@@ -158,20 +158,32 @@ def test_bn_bwd_finalize_frozen_brackets(nparts):
 
 
 def _wg_task(kind, seed):
-    """(MnasPostWgrad fields, partial, grad): a single-level weight-gradient reduction, dense 1x1 or depthwise 3x3"""
-    nsplit, Co, Ci, taps, dw = (5, 8, 16, 1, 0) if kind == "pw" else (7, 24, 1, 9, 1)
+    """(MnasPostWgrad fields, partial, grad, (nsplit, Co, Ci, taps, dw), the gradient before the launch on the host): a
+    single-level weight-gradient reduction, dense 1x1 or depthwise 3x3"""
+    dims = (5, 8, 16, 1, 0) if kind == "pw" else (7, 24, 1, 9, 1)
+    nsplit, Co, Ci, taps, dw = dims
     total = Co * taps if dw else Co * Ci * taps
     partial, grad = _rand((nsplit, total), seed), _rand((total,), seed + 1)
-    return (partial.data_ptr(), grad.data_ptr(), nsplit, Co, Ci, taps, dw, 1), partial, grad
+    return (partial.data_ptr(), grad.data_ptr(), nsplit, Co, Ci, taps, dw, 1), partial, grad, dims, grad.cpu().clone()
 
 
 @pytest.mark.parametrize("nparts", [1, 3, 256, 257, 1024])
 @pytest.mark.parametrize("Cn", [8, 24, 576])
 def test_bwd_post_frozen(Cn, nparts):
-    """merged twin, with and without weight-gradient tasks riding in the launch; those are mnas_bwd_post's, bit for bit"""
+    """merged twin, with and without weight-gradient tasks riding in the launch; those are mnas_bwd_post's, bit for bit.  dgamma,
+    dbeta and dbias of every channel inside gpu_util.bn_bwd_finalize_intervals of the table as given and bit-equal to the
+    standalone mnas_bn_bwd_finalize_frozen's (the same bn_bwd_finalize_body<TPC, true>); the weight gradients inside
+    check_sum_bound (M = nsplit, c = 1, the accumulate target the +1).  hard: every channel of the table times a power of two
+    2^-20..2^4 and the last channel exact zeros."""
+    from gpu_util import bn_bwd_finalize_intervals, check_interval, check_sum_bound
     lib = L.load()
-    for tasks in (False, True):
+    for tasks, hard in ((False, False), (True, False), (True, True)):
         partial, bnbuf, old, sums = _post_inputs(Cn, nparts, 300 + int(tasks))
+        if hard:
+            partial *= torch.pow(torch.tensor(2.0), ((torch.arange(Cn) * 7) % 25 - 20).float()).cuda().view(1, -1, 1)
+            partial[:, Cn - 1] = 0.0
+            S1, S2 = partial[0].double().sum(1), partial[1].double().sum(1)
+            sums = (S2, S1, bnbuf[0].double() * S1)
         before = bnbuf.clone()
         outs = []
         for o in old:
@@ -186,24 +198,129 @@ def test_bwd_post_frozen(Cn, nparts):
         keep = []
         if tasks:
             for slot, kind in (("w1", "pw"), ("w2", "dw")):
-                f, p_, g_ = _wg_task(kind, 400 if kind == "pw" else 500)
-                f2, p2, g2 = _wg_task(kind, 400 if kind == "pw" else 500)
+                f, p_, g_, dims, init = _wg_task(kind, 400 if kind == "pw" else 500)
+                f2, p2, g2, _, _ = _wg_task(kind, 400 if kind == "pw" else 500)
                 setattr(a, slot, L.MnasPostWgrad(*f))
                 setattr(ref, slot, L.MnasPostWgrad(*f2))
-                keep.append((p_, g_, p2, g2))
+                keep.append((p_, g_, p2, g2, dims, init))
         L.check(lib.mnas_bwd_post_frozen(ctypes.byref(a), L.cur_stream()), "bwd_post_frozen")
         for view, check in outs:
             check("bwd_post_frozen C=%d nparts=%d" % (Cn, nparts))
         _check_sums([v for v, _ in outs], old, sums, (Cn, nparts, tasks))
         bits_equal(bnbuf, before, "bnbuf")
+        ivs = bn_bwd_finalize_intervals(partial.cpu(), 1.0, bnbuf.cpu(), old[0].cpu(), old[1].cpu(), frozen=True, dbias0=old[2].cpu())
+        alone = [o.clone() for o in old]
+        L.check(lib.mnas_bn_bwd_finalize_frozen(partial.data_ptr(), nparts, Cn, bnbuf.data_ptr(), alone[0].data_ptr(), alone[1].data_ptr(),
+                                                alone[2].data_ptr(), 1, L.cur_stream()), "finalize_frozen")
+        for name, (view, _), one in zip(("dgamma", "dbeta", "dbias"), outs, alone):
+            check_interval(view.cpu(), ivs[name], "bwd_post_frozen C=%d nparts=%d hard=%d %s" % (Cn, nparts, hard, name), "fused finalize launch")
+            bits_equal(view, one, "%s: fused frozen launch vs mnas_bn_bwd_finalize_frozen" % name)
         if tasks:
+            for p_, g_, p2, g2, (nsplit, Co, Ci, taps, dw), init in keep:
+                tab, init = p_.cpu().double(), init.double()                   # [nsplit][total]; the target in the gradient's layout
+                lay = (lambda v: v.view(taps, Co).t().reshape(-1)) if dw else (lambda v: v.view(Co, taps, Ci).permute(0, 2, 1).reshape(-1))
+                check_sum_bound(g_.cpu(), lay(tab.sum(0)) + init, lay(tab.abs().sum(0)) + init.abs(), nsplit, 0, 1,
+                                "bwd_post_frozen %s task" % ("dw" if dw else "pw"), None, "fused finalize launch")
             L.check(lib.mnas_bwd_post(ctypes.byref(ref), L.cur_stream()), "bwd_post")
-            for p_, g_, p2, g2 in keep:
+            for p_, g_, p2, g2, _, init in keep:
                 bits_equal(g_, g2, "weight gradient of a task in the frozen launch vs mnas_bwd_post")
-                assert not torch.equal(g_, _rand(tuple(g_.shape), 401 if g_.numel() == 128 else 501))      # ... and it was accumulated into
+                assert not torch.equal(g_.cpu(), init)                                     # ... and it was accumulated into
     a = L.MnasBwdPostFrozen()
     a.bn_C, a.bn_nparts = Cn, nparts
     assert lib.mnas_bwd_post_frozen(ctypes.byref(a), L.cur_stream()) == L.EINVAL          # BatchNorm part without its tables
+
+
+class _FrozenBn:
+    """the BatchNorm part of one mnas_bwd_post_frozen launch on test_gpu_bwd_forms._bn_table's "hard" table (channels times
+    2^-20..2^4, partial columns times 2^0..2^-7, channels whose sum dz is mean*invstd times their sum dz*xhat, the last channel
+    exact zeros): guarded table, bnbuf, dgamma, dbeta and dbias, all three accumulated into"""
+    def __init__(self, C_, nparts, seed):
+        import test_gpu_bwd_forms as BF
+        from gpu_util import rand_bn_coefs
+        self.C_, self.nparts = C_, nparts
+        self.b = rand_bn_coefs(C_, seed + 1, O)
+        self.partial = BF._bn_table(C_, nparts, seed, self.b, "hard")
+        self.bp, self.pchk = guarded((2, C_, nparts), torch.float32)
+        self.bp.copy_(self.partial.cuda())
+        self.bnbuf, self.bchk = guarded((8, C_), torch.float32)
+        self.bnbuf.copy_(self.b.cuda())
+        self.old = [O.det_uniform((C_,), seed + 2 + k) for k in range(3)]
+        self.outs = []
+        for o in self.old:
+            view, check = guarded((C_,), torch.float32)
+            view.copy_(o.cuda())
+            self.outs.append((view, check))
+
+    def fill(self, a):
+        a.bn_partial, a.bnbuf = self.bp.data_ptr(), self.bnbuf.data_ptr()
+        a.dgamma, a.dbeta, a.dbias = (v.data_ptr() for v, _ in self.outs)
+        a.count, a.bn_nparts, a.bn_C = 123.0, self.nparts, self.C_
+
+    def check(self, what):
+        """guards; bnbuf bitwise untouched; every channel of dgamma, dbeta, dbias inside bn_bwd_finalize_intervals(frozen) of the
+        table as given and bit-equal to mnas_bn_bwd_finalize_frozen (the same bn_bwd_finalize_body<64 | 256, true>)"""
+        from gpu_util import bn_bwd_finalize_intervals, check_interval
+        self.pchk(what + " partial")
+        self.bchk(what + " bnbuf")
+        bits_equal(self.bnbuf.cpu(), self.b, what + ": bnbuf")
+        ivs = bn_bwd_finalize_intervals(self.partial, 1.0, self.b, self.old[0], self.old[1], frozen=True, dbias0=self.old[2])
+        alone = [o.clone().cuda() for o in self.old]
+        bn2 = self.b.clone().cuda()
+        L.check(L.load().mnas_bn_bwd_finalize_frozen(self.bp.data_ptr(), self.nparts, self.C_, bn2.data_ptr(), alone[0].data_ptr(),
+                                                     alone[1].data_ptr(), alone[2].data_ptr(), 1, L.cur_stream()), "finalize_frozen")
+        worst = 0.0
+        for name, (view, chk), one in zip(("dgamma", "dbeta", "dbias"), self.outs, alone):
+            chk("%s %s" % (what, name))
+            worst = max(worst, check_interval(view.cpu(), ivs[name], "%s %s" % (what, name), "fused finalize launch (frozen)"))
+            bits_equal(view, one, "%s %s: fused frozen launch vs mnas_bn_bwd_finalize_frozen" % (what, name))
+        return worst
+
+
+def _post_frozen(lib, bn, w1=None, w2=None):
+    a = L.MnasBwdPostFrozen()
+    bn.fill(a)
+    for slot, w in (("w1", w1), ("w2", w2)):
+        if w is not None:
+            partial, grad, nsplit, Co, Ci, taps, dw, level = w
+            setattr(a, slot, L.MnasPostWgrad(L.ptr(partial), L.ptr(grad), nsplit, Co, Ci, taps, dw, level))
+    L.check(lib.mnas_bwd_post_frozen(ctypes.byref(a), L.cur_stream()), "bwd_post_frozen")
+
+
+@pytest.mark.parametrize("C_", [1, 3, 4, 5])
+@pytest.mark.parametrize("bn_nparts", [1, 256, 257, 1025])
+def test_bwd_post_frozen_mapping(C_, bn_nparts):
+    """k_bwd_post_frozen's own mapping of workgroups to the three parts, as test_gpu_bwd_forms.test_bwd_post_mapping holds
+    k_bwd_post's: the frozen BatchNorm part on the hard table (C = 1, 3, 4, 5: the `c >= C` return in a partial last workgroup
+    of bn_bwd_finalize_body<64, true>; above 256 partials one workgroup per channel; 1025: two terms per fp32 accumulator)
+    beside w1 alone, beside w2 alone (w1 at level 0), beside both in either order (108, 5 and 24 x 3 workgroups), and beside a
+    level 2 and then a level 3 task in either slot.  Every output inside its bracket and bit-equal to the standalone entry."""
+    import test_gpu_bwd_forms as BF
+    lib = L.load()
+    what = "frozen mapping C=%d nparts=%d" % (C_, bn_nparts)
+    empty = (None, None, 0, 0, 0, 0, 0, 0)
+    A = lambda tab="scaled": BF._Wg(5, 24, 16, 9, 0, 210, tab)            # 3456 outputs: 108 workgroups
+    B = lambda tab="scaled": BF._Wg(130, 16, 1, 9, 1, 212, tab)           # 144 outputs: 5 workgroups
+    T2 = lambda tab: BF._Wg(300, 16, 48, 1, 0, 214, tab)                  # 768 outputs: 24 x 3 workgroups at level 2, 24 at level 3
+    worst = 0.0
+    for name, use in (("w1 only", "a-"), ("w2 only", "-b"), ("w1 + w2", "ab"), ("w2 + w1", "ba")):
+        w = {"a": A(), "b": B()}
+        slots = [empty if ch == "-" else w[ch].slot(1) for ch in use]
+        bn = _FrozenBn(C_, bn_nparts, 220)
+        _post_frozen(lib, bn, w1=slots[0], w2=slots[1])
+        worst = max(worst, bn.check("%s, %s: bn" % (what, name)))
+        for ch in use.replace("-", ""):
+            worst = max(worst, w[ch].check("%s, %s: %s" % (what, name, ch.upper())))
+    for slot2, slot3 in (("w1", "w2"), ("w2", "w1")):
+        for tab in ("sparse", "scaled"):
+            t2, a, b = T2(tab), A(), B()
+            bn = _FrozenBn(C_, bn_nparts, 222)
+            _post_frozen(lib, bn, **{slot2: t2.slot(2), slot3: a.slot(1)})
+            worst = max(worst, bn.check("%s, level 2 in %s: bn" % (what, slot2)), a.check("%s, level 2 in %s: A" % (what, slot2)))
+            bn = _FrozenBn(C_, bn_nparts, 224)
+            _post_frozen(lib, bn, **{slot3: t2.slot(3), slot2: b.slot(1)})
+            worst = max(worst, bn.check("%s, level 3 in %s: bn" % (what, slot3)), b.check("%s, level 3 in %s: B" % (what, slot3)),
+                        t2.check("%s, level 2 in %s then 3 in %s (%s)" % (what, slot2, slot3, tab)))
+    print("%s: worst error / bound %.3f" % (what, worst))
 
 
 # Scale agreement per tensor at whole-network scope, test_gpu_model.py's rule (NET_GRAD_SCALE / NET_STAGE_MEDIAN) re-measured for

@@ -3,7 +3,14 @@ with a MultiClassBCELoss) against tests/golden/multilabel.json (what the referen
 
 Bounds.  F1 and the integer counts: exact.  Dice: 4 * 2^-24 -- three fp32 roundings of magnitude <= 1 in 1 + log(2I/U) plus one for a
 differing logf.  Loss and gradient: the bounds tests/test_gpu_head.py::test_cross_entropy holds the cross-entropy kernels to, against
-an fp64 evaluation of the rule on the same inputs: |loss - ref| <= 2e-5 |ref| and max |dl - ref| < 1e-5 max |ref|."""
+an fp64 evaluation of the rule on the same inputs: |loss - ref| <= 2e-5 |ref| and max |dl - ref| < 1e-5 max |ref|.
+
+Per-element bounds (test_bounds*, test_dice_bounds*): every element of dlogits, every row sum, the loss and the focal factor s
+inside the brackets of gpu_util.mlabel_intervals (interval propagation through ml_elem as written, expf / log1pf / division at one
+ulp; the loss and s from the row sums the device left in the scratch), HardDice inside gpu_util.dice_interval; no element is
+excluded.  tests/test_bounds_cpu.py proves on the same inputs that these brackets admit the kernel's arithmetic in every variant
+and reject a dropped tail element, a wrong weight, a wrong 1/(N*C), log(1 + ea) for log1pf and the other faults listed there.
+MEASURED on an MI355X, worst error / bound: dlogits 0.79, row sums 0.13 (the sparse probes 0.07), loss 0.33, s 0.33, HardDice 0.20."""
 import json
 import os
 
@@ -12,6 +19,7 @@ import pytest
 import torch
 
 import cases as C
+import gpu_util as GU
 import multilabel_ref as R
 from gpu_util import relerr
 from mnasnet_pytorch_amd import HardDice, MultiClassBCELoss, MultiLabelMeters
@@ -31,34 +39,64 @@ def _bits(t):
 
 class _Bce:
     """one call of mnas_mlabel_bce into guarded buffers: NaN-filled margins around dlogits and the loss, 0xA5 bytes around the scratch;
-    `ok()` checks that they are untouched.  misalign: the weights start 4 bytes past a 16-byte boundary."""
+    `ok()` checks that they are untouched.  misalign: the weights start 4 bytes past a 16-byte boundary; mis = "z" / "t" / "w" /
+    "dl": that pointer alone does (any one of them sends a vector-eligible shape down the scalar path).  rows, s: the row sums
+    and the focal factor the device left in the scratch (include/mnas.h: float[N] at byte 8 N, one float at byte 24 N).
+    expect: the return code the call must give (then nothing may be written: `untouched()`)."""
 
-    def __init__(self, z, t, w=None, focal=False, gamma=R.FOCUS, balance=R.BALANCE, meters=None, nw=(0, 0, 0), grad=True, misalign=False):
+    def __init__(self, z, t, w=None, focal=False, gamma=R.FOCUS, balance=R.BALANCE, meters=None, nw=(0, 0, 0), grad=True, misalign=False,
+                 mis=None, expect=0, shape=None, null=(), scratch_shift=0):
         lib = L.load()
         N, Cn = z.shape
         self.N, self.Cn = N, Cn
-        self.dl_buf = torch.full((N * Cn + 2 * G,), NAN, device="cuda")
+        mis = "w" if misalign else mis
+        self.dlo = 1 if mis == "dl" else 0
+        self.dl_buf = torch.full((N * Cn + 2 * G + 4,), NAN, device="cuda")
         self.loss_buf = torch.full((2 * G + 1,), NAN, device="cuda")
         self.nb = int(lib.mnas_mlabel_scratch_bytes(N))
         self.scratch = torch.full((self.nb + 2 * G,), 0xA5, dtype=torch.uint8, device="cuda")
-        wptr = 0
-        if w is not None:
-            off = 1 if misalign else 0
-            self.wbuf = torch.zeros(N * Cn + 8, device="cuda")
-            self.wbuf[off:off + N * Cn] = w.reshape(-1)
-            wptr = self.wbuf.data_ptr() + 4 * off
-            assert wptr % 16 == (4 if misalign else 0)
+        self.keep = []
+
+        def place(x, off):
+            buf = torch.zeros(N * Cn + 8, device="cuda")
+            buf[off:off + N * Cn] = x.reshape(-1)
+            self.keep.append(buf)
+            assert (buf.data_ptr() + 4 * off) % 16 == 4 * off
+            return buf.data_ptr() + 4 * off
+        zptr = place(z, 1) if mis == "z" else z.data_ptr()
+        tptr = place(t, 1) if mis == "t" else t.data_ptr()
+        wptr = 0 if w is None else place(w, 1 if mis == "w" else 0)
         self.grad = grad
-        L.check(lib.mnas_mlabel_bce(z.data_ptr(), t.data_ptr(), wptr, N, Cn, 1 if focal else 0, float(gamma), float(balance),
-                                    self.scratch.data_ptr() + G, self.loss_buf.data_ptr() + 4 * G,
-                                    self.dl_buf.data_ptr() + 4 * G if grad else 0, meters.kernel_args(z.device) if meters else 0,
-                                    nw[0], nw[1], nw[2], L.cur_stream()), "mlabel_bce")
+        ptrs = {"logits": zptr, "target": tptr, "scratch": self.scratch.data_ptr() + G + scratch_shift, "loss": self.loss_buf.data_ptr() + 4 * G}
+        for k in null:
+            ptrs[k] = 0
+        assert (self.dl_buf.data_ptr() + 4 * (G + self.dlo)) % 16 == 4 * self.dlo
+        cN, cC = (N, Cn) if shape is None else shape
+        rc = lib.mnas_mlabel_bce(ptrs["logits"], ptrs["target"], wptr, cN, cC, 1 if focal else 0, float(gamma), float(balance),
+                                 ptrs["scratch"], ptrs["loss"], self.dl_buf.data_ptr() + 4 * (G + self.dlo) if grad else 0,
+                                 meters.kernel_args(z.device) if meters else 0, nw[0], nw[1], nw[2], L.cur_stream())
+        if expect:
+            assert rc == expect, rc
+        else:
+            L.check(rc, "mlabel_bce")
         self.loss = self.loss_buf[G]
-        self.dl = self.dl_buf[G:G + N * Cn].view(N, Cn)
+        self.dl = self.dl_buf[G + self.dlo:G + self.dlo + N * Cn].view(N, Cn)
+
+    @property
+    def rows(self):
+        return self.scratch[G + 8 * self.N:G + 12 * self.N].view(torch.float32)
+
+    @property
+    def s(self):
+        return self.scratch[G + 24 * self.N:G + 24 * self.N + 4].view(torch.float32)[0]
+
+    def untouched(self):
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(self.dl_buf).all()) and bool(torch.isnan(self.loss_buf).all()) and bool((self.scratch == 0xA5).all())
 
     def ok(self):
         n = self.N * self.Cn
-        assert bool(torch.isnan(self.dl_buf[:G]).all()) and bool(torch.isnan(self.dl_buf[G + n:]).all())
+        assert bool(torch.isnan(self.dl_buf[:G + self.dlo]).all()) and bool(torch.isnan(self.dl_buf[G + self.dlo + n:]).all())
         assert bool(torch.isnan(self.loss_buf[:G]).all()) and bool(torch.isnan(self.loss_buf[G + 1:]).all())
         assert bool((self.scratch[:G] == 0xA5).all()) and bool((self.scratch[G + self.nb:] == 0xA5).all())
         if not self.grad:
@@ -236,6 +274,205 @@ def test_edge_rows():
     rec = m.read()
     assert (rec.tp, rec.fp, rec.fn) == R.dice_counts(z.numpy(), t.numpy()) and rec.f1.val == R.f1_batch(z.numpy(), t.numpy())
     assert rec.tp + rec.fn == int((t == 1).sum())
+
+
+# ---- per-element bounds (gpu_util.mlabel_intervals / dice_interval; tests/test_bounds_cpu.py proves that they bite) ------------------------
+def _check_bounds(call, z, t, w, focal, gamma, balance, vec, what):
+    """every output of one mnas_mlabel_bce call inside its bracket: dlogits and the row sums element by element, the loss and
+    (focal) s from the rows the device stored.  z, t, w where the fp64 work shall run (host, or the device for the large case)."""
+    N, Cn = z.shape
+    dev = z.device
+    iv = GU.mlabel_intervals(z, t, w, N, Cn, focal, gamma, balance, vec, rows_dev=call.rows)
+    r = {"dlogits": GU.check_iv(call.dl.to(dev), iv["dl"], what + " dlogits", "multi-label dlogits"),
+         "rows": GU.check_iv(call.rows.to(dev), iv["rows"], what + " row sums", "multi-label row sums"),
+         "loss": GU.check_iv(call.loss.cpu(), iv["loss"], what + " loss", "multi-label loss")}
+    if focal:
+        r["s"] = GU.check_iv(call.s.cpu(), iv["s"], what + " s", "multi-label focal s")
+    return r, iv
+
+
+def _vec(Cn, mis=None):
+    return Cn % 4 == 0 and mis is None
+
+
+@pytest.mark.parametrize("N,Cn", GU.ML_SHAPES)
+def test_bounds(N, Cn):
+    """one class; partial waves; the workgroup's second trip on the scalar path (257, 1000 misaligned, 1027: its fifth) and on the
+    vector path (1028: second, 2052: third); the batch stage's second and third trip (257, 513 rows).  Every input family of
+    gpu_util.mlabel_inputs, all four variants (the confident batch under every focal setting), weights aligned (the vector path
+    where C % 4 == 0) and 4 bytes off (the scalar path); guarded buffers.  The fused entry gives the plain one's bits and exact
+    meters, as on the older shapes."""
+    worst, small = {}, (1.0, 0.0)
+    for ki, kind in enumerate(GU.ML_KINDS):
+        z, t, w = GU.mlabel_inputs(kind, N, Cn)
+        zc, tc, wc = z.cuda(), t.cuda(), w.cuda()
+        f1, counts, dice = R.f1_batch(z.numpy(), t.numpy()), R.dice_counts(z.numpy(), t.numpy()), R.hard_dice(z.numpy(), t.numpy())
+        for name, weighted, focal in R.LOSS_VARIANTS:
+            for gamma, balance in (GU.ML_FOCAL if (focal and kind == "confident") else (GU.ML_FOCAL[ki % 3],)):
+                for mis in ((None, "w") if weighted else (None,)):
+                    what = "%s %s (%d, %d) gamma %g mis %s" % (kind, name, N, Cn, gamma, mis)
+                    m = MultiLabelMeters()
+                    a = _Bce(zc, tc, wc if weighted else None, focal, gamma, balance, mis=mis)
+                    b = _Bce(zc, tc, wc if weighted else None, focal, gamma, balance, meters=m, nw=(N, N, 3), mis=mis)
+                    torch.cuda.synchronize()
+                    a.ok(), b.ok()
+                    assert torch.equal(_bits(a.loss), _bits(b.loss)) and torch.equal(_bits(a.dl), _bits(b.dl)), what
+                    rec = m.read()
+                    assert rec.f1.val == f1 and (rec.last_tp, rec.last_fp, rec.last_fn) == counts and rec.loss.val == float(a.loss), what
+                    assert abs(rec.hdice.val - dice) <= DICE_TOL and (rec.steps, rec.samples, rec.f1_n) == (1, N, 3), what
+                    r, iv = _check_bounds(a, z, t, w if weighted else None, focal, gamma, balance, _vec(Cn, mis), what)
+                    for k, v in r.items():
+                        worst[k] = max(worst.get(k, 0.0), v)
+                    if focal and kind == "confident":
+                        small = min(small, (float(iv["b"].mid), float(iv["s"].half / iv["s"].mid.abs())))
+                    if kind == "sparse" and weighted and not focal:
+                        GU.mlabel_probe_visible(iv, GU.mlabel_live(N, Cn), what)
+                        rr = float(((a.rows.cpu().double() - iv["rows"].mid).abs() / iv["row_half"]).max())
+                        worst["sparse rows"] = max(worst.get("sparse rows", 0.0), rr)
+    print("(%d, %d): worst error / bound %s; smallest confident b %.3g, relative half width of s there %.3g"
+          % (N, Cn, ", ".join("%s %.3f" % kv for kv in sorted(worst.items())), small[0], small[1]))
+
+
+@pytest.mark.parametrize("N,Cn", [(3, 1024), (2, 2052)])
+def test_bounds_alignment(N, Cn):
+    """a vector-eligible shape: all aligned takes k_mlabel_row<true>; each of z, t, w, dlogits ALONE at element offset 1 takes
+    k_mlabel_row<false>.  Each run inside its own path's bracket; dlogits (every element computed alone) bit-equal between the
+    paths; the row sums' order differs between the paths, so they are held to their own path's bracket, not to each other.  On
+    (3, 1024) the two orders give different bits in every row (tests/test_bounds_cpu.py's emulation, fused and unfused), so a
+    misaligned run whose row sums equal the aligned run's did not change path; on (2, 2052) they happen to agree and nothing
+    is asserted."""
+    z, t, w = GU.mlabel_inputs("scale8", N, Cn)
+    zc, tc, wc = z.cuda(), t.cuda(), w.cuda()
+    for focal in (False, True):
+        base = _Bce(zc, tc, wc, focal).ok()
+        _check_bounds(base, z, t, w, focal, R.FOCUS, R.BALANCE, True, "aligned (%d, %d)" % (N, Cn))
+        plain = _Bce(zc, tc, wc, False).ok()
+        for mis in ("z", "t", "w", "dl"):
+            c = _Bce(zc, tc, wc, focal, mis=mis).ok()
+            r, iv = _check_bounds(c, z, t, w, focal, R.FOCUS, R.BALANCE, False, "%s off by one element (%d, %d)" % (mis, N, Cn))
+            ref = base.dl if not focal else (plain.dl * c.s)           # (focal: s comes from the path's own row sums)
+            assert torch.equal(_bits(c.dl), _bits(ref)), (mis, focal)
+            if Cn == 1024:      # the dispatch did move: the two lane orders round these rows apart (all three, in the CPU emulation)
+                assert not torch.equal(_bits(c.rows), _bits(base.rows)), "%s off by one element: the vector path's row sums" % mis
+
+
+def test_bounds_scale_second_trip():
+    """(1100, 1000) focal, weighted: N*C = 1.1 M > 4096*256, so every lane of k_mlabel_scale's capped grid takes a second trip for
+    the elements from 1 048 576 on.  Brackets in fp64 on the device; and separately: every element -- those at and beyond the cap
+    among them -- is the unscaled gradient times the device's s, rounded once, to the bit (scaled exactly once)."""
+    N, Cn = GU.ML_BIG
+    cap = 4096 * 256
+    z, t, w = GU.mlabel_inputs("scale8", N, Cn)
+    zc, tc, wc = z.cuda(), t.cuda(), w.cuda()
+    gamma, balance = GU.ML_FOCAL[1]
+    a = _Bce(zc, tc, wc, True, gamma, balance).ok()
+    plain = _Bce(zc, tc, wc, False).ok()
+    r, _ = _check_bounds(a, zc, tc, wc, True, gamma, balance, True, "(1100, 1000) focal")
+    once = (plain.dl * a.s).reshape(-1)
+    got = a.dl.reshape(-1)
+    assert float(a.s) != 1.0 and N * Cn > cap
+    assert torch.equal(_bits(got[cap:]), _bits(once[cap:])), "elements from 4096*256 on are not scaled exactly once"
+    assert torch.equal(_bits(got[:cap]), _bits(once[:cap]))
+    assert (gamma, balance) == (R.FOCUS, R.BALANCE)
+    _check_loss(a, z, t, w, True, "(1100, 1000) focal")                 # (the older tolerances, beside the brackets)
+    print("(1100, 1000) focal: worst error / bound %s" % ", ".join("%s %.3f" % kv for kv in sorted(r.items())))
+
+
+def _dice_batch(N, Cn, I, fp, fn, weak=0):
+    """logits / targets on the device with I predicted-and-true, fp predicted-only and fn true-only elements; `weak` of the I
+    sit at z = 0.5: predicted under threshold 0.5, not under 0.7"""
+    z = torch.full((N * Cn,), -3.0, device="cuda")
+    t = torch.zeros(N * Cn, device="cuda")
+    z[:I + fp] = 3.0
+    z[:weak] = 0.5
+    t[:I] = 1.0
+    t[I + fp:I + fp + fn] = 1.0
+    return z.view(N, Cn), t.view(N, Cn)
+
+
+def _hard_dice(z, t, thr_logit, deduct, expect=0, null=()):
+    lib = L.load()
+    N, Cn = z.shape
+    out = torch.full((2 * G + 1,), NAN, device="cuda")
+    nb = int(lib.mnas_mlabel_scratch_bytes(N))
+    scratch = torch.full((nb + 2 * G,), 0xA5, dtype=torch.uint8, device="cuda")
+    p = {"z": z.data_ptr(), "t": t.data_ptr(), "scratch": scratch.data_ptr() + G, "out": out.data_ptr() + 4 * G}
+    for k in null:
+        p[k] = 0
+    rc = lib.mnas_mlabel_hard_dice(p["z"], p["t"], N, Cn, float(thr_logit), deduct, p["scratch"], p["out"], L.cur_stream())
+    torch.cuda.synchronize()
+    if expect:
+        assert rc == expect and bool(torch.isnan(out).all()) and bool((scratch == 0xA5).all())
+        return None
+    L.check(rc, "hard_dice")
+    assert bool(torch.isnan(out[:G]).all()) and bool(torch.isnan(out[G + 1:]).all())
+    assert bool((scratch[:G] == 0xA5).all()) and bool((scratch[G + nb:] == 0xA5).all())
+    return out[G].cpu()
+
+
+@pytest.mark.parametrize("N,Cn,I,fp,fn,weak", [(1, 7, 7, 0, 0, 0), (100, 1000, 18394, 31606, 31606, 0), (100, 1001, 18394, 31606, 31607, 0),
+                                               (7, 33, 40, 50, 90, 11), (3, 5, 0, 5, 9, 0), (1, 1, 1, 0, 0, 0)])
+def test_dice_bounds(N, Cn, I, fp, fn, weak):
+    """2I == U: exactly 1.0; 2I/U = 0.36788 and 0.3678763, either side of 1/e (the clamp at 0); deduct pushing the value above 1
+    (clamped); thresholds 0.5 and 0.7 (the `weak` hits drop out under 0.7); nothing hit: 0.  Counts from numpy (dice_counts);
+    the old DICE_TOL assertion beside the bracket."""
+    z, t = _dice_batch(N, Cn, I, fp, fn, weak)
+    zn, tn = z.cpu().numpy(), t.cpu().numpy()
+    for th in (0.5, 0.7):
+        thr = float(np.log(th / (1 - th)))
+        tp, fp_, fn_ = R.dice_counts(zn, tn, thr)
+        assert (tp, fp_, fn_) == ((I, fp, fn) if th == 0.5 else (I - weak, fp, fn + weak))
+        for deduct in (0, 1):
+            got = _hard_dice(z, t, thr, deduct)
+            iv = GU.dice_interval(tp, tp + fp_, tp + fn_, deduct)
+            r = GU.check_iv(got, iv, "HardDice %r threshold %g deduct %d" % ((N, Cn, I, fp, fn), th, deduct), "HardDice")
+            assert abs(float(got) - R.hard_dice(zn, tn, thr, bool(deduct))) <= DICE_TOL
+            if tp > 0 and fp_ == 0 and fn_ == 0:
+                assert float(got) == 1.0                                  # 2I == U: 1 + logf(1); with deduct 1 + log 2, clamped
+            if tp == 0:
+                assert float(got) == 0.0
+    if (I, fp, fn) == (18394, 31606, 31606):
+        assert 0.0 < float(_hard_dice(z, t, 0.0, 0)) < 1e-5
+    if (I, fp, fn) == (18394, 31606, 31607):
+        assert float(_hard_dice(z, t, 0.0, 0)) == 0.0
+
+
+def test_dice_bounds_rounded_conversion():
+    """4100 x 4100 (16.8 M elements built on the device: under 0.1 s, so the size is not reduced), all predicted and true but 3 + 2: 2I = 33 619 990 > 2^25 and U = 33 619 995 are no
+    fp32 numbers, so (float)(2I) and (float)U round.  The mnas_mlabel_hard_dice entry only; the counts are known by construction."""
+    N = Cn = 4100
+    I, fp, fn = N * Cn - 5, 2, 3
+    z, t = _dice_batch(N, Cn, I, fp, fn)
+    assert float(torch.tensor(float(2 * I)).float()) != 2 * I and 2 * I > 2 ** 25
+    for deduct in (0, 1):
+        got = _hard_dice(z, t, 0.0, deduct)
+        r = GU.check_iv(got, GU.dice_interval(I, I + fp, I + fn, deduct), "HardDice 4100 x 4100 deduct %d" % deduct, "HardDice")
+        print("HardDice 4100 x 4100 deduct %d: %r, error / bound %.3f" % (deduct, float(got), r))
+
+
+def test_rejects_write_nothing():
+    """every refused call returns MNAS_EINVAL and leaves the NaN / 0xA5 guards and the meter block as they were"""
+    z, t, w = GU.mlabel_inputs("scale8", 3, 8)
+    zc, tc, wc = z.cuda(), t.cuda(), w.cuda()
+    m = MultiLabelMeters()
+    m.update(zc, tc)
+    torch.cuda.synchronize()
+    block = m.block.clone()
+    E = L.EINVAL
+    kw = dict(meters=m, nw=(3, 3, 3), expect=E)
+    cases = [dict(shape=(0, 8)), dict(shape=(-1, 8)), dict(shape=(3, 0)), dict(shape=(3, -2)), dict(null=("logits",)), dict(null=("target",)),
+             dict(null=("scratch",)), dict(null=("loss",)), dict(scratch_shift=8), dict(focal=True, gamma=0.5), dict(focal=True, gamma=NAN),
+             dict(nw=(-1, 3, 3)), dict(nw=(3, -1, 3)), dict(nw=(3, 3, -1))]
+    for c in cases:
+        _Bce(zc, tc, wc, **{**kw, **c}).untouched()
+        assert torch.equal(m.block, block), c
+    for c in (dict(null=("z",)), dict(null=("t",)), dict(null=("scratch",)), dict(null=("out",))):
+        _hard_dice(zc, tc, 0.0, 0, expect=E, **c)
+    _hard_dice(zc, tc, NAN, 0, expect=E)
+    _hard_dice(zc[:0], tc[:0], 0.0, 0, expect=E)
+    assert torch.equal(m.block, block)
+    _Bce(zc, tc, wc, meters=m, nw=(3, 3, 3)).ok()                       # ... and the same arguments, valid, do run
+    assert not torch.equal(m.block, block)
 
 
 # ---- meters ------------------------------------------------------------------------------------------------------------------------------
