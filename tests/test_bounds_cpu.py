@@ -1,4 +1,4 @@
-"""CPU proof that the per-element bounds of tests/gpu_util.py bite.  A plain torch emulation of each kernel class's arithmetic
+"""CPU proof that the per-element bounds of tests/bounds_*.py bite.  A plain torch emulation of each kernel class's arithmetic
 (fp32 operands formed from bf16 inputs, fp32 accumulate, round-to-nearest-even bf16 store) must sit inside its bound with every
 condition of the helpers met; the same emulation with one fault -- a precision loss or a dropped / misplaced term of the kind an
 optimisation of the kernels can introduce -- must be rejected.  Nothing here touches a kernel: the faults live in the emulation.
@@ -7,10 +7,17 @@ import numpy as np
 import pytest
 import torch
 
-import gpu_util as G
-from gpu_util import (Interval, act_interval, bf16r, check_dw_bound, check_onload_bound, check_red_bound, check_stats_bound,
-                      check_sum_bound, dw_dgrad_terms, dw_elem_err, dw_fwd_terms, dw_wgrad_terms, dy_interval, off_hinge,
-                      onload_dgrad_terms, onload_elem_err, onload_fwd_terms, pad_hw, wgrad_terms)
+import bounds_conv as BC
+import bounds_mlabel as BM
+import bounds_se as BS
+import bounds_tail as BT
+import intervals as IV
+from bounds_conv import (act_interval, check_dw_bound, check_onload_bound, check_red_bound, check_stats_bound, dw_dgrad_terms, dw_elem_err,
+                         dw_fwd_terms, dw_wgrad_terms, dy_interval, off_hinge, onload_dgrad_terms, onload_elem_err, onload_fwd_terms,
+                         wgrad_terms)
+from gpu_util import bf16r
+from intervals import Interval, check_sum_bound
+from refs64 import pad_hw
 
 
 def _u(shape, seed):
@@ -132,7 +139,7 @@ def pw():
 def test_mfma_forward_emulation_inside_bound(pw):
     worst = pw.check()
     assert 0.3 < worst <= 1.0, worst
-    assert pw.iv.split_share() <= G.MAX_ACT_SPLIT
+    assert pw.iv.split_share() <= BC.MAX_ACT_SPLIT
 
 
 @pytest.mark.parametrize("fault", ["trunc", "acc_bf16_chunks", "shift_dropped", "bias_missing"])
@@ -172,7 +179,7 @@ def pwd():
 def test_mfma_dgrad_emulation_inside_bound(pwd):
     worst = pwd.check()
     assert 0.3 < worst <= 1.0, worst
-    assert pwd.iv.split_share() <= G.MAX_DY_SPLIT
+    assert pwd.iv.split_share() <= BC.MAX_DY_SPLIT
 
 
 def test_mask_taken_with_ge_on_exact_zeros_rejected(pwd):
@@ -185,7 +192,7 @@ def test_hinge_conditions_are_asserted():
     with pytest.raises(AssertionError, match="off_hinge would move"):
         off_hinge(v, s, t)
     with pytest.raises(AssertionError, match="on the ReLU hinge"):
-        G.relu_mask(v, s, t)
+        BC.relu_mask(v, s, t)
     with pytest.raises(AssertionError, match="straddle a rounding boundary"):
         # shifts of 2^20 make the interval wider than a bf16 ulp of most elements
         act_interval(bf16r(_u((50, 8), 2)), torch.full((8,), 2.0 ** 10), torch.full((8,), 3.0 * 2.0 ** 17), bf16=True)
@@ -345,7 +352,7 @@ def test_dw_statistics_emulation(dw):
 # The device's sigmoid is modelled as the fp64 value moved 0.8 of the way to an end of its bracket (end = -1, 0, +1) and rounded to
 # fp32; everything else is fp32 torch arithmetic in the kernels' operation order where the kernels fix one.
 def _sig(v, end=0):
-    iv = G.sigmoid_interval(v)
+    iv = BS.sigmoid_interval(v)
     return (iv.val + 0.8 * end * (iv.hi - iv.val if end > 0 else iv.val - iv.lo)).float()
 
 
@@ -357,21 +364,21 @@ def _ok(r):
 
 def test_sigmoid_bracket_and_faults():
     v = torch.cat([torch.arange(-30 * 64, 30 * 64 + 1).float() / 64, torch.tensor([0.0, -0.0])])
-    iv = G.sigmoid_interval(v)
+    iv = BS.sigmoid_interval(v)
     got = 1.0 / (1.0 + torch.exp(-v))                      # fp32, a correctly rounded exponential
-    assert 0.05 < _ok(G.check_interval(got, iv, "sigmoid", None))
+    assert 0.05 < _ok(IV.check_interval(got, iv, "sigmoid", None))
     for end in (-1, 1):
-        _ok(G.check_interval(_sig(v, end), iv, "sigmoid end %d" % end, None))
-    _rejected(lambda: G.check_interval(bf16r(got), iv, "sigmoid rounded to bf16", None))
+        _ok(IV.check_interval(_sig(v, end), iv, "sigmoid end %d" % end, None))
+    _rejected(lambda: IV.check_interval(bf16r(got), iv, "sigmoid rounded to bf16", None))
     # du = acc * sg * (1 - sg)
     acc = _u(v.shape, 1)
-    du_iv = G.imul(Interval.exact(acc), G.sig1m_interval(v), 1)
+    du_iv = Interval.exact(acc).mul(BS.sig1m_interval(v), 1)
     for end in (-1, 0, 1):
         sg = _sig(v, end)
-        _ok(G.check_interval(acc * sg * (1.0 - sg), du_iv, "du end %d" % end, None))
-    _rejected(lambda: G.check_interval(acc * _sig(v), du_iv, "du without 1 - sg", None))
+        _ok(IV.check_interval(acc * sg * (1.0 - sg), du_iv, "du end %d" % end, None))
+    _rejected(lambda: IV.check_interval(acc * _sig(v), du_iv, "du without 1 - sg", None))
     sgb = bf16r(_sig(v))
-    _rejected(lambda: G.check_interval(acc * sgb * (1.0 - sgb), du_iv, "du with a bf16 sigmoid", None))
+    _rejected(lambda: IV.check_interval(acc * sgb * (1.0 - sgb), du_iv, "du with a bf16 sigmoid", None))
 
 
 class _Se:
@@ -385,8 +392,8 @@ class _Se:
         self.u = amp * _u((self.N, self.C), 34)
         self.gs = bf16r(_u(sh, 35))
         self.dz = _u((self.N, self.C), 36)
-        self.gate = G.sigmoid_interval(self.u)
-        self.g4 = G.gate_nhwc(self.gate, sh)
+        self.gate = BS.sigmoid_interval(self.u)
+        self.g4 = BS.gate_nhwc(self.gate, sh)
 
     def sg(self, end=0):
         return _sig(self.u, end).view(self.N, 1, 1, self.C)
@@ -399,21 +406,21 @@ def se(request):
 
 @pytest.mark.parametrize("virt", [True, False])
 def test_se_scale_emulation_and_faults(se, virt):
-    iv = G.gated_act_interval(se.z, se.s if virt else None, se.t if virt else None, se.g4, bf16=False)
+    iv = BS.gated_act_interval(se.z, se.s if virt else None, se.t if virt else None, se.g4, bf16=False)
     a = emu_act(se.z, se.s, se.t, False) if virt else se.z
     for end in (-1, 0, 1):
-        _ok(G.check_store_bound(bf16r(a * se.sg(end)), iv, "se_scale end %d" % end, None))
+        _ok(IV.check_store_bound(bf16r(a * se.sg(end)), iv, "se_scale end %d" % end, None))
     if virt:            # (a plain input is a bf16 value already: there is no rounding to do twice)
-        _rejected(lambda: G.check_store_bound(bf16r(bf16r(a) * se.sg()), iv, "se_scale: value rounded before the gate", None))
-        _rejected(lambda: G.check_store_bound(bf16r(emu_act(se.z, se.s, se.t, False, "shift_dropped") * se.sg()), iv, "se_scale: shift dropped", None))
+        _rejected(lambda: IV.check_store_bound(bf16r(bf16r(a) * se.sg()), iv, "se_scale: value rounded before the gate", None))
+        _rejected(lambda: IV.check_store_bound(bf16r(emu_act(se.z, se.s, se.t, False, "shift_dropped") * se.sg()), iv, "se_scale: shift dropped", None))
 
 
 def test_gated_mfma_operand_emulation_and_faults(se):
     Co = 16
     w = bf16r(_u((Co, se.C, 1, 1), 37) * (3.0 / se.C) ** 0.5)
     bias = 0.1 * _u((Co,), 38)
-    iv = G.gated_act_interval(se.z, se.s, se.t, se.g4, bf16=True)
-    assert iv.split_share() <= G.MAX_ACT_SPLIT
+    iv = BS.gated_act_interval(se.z, se.s, se.t, se.g4, bf16=True)
+    assert iv.split_share() <= BC.MAX_ACT_SPLIT
     ref, slack, S = onload_fwd_terms(iv, w, bias)
     M = se.N * se.HW
 
@@ -429,7 +436,7 @@ def test_gated_mfma_operand_emulation_and_faults(se):
 def _emu_se_reduce(se, a, fault=None):
     """k_se_bwd_reduce + k_se_bwd_finish: per split, lane pr walks pixels p0+pr, p0+pr+R, ... with one fma each; lanes, then splits,
     added in order"""
-    G_, R, chunk, splits = G.se_geom(se.N, se.HW, se.C)
+    G_, R, chunk, splits = BS.se_geom(se.N, se.HW, se.C)
     assert (R, chunk, splits) == (42, 126, 2)
     g, a = se.gs.reshape(se.N, se.HW, se.C), a.reshape(se.N, se.HW, se.C)
     parts = []
@@ -460,24 +467,24 @@ def _emu_se_reduce(se, a, fault=None):
 
 @pytest.mark.parametrize("virt", [True, False])
 def test_se_bwd_reduce_emulation_and_faults(se, virt):
-    G_, R, chunk, splits = G.se_geom(se.N, se.HW, se.C)
+    G_, R, chunk, splits = BS.se_geom(se.N, se.HW, se.C)
     aiv = act_interval(se.z, se.s, se.t, bf16=False) if virt else Interval.exact(se.z)
-    ref, S, slack = G.se_reduce_terms(se.gs, aiv, se.HW)
-    iv = G.imul(G.sum_interval(ref, S, se.HW, R + splits, 1, slack), G.sig1m_interval(se.u), 1)
+    ref, S, slack = BS.se_reduce_terms(se.gs, aiv, se.HW)
+    iv = IV.sum_interval(ref, S, se.HW, R + splits, 1, slack).mul(BS.sig1m_interval(se.u), 1)
     a = emu_act(se.z, se.s, se.t, False) if virt else se.z
-    _ok(G.check_interval(_emu_se_reduce(se, a), iv, "se_bwd_reduce", None))
+    _ok(IV.check_interval(_emu_se_reduce(se, a), iv, "se_bwd_reduce", None))
     for fault in ("drop_chunk_last", "double_split_first", "acc_bf16"):
-        _rejected(lambda: G.check_interval(_emu_se_reduce(se, a, fault), iv, "se_bwd_reduce " + fault, None))
+        _rejected(lambda: IV.check_interval(_emu_se_reduce(se, a, fault), iv, "se_bwd_reduce " + fault, None))
 
 
 def test_se_bwd_apply_emulation_and_faults(se):
-    iv = G.se_apply_interval(se.gs, se.u, se.dz, se.HW)
+    iv = BS.se_apply_interval(se.gs, se.u, se.dz, se.HW)
     dz4 = se.dz.view(se.N, 1, 1, se.C)
     inv = torch.tensor(1.0) / torch.tensor(float(se.HW))
     for end in (-1, 0, 1):
-        _ok(G.check_store_bound(bf16r(se.gs * se.sg(end) + dz4 * inv), iv, "se_bwd_apply end %d" % end, None))
-    _rejected(lambda: G.check_store_bound(bf16r(se.gs * se.sg() + dz4 / (se.HW + 1)), iv, "se_bwd_apply dz/(HW+1)", None))
-    _rejected(lambda: G.check_store_bound(bf16r(se.gs * se.sg()), iv, "se_bwd_apply without dz", None))
+        _ok(IV.check_store_bound(bf16r(se.gs * se.sg(end) + dz4 * inv), iv, "se_bwd_apply end %d" % end, None))
+    _rejected(lambda: IV.check_store_bound(bf16r(se.gs * se.sg() + dz4 / (se.HW + 1)), iv, "se_bwd_apply dz/(HW+1)", None))
+    _rejected(lambda: IV.check_store_bound(bf16r(se.gs * se.sg()), iv, "se_bwd_apply without dz", None))
 
 
 def _emu_proj(wp, N, kseg, W, u, fault=None):
@@ -504,13 +511,13 @@ def _emu_proj(wp, N, kseg, W, u, fault=None):
 def test_se_proj_finalize_emulation_and_faults(N, kseg, Co, Ci):
     wp = _u((N * kseg, Co, Ci), 41) * 5
     W, u = _u((Co, Ci), 42) * 0.3, 2 * _u((N, Ci), 43)
-    du_iv, ref, S, slack, M = G.se_proj_finalize_intervals(wp, N, kseg, W, u)
+    du_iv, ref, S, slack, M = BS.se_proj_finalize_intervals(wp, N, kseg, W, u)
     du, dW = _emu_proj(wp, N, kseg, W, u)
-    _ok(G.check_interval(du, du_iv, "se_proj du", None))
+    _ok(IV.check_interval(du, du_iv, "se_proj du", None))
     _ok(check_sum_bound(dW, ref, S, M, 0, 2, "se_proj dW", slack, family=None))
     if kseg > 1:
         du, dW = _emu_proj(wp, N, kseg, W, u, "slab_dropped")
-        _rejected(lambda: G.check_interval(du, du_iv, "se_proj du, slab dropped", None))
+        _rejected(lambda: IV.check_interval(du, du_iv, "se_proj du, slab dropped", None))
         _rejected(lambda: check_sum_bound(dW, ref, S, M, 0, 2, "se_proj dW, slab dropped", slack, family=None))
     _, dW = _emu_proj(wp, N, kseg, W, u, "sigma_last_image")
     _rejected(lambda: check_sum_bound(dW, ref, S, M, 0, 2, "se_proj dW without the last image's sigma", slack, family=None))
@@ -522,20 +529,20 @@ def test_se_fc_emulation_and_faults(N, E, R):
     W1, b1 = torch.randn(R, E, generator=torch.Generator().manual_seed(52)) / E ** 0.5, 0.1 * _u((R,), 53) + 0.3
     W2, b2 = torch.randn(E, R, generator=torch.Generator().manual_seed(54)) / R ** 0.5, 0.1 * _u((E,), 55)
     du = _u((N, E), 56)
-    hb_iv, u_iv, gate_iv = G.se_fc_fwd_intervals(z, W1, b1, W2, b2)
+    hb_iv, u_iv, gate_iv = BS.se_fc_fwd_intervals(z, W1, b1, W2, b2)
     hb = torch.relu(z @ W1.t() + b1)
     u = hb @ W2.t() + b2
-    _ok(G.check_interval(hb, hb_iv, "se_fc hb", None))
-    _ok(G.check_interval(u, u_iv, "se_fc u", None))
-    _ok(G.check_interval(_sig(u), gate_iv, "se_fc gate", None))
+    _ok(IV.check_interval(hb, hb_iv, "se_fc hb", None))
+    _ok(IV.check_interval(u, u_iv, "se_fc u", None))
+    _ok(IV.check_interval(_sig(u), gate_iv, "se_fc gate", None))
     if R % 4:
-        _rejected(lambda: G.check_interval(hb[:, :R - 1] @ W2[:, :R - 1].t() + b2, u_iv, "se_fc u, last hidden unit dropped", None))
+        _rejected(lambda: IV.check_interval(hb[:, :R - 1] @ W2[:, :R - 1].t() + b2, u_iv, "se_fc u, last hidden unit dropped", None))
     base = {k: 0.5 * _u(s_, 60 + i) for i, (k, s_) in enumerate((("dW1", (R, E)), ("db1", (R,)), ("dW2", (E, R)), ("db2", (E,))))}
     for acc in (False, True):
-        dh_iv, dz_iv, terms = G.se_fc_bwd_terms(du, z, hb, W1, W2, base if acc else None)
+        dh_iv, dz_iv, terms = BS.se_fc_bwd_terms(du, z, hb, W1, W2, base if acc else None)
         dh = (du @ W2) * (hb > 0)
-        _ok(G.check_interval(dh, dh_iv, "se_fc dh", None))
-        _ok(G.check_interval(dh @ W1, dz_iv, "se_fc dz", None))
+        _ok(IV.check_interval(dh, dh_iv, "se_fc dh", None))
+        _ok(IV.check_interval(dh @ W1, dz_iv, "se_fc dz", None))
         got = {"dW1": dh.t() @ z, "db1": dh.sum(0), "dW2": du.t() @ hb, "db2": du.sum(0)}
         for k, (ref, S, slack, c) in terms.items():
             _ok(check_sum_bound(got[k] + (base[k] if acc else 0), ref, S, N, 16, c, "se_fc " + k, slack, family=None))
@@ -573,7 +580,7 @@ def _emu_stem_wgrad(x, dy, fault=None, rb=4):
 def test_stem_wgrad_emulation_and_faults():
     N, H, W, Co = 2, 20, 32, 32
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    assert G.stem_wgrad_band_rows(W, Wo) == 4 and Ho % 4
+    assert BS.stem_wgrad_band_rows(W, Wo) == 4 and Ho % 4
     x = bf16r(_u((N, H, W, 3), 71))
     cf = _coefs(Co, 72)
     g, y = bf16r(_u((N, Ho, Wo, Co), 73)), off_hinge(bf16r(_u((N, Ho, Wo, Co), 74)), cf[0], cf[1])
@@ -616,10 +623,10 @@ def test_stem_dgrad_emulation_and_faults(Co):
     div = dy_interval(g, y, cf, bf16=True)
     dy = emu_dy(g, y, cf, True)
     for a_ in (None, aff):
-        ref, bound = G.stem_dgrad_terms(div, bf16r(w), H, W, a_)
-        _ok(G._assert_bound(_emu_stem_dgrad(dy, w, H, W, a_), ref, bound, "stem dgrad", None))
+        ref, bound = BS.stem_dgrad_terms(div, bf16r(w), H, W, a_)
+        _ok(IV._assert_bound(_emu_stem_dgrad(dy, w, H, W, a_), ref, bound, "stem dgrad", None))
         for fault in ("last_row", "weights_fp32") + (("affine_plane",) if a_ is not None else ()):
-            _rejected(lambda: G._assert_bound(_emu_stem_dgrad(dy, w, H, W, a_, fault), ref, bound, "stem dgrad " + fault, None))
+            _rejected(lambda: IV._assert_bound(_emu_stem_dgrad(dy, w, H, W, a_, fault), ref, bound, "stem dgrad " + fault, None))
 
 
 # ---- glue -----------------------------------------------------------------------------------------------------------------------
@@ -629,29 +636,29 @@ def test_pool_act_emulation_and_faults(N, HW, C_, virt):
     x = bf16r(_u((N, HW, C_), 81))
     s, t = 1 + 0.3 * _u((C_,), 82), 0.2 * _u((C_,), 83)
     aiv = act_interval(x, s, t, bf16=False) if virt else Interval.exact(x)
-    ref, bound = G.pool_act_terms(aiv, HW)
+    ref, bound = BS.pool_act_terms(aiv, HW)
     a = emu_act(x, s, t, False) if virt else x
     R = 256 // (C_ // 8)
     acc = torch.zeros(N, C_)
     for p in range(HW):
         acc = acc + a[:, p]
-    _ok(G._assert_bound(acc / HW, ref, bound, "pool_act", None))
+    _ok(IV._assert_bound(acc / HW, ref, bound, "pool_act", None))
     padded = -(-HW // (8 * R)) * 8 * R
-    _rejected(lambda: G._assert_bound(acc / padded, ref, bound, "pool_act / padded count", None))
+    _rejected(lambda: IV._assert_bound(acc / padded, ref, bound, "pool_act / padded count", None))
     if HW > 1:
-        _rejected(lambda: G._assert_bound((acc - a[:, HW - 1]) / HW, ref, bound, "pool_act, last pixel dropped", None))
+        _rejected(lambda: IV._assert_bound((acc - a[:, HW - 1]) / HW, ref, bound, "pool_act, last pixel dropped", None))
 
 
 def test_add_act_emulation_and_faults():
     rows, C_ = 98, 320
     a, b = bf16r(_u((rows, C_), 84)), bf16r(_u((rows, C_), 85))
     sa, ta, sb, tb = 1 + 0.3 * _u((C_,), 86), 0.2 * _u((C_,), 87), 1 + 0.3 * _u((C_,), 88), 0.2 * _u((C_,), 89)
-    iv = G.add_act_interval(act_interval(a, sa, ta, bf16=False), act_interval(b, sb, tb, bf16=False))
+    iv = BS.add_act_interval(act_interval(a, sa, ta, bf16=False), act_interval(b, sb, tb, bf16=False))
     v = emu_act(a, sa, ta, False) + emu_act(b, sb, tb, False)
-    _ok(G.check_interval(v, iv, "add_act fp32", None))
-    _ok(G.check_store_bound(bf16r(v), iv, "add_act bf16", None))
-    _rejected(lambda: G.check_interval(bf16r(emu_act(a, sa, ta, False)) + emu_act(b, sb, tb, False), iv, "add_act: a rounded to bf16", None))
-    _rejected(lambda: G.check_store_bound(bf16r(bf16r(emu_act(a, sa, ta, False)) + emu_act(b, sb, tb, False)), iv, "add_act bf16: two roundings", None))
+    _ok(IV.check_interval(v, iv, "add_act fp32", None))
+    _ok(IV.check_store_bound(bf16r(v), iv, "add_act bf16", None))
+    _rejected(lambda: IV.check_interval(bf16r(emu_act(a, sa, ta, False)) + emu_act(b, sb, tb, False), iv, "add_act: a rounded to bf16", None))
+    _rejected(lambda: IV.check_store_bound(bf16r(bf16r(emu_act(a, sa, ta, False)) + emu_act(b, sb, tb, False)), iv, "add_act bf16: two roundings", None))
 
 
 # ---- finalizes ------------------------------------------------------------------------------------------------------------------
@@ -675,23 +682,23 @@ def _emu_bn_fwd(partial, count, gamma, beta, rm, rv, mom=0.1, eps=1e-5, fault=No
 @pytest.mark.parametrize("C_,nparts,count", [(16, 7, 100.0), (8, 256, 50176.0), (8, 1024, 802816.0), (8, 1, 1.0), (8, 1, 64.0)])
 def test_bn_fwd_finalize_emulation_and_faults(C_, nparts, count):
     Ct = C_ + 3
-    partial = G.bn_fwd_partials(_u((2, Ct, nparts), 91), count)
+    partial = BS.bn_fwd_partials(_u((2, Ct, nparts), 91), count)
     gamma, beta = 1 + 0.2 * _u((Ct,), 92), 0.1 * _u((Ct,), 93)
     rm, rv = 0.1 * _u((Ct,), 94), 1 + 0.3 * _u((Ct,), 95).abs()
-    ivs = G.bn_fwd_finalize_intervals(partial, count, gamma, beta, rm, rv, 0.1, 1e-5)
+    ivs = BS.bn_fwd_finalize_intervals(partial, count, gamma, beta, rm, rv, 0.1, 1e-5)
     got = _emu_bn_fwd(partial, count, gamma, beta, rm, rv)
     for k, iv in ivs.items():
-        _ok(G.check_interval(got[k].float(), iv, "bn_fwd_finalize " + k, None))
+        _ok(IV.check_interval(got[k].float(), iv, "bn_fwd_finalize " + k, None))
     assert float(ivs["invstd"].half[-1]) < 1e-6 * float(ivs["invstd"].mid[-1])          # the clamped channel: both ends at var = 0
     bad = _emu_bn_fwd(partial, count, gamma, beta, rm, rv, fault="fp32")
     if count > 1:
         ch = Ct - 3                                                                       # |mean|/std = 30
         one = Interval(ivs["invstd"].lo[ch], ivs["invstd"].hi[ch])
-        _rejected(lambda: G.check_interval(bad["invstd"][ch].float(), one, "bn_fwd_finalize in fp32 at |mean|/std = 30", None))
+        _rejected(lambda: IV.check_interval(bad["invstd"][ch].float(), one, "bn_fwd_finalize in fp32 at |mean|/std = 30", None))
         bad = _emu_bn_fwd(partial, count, gamma, beta, rm, rv, fault="biased")
-        _rejected(lambda: G.check_interval(bad["running_var"].float(), ivs["running_var"], "biased variance into running_var", None))
+        _rejected(lambda: IV.check_interval(bad["running_var"].float(), ivs["running_var"], "biased variance into running_var", None))
         bad = _emu_bn_fwd(partial, count, gamma, beta, rm, rv, fault="no_clamp")
-        _rejected(lambda: G.check_interval(bad["invstd"].float(), ivs["invstd"], "no clamp on a negative var", None))
+        _rejected(lambda: IV.check_interval(bad["invstd"].float(), ivs["invstd"], "no clamp on a negative var", None))
 
 
 @pytest.mark.parametrize("nparts", [7, 257, 1025])
@@ -708,15 +715,15 @@ def test_bn_bwd_finalize_emulation_and_faults(nparts):
         c3 = s * (mean * inv * s2 / cnt - s1 / cnt)
         return {"c1": s.float(), "c2": (-s * inv * s2 / cnt).float(), "c3": (-c3 if fault == "sign" else c3).float(),
                 "dgamma": g0 + s2.float(), "dbeta": b0 + s1.float(), "dbias": c0 + (s * s1).float()}
-    ivs = G.bn_bwd_finalize_intervals(partial, count, bn, g0, b0)
-    ivs["dbias"] = G.bn_bwd_finalize_intervals(partial, count, bn, g0, b0, frozen=True, dbias0=c0)["dbias"]
+    ivs = BS.bn_bwd_finalize_intervals(partial, count, bn, g0, b0)
+    ivs["dbias"] = BS.bn_bwd_finalize_intervals(partial, count, bn, g0, b0, frozen=True, dbias0=c0)["dbias"]
     got = emu()
     for k, iv in ivs.items():
-        _ok(G.check_interval(got[k], iv, "bn_bwd_finalize " + k, None))
-    _rejected(lambda: G.check_interval(emu("sign")["c3"], ivs["c3"], "bn_bwd_finalize: sign of row 4", None))
+        _ok(IV.check_interval(got[k], iv, "bn_bwd_finalize " + k, None))
+    _rejected(lambda: IV.check_interval(emu("sign")["c3"], ivs["c3"], "bn_bwd_finalize: sign of row 4", None))
     if nparts <= 1024:          # (at T = 2 the bracket of the fp32 partial sums is wider than 1/count)
-        _rejected(lambda: G.check_interval(emu("count")["c2"], ivs["c2"], "bn_bwd_finalize: count - 1", None))
-    _rejected(lambda: G.check_interval(got["dgamma"] - g0, ivs["dgamma"], "bn_bwd_finalize: accumulate ignored", None))
+        _rejected(lambda: IV.check_interval(emu("count")["c2"], ivs["c2"], "bn_bwd_finalize: count - 1", None))
+    _rejected(lambda: IV.check_interval(got["dgamma"] - g0, ivs["dgamma"], "bn_bwd_finalize: accumulate ignored", None))
 
 
 @pytest.mark.parametrize("nsplit,acc", [(5, 0), (300, 1), (129, 1)])
@@ -739,11 +746,11 @@ def test_gated_operand_straddle_share_of_the_gpu_tests(shape):
     """the inputs of tests/test_gpu_se.py::test_gated_project_forward where it asserts check_onload_bound over
     gated_act_interval(..., bf16=True): the share of bf16 elements whose bracket straddles a rounding boundary is <= MAX_ACT_SPLIT"""
     from cases import O
-    y, s, t, u, w, bias = G.gated_fwd_inputs(shape, O)
+    y, s, t, u, w, bias = BS.gated_fwd_inputs(shape, O)
     yn = y.permute(0, 2, 3, 1)
-    iv = G.gated_act_interval(yn, s, t, G.gate_nhwc(G.sigmoid_interval(u), yn.shape), bf16=True)
+    iv = BS.gated_act_interval(yn, s, t, BS.gate_nhwc(BS.sigmoid_interval(u), yn.shape), bf16=True)
     print("gated operand %s: straddle share %.3g" % (shape, iv.split_share()))
-    assert iv.split_share() <= G.MAX_ACT_SPLIT
+    assert iv.split_share() <= BC.MAX_ACT_SPLIT
 
 
 # ---- the fp32 tail of the step: head GEMMs, cross-entropy, optimizers ----------------------------------------------------------------
@@ -809,10 +816,10 @@ def emu_head_rowsum(A, r0=None):
 
 
 def _head_case(N, I, O_, p, scaled):
-    x, w, b, dz, u_prev, c0w, c0b = G.head_inputs(N, I, O_, scaled)
+    x, w, b, dz, u_prev, c0w, c0b = BT.head_inputs(N, I, O_, scaled)
     keep = (_u((N, I), 99) > 2 * p - 1) if p else torch.ones(N, I, dtype=torch.bool)
-    xd = G.head_dropped(x, keep, p)
-    post = keep * G.head_drop_scale(p) if p else None
+    xd = BT.head_dropped(x, keep, p)
+    post = keep * BT.head_drop_scale(p) if p else None
     return x, w, b, dz, u_prev, c0w, c0b, keep, xd, post
 
 
@@ -823,14 +830,14 @@ def test_head_gemm_emulations_inside_bound(N, I, O_, scaled):
         x, w, b, dz, u_prev, c0w, c0b, keep, xd, post = _head_case(N, I, O_, p, scaled)
         for fused in (True, False):
             for relu in (False, True):
-                _ok(G.check_interval(emu_head_gemm(xd, w.t(), b, relu=relu, fused=fused),
-                                     G.head_gemm_interval(xd, w.t(), b, relu=relu), "head fwd", None))
-            _ok(G.check_interval(emu_head_gemm(xd, w.t(), fused=fused), G.head_gemm_interval(xd, w.t()), "head fwd, no bias", None))
-            _ok(G.check_interval(emu_head_gemm(dz.t(), xd, C0=c0w, fused=fused), G.head_gemm_interval(dz.t(), xd, C0=c0w), "head dW", None))
+                _ok(IV.check_interval(emu_head_gemm(xd, w.t(), b, relu=relu, fused=fused),
+                                     BT.head_gemm_interval(xd, w.t(), b, relu=relu), "head fwd", None))
+            _ok(IV.check_interval(emu_head_gemm(xd, w.t(), fused=fused), BT.head_gemm_interval(xd, w.t()), "head fwd, no bias", None))
+            _ok(IV.check_interval(emu_head_gemm(dz.t(), xd, C0=c0w, fused=fused), BT.head_gemm_interval(dz.t(), xd, C0=c0w), "head dW", None))
             mask = u_prev > 0
-            _ok(G.check_interval(emu_head_gemm(dz, w, post=post, mask_src=u_prev, fused=fused),
-                                 G.head_gemm_interval(dz, w, post=post, mask=mask), "head dx", None))
-        _ok(G.check_interval(emu_head_rowsum(dz.t(), c0b), G.head_rowsum_interval(dz.t(), c0b), "head db", None))
+            _ok(IV.check_interval(emu_head_gemm(dz, w, post=post, mask_src=u_prev, fused=fused),
+                                 BT.head_gemm_interval(dz, w, post=post, mask=mask), "head dx", None))
+        _ok(IV.check_interval(emu_head_rowsum(dz.t(), c0b), BT.head_rowsum_interval(dz.t(), c0b), "head db", None))
 
 
 @pytest.mark.parametrize("fault", ["operand_bf16", "trunc10", "partials_bf16", "bias_missing", "mask_ge"])
@@ -838,36 +845,36 @@ def test_head_gemm_emulations_inside_bound(N, I, O_, scaled):
 def test_head_gemm_faults_rejected(N, I, O_, fault):
     x, w, b, dz, u_prev, c0w, c0b, keep, xd, post = _head_case(N, I, O_, 0.2, True)
     if fault == "mask_ge":
-        iv = G.head_gemm_interval(dz, w, post=post, mask=u_prev > 0)
-        _rejected(lambda: G.check_interval(emu_head_gemm(dz, w, post=post, mask_src=u_prev, fault=fault), iv, "head dx " + fault, None))
+        iv = BT.head_gemm_interval(dz, w, post=post, mask=u_prev > 0)
+        _rejected(lambda: IV.check_interval(emu_head_gemm(dz, w, post=post, mask_src=u_prev, fault=fault), iv, "head dx " + fault, None))
         return
-    iv = G.head_gemm_interval(xd, w.t(), b)
-    _rejected(lambda: G.check_interval(emu_head_gemm(xd, w.t(), b, fault=fault), iv, "head fwd " + fault, None))
+    iv = BT.head_gemm_interval(xd, w.t(), b)
+    _rejected(lambda: IV.check_interval(emu_head_gemm(xd, w.t(), b, fault=fault), iv, "head fwd " + fault, None))
     if fault != "bias_missing":
-        iv = G.head_gemm_interval(dz.t(), xd, C0=c0w)
-        _rejected(lambda: G.check_interval(emu_head_gemm(dz.t(), xd, C0=c0w, fault=fault), iv, "head dW " + fault, None))
+        iv = BT.head_gemm_interval(dz.t(), xd, C0=c0w)
+        _rejected(lambda: IV.check_interval(emu_head_gemm(dz.t(), xd, C0=c0w, fault=fault), iv, "head dW " + fault, None))
 
 
 def test_head_sparse_probe_sees_a_dropped_and_a_doubled_term():
     N, I, O_ = 130, 133, 131
-    x, w, b, dz, u_prev, c0w, c0b = G.head_inputs(N, I, O_, False)
-    cases = {"fwd": (G.head_sparse(x, 1, I), w.t()), "dW": (G.head_sparse(dz.t(), 1, N), x), "dx": (G.head_sparse(dz, 1, O_), w)}
+    x, w, b, dz, u_prev, c0w, c0b = BT.head_inputs(N, I, O_, False)
+    cases = {"fwd": (BT.head_sparse(x, 1, I), w.t()), "dW": (BT.head_sparse(dz.t(), 1, N), x), "dx": (BT.head_sparse(dz, 1, O_), w)}
     for name, (A, B) in cases.items():
-        iv = G.head_gemm_interval(A, B)
-        G.head_probe_visible(A, B, iv, name)
-        _ok(G.check_interval(emu_head_gemm(A, B), iv, "sparse " + name, None))
-        for k in G.HEAD_LIVE_K(A.shape[1]):
+        iv = BT.head_gemm_interval(A, B)
+        BT.head_probe_visible(A, B, iv, name)
+        _ok(IV.check_interval(emu_head_gemm(A, B), iv, "sparse " + name, None))
+        for k in BT.HEAD_LIVE_K(A.shape[1]):
             for f in (0.0, 2.0):
                 A2 = A.clone()
                 A2[:, k] *= f
-                _rejected(lambda: G.check_interval(emu_head_gemm(A2, B), iv, "sparse %s k %d x%g" % (name, k, f), None))
-    A = G.head_sparse(dz.t(), 1, N)
-    iv = G.head_rowsum_interval(A)
-    _ok(G.check_interval(emu_head_rowsum(A), iv, "sparse db", None))
-    for k in G.HEAD_LIVE_K(N):
+                _rejected(lambda: IV.check_interval(emu_head_gemm(A2, B), iv, "sparse %s k %d x%g" % (name, k, f), None))
+    A = BT.head_sparse(dz.t(), 1, N)
+    iv = BT.head_rowsum_interval(A)
+    _ok(IV.check_interval(emu_head_rowsum(A), iv, "sparse db", None))
+    for k in BT.HEAD_LIVE_K(N):
         A2 = A.clone()
         A2[:, k] = 0
-        _rejected(lambda: G.check_interval(emu_head_rowsum(A2), iv, "sparse db k %d dropped" % k, None))
+        _rejected(lambda: IV.check_interval(emu_head_rowsum(A2), iv, "sparse db k %d dropped" % k, None))
 
 
 def _wg_sum(v):
@@ -948,27 +955,27 @@ def emu_ce(x, ta, tb=None, lam=None, eps=None, fused=False, fault=None, ignore_i
 
 def _ce_check(x, ta, tb, lam, eps, fused=False, fault=None):
     dl, rows, loss = emu_ce(x, ta, tb, lam, eps, fused, fault)
-    iv = G.ce_intervals(x, ta, tb, lam, eps)
-    r = [G.check_iv(dl, iv["dl"], "ce dlogits", None), G.check_iv(rows, iv["rows"], "ce loss rows", None)]
-    r.append(G.check_ce_mean(loss, rows, iv["count"], "ce mean", None))
+    iv = BT.ce_intervals(x, ta, tb, lam, eps)
+    r = [IV.check_interval(dl, iv["dl"], "ce dlogits", None), IV.check_interval(rows, iv["rows"], "ce loss rows", None)]
+    r.append(BT.check_ce_mean(loss, rows, iv["count"], "ce mean", None))
     if iv["count"] == 0:
         assert bool((dl == 0).all())
     return max(r)
 
 
 def _soft_args(N, Cn, how):
-    a, b = G.ce_targets(N, Cn)
+    a, b = BT.ce_targets(N, Cn)
     lam = torch.tensor([0.0, 0.5, 1.0, 0.3, 0.8125, 0.49999997])[torch.arange(N) % 6]
     b = torch.where(torch.arange(N) % 4 == 1, a, b)                      # rows with a == b among the others
-    return G.ce_ignore(a, how), b, lam
+    return BT.ce_ignore(a, how), b, lam
 
 
-@pytest.mark.parametrize("N,Cn", G.CE_SIZES)
+@pytest.mark.parametrize("N,Cn", BT.CE_SIZES)
 def test_cross_entropy_emulations_inside_bracket(N, Cn):
     worst = 0.0
-    for i, kind in enumerate(G.CE_ROWS):
-        x = G.ce_logits(kind, N, Cn)
-        for how in (G.CE_IGNORE if N * Cn <= 10000 else G.CE_IGNORE[i % 4:i % 4 + 1]):
+    for i, kind in enumerate(BT.CE_ROWS):
+        x = BT.ce_logits(kind, N, Cn)
+        for how in (BT.CE_IGNORE if N * Cn <= 10000 else BT.CE_IGNORE[i % 4:i % 4 + 1]):
             a, b, lam = _soft_args(N, Cn, how)
             for fused in (False, True):
                 worst = max(worst, _ce_check(x, a, None, None, None, fused))
@@ -988,7 +995,7 @@ def test_cross_entropy_faults_rejected(fault, N, Cn, how, eps):
     """wb_on_same: the label of a row with a == b gets wa = 1 - eps AND a share wb on top.  (The milder variant -- such a row
     treated as any other, two rounded shares that add up to 1 - eps within one ulp -- moves q by at most u and lies inside any
     bracket that allows the kernel's own roundings of p - q: it cannot be separated and is not claimed.)"""
-    x = G.ce_logits("uniform4", N, Cn)
+    x = BT.ce_logits("uniform4", N, Cn)
     a, b, lam = _soft_args(N, Cn, how)
     tb, l = (None, None) if eps is None else (b, lam)
     _ok(_ce_check(x, a, tb, l, eps))
@@ -996,13 +1003,13 @@ def test_cross_entropy_faults_rejected(fault, N, Cn, how, eps):
 
 
 def _opt_state(n):
-    return G.opt_data(n, seed=n)
+    return BT.opt_data(n, seed=n)
 
 
 def emu_adam(p, g, m, v, lr, b1, b2, eps, wd, step, gscale, coef=None, fused=False, fault=None):
     f = lambda c: torch.tensor(c, dtype=torch.float32)
     lr, b1, b2, eps, wd, gscale = (f(c) for c in (lr, b1, b2, eps, wd, gscale))
-    bc1, bc2s = (f(c) for c in G.adam_bias(float(b1), float(b2), step))
+    bc1, bc2s = (f(c) for c in BT.adam_bias(float(b1), float(b2), step))
     gi = g * gscale
     if coef is not None:
         gi = gi * f(coef)
@@ -1066,7 +1073,7 @@ def emu_sgd(p, g, buf, lr, momentum, dampening, wd, nesterov, step, gscale, fuse
 
 
 def _opt_check(got, ivs, what):
-    return max(_ok(G.check_interval(got[k], ivs[k], "%s %s" % (what, k), None)) for k in ivs)
+    return max(_ok(IV.check_interval(got[k], ivs[k], "%s %s" % (what, k), None)) for k in ivs)
 
 
 ADAM = dict(lr=1e-3, b1=0.9, b2=0.999, eps=1e-8)
@@ -1080,20 +1087,20 @@ def test_optimizer_emulations_inside_bracket(n):
             for wd in (0.0, 1e-2):
                 for gs in (1.0, 0.125, 1.0 / 3):
                     _opt_check(emu_adam(p, g, m, v, wd=wd, step=step, gscale=gs, fused=fused, **ADAM),
-                               G.adam_intervals(p, g, m, v, wd=wd, step=step, gscale=gs, **ADAM), "adam")
+                               BT.adam_intervals(p, g, m, v, wd=wd, step=step, gscale=gs, **ADAM), "adam")
         _opt_check(emu_adam(p, g, m, v, wd=1e-2, step=2, gscale=0.125, coef=0.37, fused=fused, **ADAM),
-                   G.adam_intervals(p, g, m, v, wd=1e-2, step=2, gscale=0.125, coef=G._iv(G.f32(0.37)), **ADAM), "adam_ex")
+                   BT.adam_intervals(p, g, m, v, wd=1e-2, step=2, gscale=0.125, coef=Interval.exact(IV.f32(0.37)), **ADAM), "adam_ex")
         for mom in (0.0, 0.9):
             for wd in (0.0, 1e-2):
                 a = dict(lr=1e-2, alpha=0.99, eps=1e-8, wd=wd, momentum=mom, gscale=1.0 / 3)
-                _opt_check(emu_rmsprop(p, g, v, buf, fused=fused, **a), G.rmsprop_intervals(p, g, v, buf, **a), "rmsprop")
+                _opt_check(emu_rmsprop(p, g, v, buf, fused=fused, **a), BT.rmsprop_intervals(p, g, v, buf, **a), "rmsprop")
             for damp in (0.0, 0.5):
                 for nest in (0, 1):
                     for step in (1, 2):
                         if nest and (mom == 0.0 or damp != 0.0):
                             continue
                         a = dict(lr=1e-2, momentum=mom, dampening=damp, wd=1e-2, nesterov=nest, step=step, gscale=0.125)
-                        _opt_check(emu_sgd(p, g, buf, fused=fused, **a), G.sgd_intervals(p, g, buf, **a), "sgd")
+                        _opt_check(emu_sgd(p, g, buf, fused=fused, **a), BT.sgd_intervals(p, g, buf, **a), "sgd")
 
 
 @pytest.mark.parametrize("n", [255, 257])
@@ -1101,11 +1108,11 @@ def test_optimizer_emulations_inside_bracket(n):
 def test_adam_and_rmsprop_faults_rejected(n, fault):
     p, g, m, v, buf = _opt_state(n)
     a = dict(wd=1e-2, step=2, gscale=0.125, **ADAM)
-    iv = G.adam_intervals(p, g, m, v, **a)
+    iv = BT.adam_intervals(p, g, m, v, **a)
     _rejected(lambda: _opt_check(emu_adam(p, g, m, v, fault=fault, **a), iv, "adam " + fault))
     if fault in ("v_bf16", "eps_in_sqrt"):
         a = dict(lr=1e-2, alpha=0.99, eps=1e-8, wd=0.0, momentum=0.9, gscale=1.0)
-        iv = G.rmsprop_intervals(p, g, v, buf, **a)
+        iv = BT.rmsprop_intervals(p, g, v, buf, **a)
         _rejected(lambda: _opt_check(emu_rmsprop(p, g, v, buf, fault=fault, **a), iv, "rmsprop " + fault))
 
 
@@ -1115,7 +1122,7 @@ def test_sgd_faults_rejected(n, fault, step):
     p, g, m, v, buf = _opt_state(n)
     nest = fault == "no_nesterov"
     a = dict(lr=1e-2, momentum=0.9, dampening=0.0 if nest else 0.5, wd=0.0, nesterov=int(nest), step=step, gscale=1.0)
-    iv = G.sgd_intervals(p, g, buf, **a)
+    iv = BT.sgd_intervals(p, g, buf, **a)
     _opt_check(emu_sgd(p, g, buf, **a), iv, "sgd")
     _rejected(lambda: _opt_check(emu_sgd(p, g, buf, fault=fault, **a), iv, "sgd " + fault))
 
@@ -1128,9 +1135,9 @@ def test_ema_bound_and_the_old_p_fault():
         dd = torch.tensor(d, dtype=torch.float32)
         for fused in (False, True):
             got = _fma(dd.expand_as(ema), ema, (1.0 - dd) * pn) if fused else dd * ema + (1.0 - dd) * pn
-            _ok(G.check_ema(got, d, ema, pn, "ema", None))
+            _ok(BT.check_ema(got, d, ema, pn, "ema", None))
         old = dd * ema + (1.0 - dd) * p
-        _rejected(lambda: G.check_ema(old, d, ema, pn, "ema from the old p", None))
+        _rejected(lambda: BT.check_ema(old, d, ema, pn, "ema from the old p", None))
 
 
 # ---- the multi-label loss and HardDice (csrc/mnas_mlabel.hip) ---------------------------------------------------------------------------
@@ -1143,7 +1150,7 @@ ML_CAP = 4096 * 256
 
 
 def _ml_order(C_, vec):
-    T = G.mlabel_trips(C_, vec)
+    T = BM.mlabel_trips(C_, vec)
     k, l = np.arange(T)[:, None], np.arange(256)[None, :]
     idx = 1024 * (k // 4) + 4 * l + k % 4 if vec else 256 * k + l
     return np.where(idx < C_, idx, -1)
@@ -1165,7 +1172,7 @@ def emu_mlabel(z, t, w, focal, gamma, balance, vec, fused, fault=None):
             sg = F32(1) / (F32(1) + np.exp(-z))
         else:
             sg = np.where(z >= 0, F32(1) / d, ea / d)
-        inv = F32(1.0 / float(N)) if fault == "inv_N" else F32(G.mlabel_inv(N, C_))
+        inv = F32(1.0 / float(N)) if fault == "inv_N" else F32(BM.mlabel_inv(N, C_))
         df = sg - t
         dl = (ww * (ww * df)) * inv if fault == "w_twice" else df * inv if fault == "w_none" else (ww * df) * inv
     es, ws = e.copy(), ww
@@ -1207,29 +1214,29 @@ def emu_mlabel(z, t, w, focal, gamma, balance, vec, fused, fault=None):
 def _ml_check(z, t, w, focal, gamma, balance, vec, fused=False, fault=None, only=None):
     got = emu_mlabel(z, t, w, focal, gamma, balance, vec, fused, fault)
     N, C_ = z.shape
-    iv = G.mlabel_intervals(z, t, w, N, C_, focal, gamma, balance, vec, rows_dev=got["rows"])
+    iv = BM.mlabel_intervals(z, t, w, N, C_, focal, gamma, balance, vec, rows_dev=got["rows"])
     r = 0.0
     for k in ("dl", "rows", "loss", "s"):
         if got[k] is not None and (only is None or k in only):
-            r = max(r, G.check_iv(got[k], iv[k], "mlabel " + k, None))
+            r = max(r, IV.check_interval(got[k], iv[k], "mlabel " + k, None))
     return r
 
 
 ML_VARIANTS = (("plain", False, False), ("weighted", True, False), ("focal", False, True), ("weighted_focal", True, True))
 
 
-@pytest.mark.parametrize("N,Cn", G.ML_SHAPES)
+@pytest.mark.parametrize("N,Cn", BM.ML_SHAPES)
 def test_mlabel_emulations_inside_bracket(N, Cn):
     worst = 0.0
-    for ki, kind in enumerate(G.ML_KINDS):
-        z, t, w = G.mlabel_inputs(kind, N, Cn)
-        gamma, balance = G.ML_FOCAL[ki % 3]
+    for ki, kind in enumerate(BM.ML_KINDS):
+        z, t, w = BM.mlabel_inputs(kind, N, Cn)
+        gamma, balance = BM.ML_FOCAL[ki % 3]
         for name, weighted, focal in ML_VARIANTS:
             for vec in ((False, True) if Cn % 4 == 0 else (False,)):
                 for fused in (False, True):
                     worst = max(worst, _ml_check(z, t, w if weighted else None, focal, gamma, balance, vec, fused))
         if kind == "sparse":
-            G.mlabel_probe_visible(G.mlabel_intervals(z, t, w, N, Cn, False, 2.0, 0.25, Cn % 4 == 0), G.mlabel_live(N, Cn), "sparse")
+            BM.mlabel_probe_visible(BM.mlabel_intervals(z, t, w, N, Cn, False, 2.0, 0.25, Cn % 4 == 0), BM.mlabel_live(N, Cn), "sparse")
     print("N %d C %d: worst emulation / bracket %.3f" % (N, Cn, worst))
     assert worst <= 1.0
 
@@ -1249,8 +1256,8 @@ def test_mlabel_faults_rejected(fault, N, Cn, kind, weighted, focal, vec, only):
     """each fault on the inputs of tests/test_gpu_multilabel.py::test_bounds; `only`: the output that must show it.  log_not_log1p
     on the confident batch gives rows of exactly 0, which also pass every max-normalised tolerance.  other_sigmoid:
     1 / (1 + expf(-z)) at z = -90 is 1 / inf = 0 where ea / (1 + ea) is 8.2e-40."""
-    z, t, w = G.mlabel_inputs(kind, N, Cn)
-    gamma, balance = G.ML_FOCAL[1]
+    z, t, w = BM.mlabel_inputs(kind, N, Cn)
+    gamma, balance = BM.ML_FOCAL[1]
     for fused in (False, True):
         _ok(_ml_check(z, t, w if weighted else None, focal, gamma, balance, vec, fused))
         _rejected(lambda: _ml_check(z, t, w if weighted else None, focal, gamma, balance, vec, fused, fault, only=(only,)))
@@ -1261,12 +1268,12 @@ def test_mlabel_confident_focal_smallest_b():
     about 2^-52 / b relative and still admits the emulation; prints the smallest b and the bracket's relative width there"""
     small = (1.0, 0.0)
     for (N, Cn) in ((2, 1000), (3, 1027)):
-        z, t, w = G.mlabel_inputs("confident", N, Cn)
-        for gamma, balance in G.ML_FOCAL:
+        z, t, w = BM.mlabel_inputs("confident", N, Cn)
+        for gamma, balance in BM.ML_FOCAL:
             got = emu_mlabel(z, t, None, True, gamma, balance, Cn % 4 == 0, False)
-            iv = G.mlabel_intervals(z, t, None, N, Cn, True, gamma, balance, Cn % 4 == 0, rows_dev=got["rows"])
+            iv = BM.mlabel_intervals(z, t, None, N, Cn, True, gamma, balance, Cn % 4 == 0, rows_dev=got["rows"])
             for k in ("dl", "rows", "loss", "s"):
-                _ok(G.check_iv(got[k], iv[k], "confident focal " + k, None))
+                _ok(IV.check_interval(got[k], iv[k], "confident focal " + k, None))
             b = float(iv["b"].mid)
             small = min(small, (b, float(iv["s"].half / iv["s"].mid.abs())))
     print("smallest b %.3g, relative half width of s there %.3g" % small)
@@ -1276,9 +1283,9 @@ def test_mlabel_confident_focal_smallest_b():
 @pytest.mark.parametrize("fault", ["scale_none_beyond", "scale_twice_beyond"])
 def test_mlabel_scale_second_trip_faults_rejected(fault):
     """the (1100, 1000) focal batch: the factor s not applied, and applied twice, from element 4096*256 on"""
-    N, Cn = G.ML_BIG
-    z, t, w = G.mlabel_inputs("scale8", N, Cn)
-    gamma, balance = G.ML_FOCAL[1]
+    N, Cn = BM.ML_BIG
+    z, t, w = BM.mlabel_inputs("scale8", N, Cn)
+    gamma, balance = BM.ML_FOCAL[1]
     _ok(_ml_check(z, t, w, True, gamma, balance, True, False, only=("dl",)))
     _rejected(lambda: _ml_check(z, t, w, True, gamma, balance, True, False, fault, only=("dl",)))
 
@@ -1311,16 +1318,16 @@ def test_dice_emulation_and_faults():
     4u; here 6 / 2^25 and 14 / 2^25 of 2I) -- rejected on both."""
     for (I, P, T) in DICE_COUNTS:
         for deduct in (0, 1):
-            _ok(G.check_iv(emu_dice(I, P, T, deduct), G.dice_interval(I, P, T, deduct), "dice %r" % ((I, P, T, deduct),), None))
-    assert float(emu_dice(7, 7, 7, 0)) == 1.0 and float(G.dice_interval(7, 7, 7, 0).hi) == 1.0
-    assert float(G.dice_interval(7, 7, 7, 1).lo) == 1.0                                         # deduct pushes it above 1: clamped
-    assert float(G.dice_interval(18394, 50000, 50000, 0).lo) > 0.0 and float(G.dice_interval(18394, 50000, 50001, 0).hi) == 0.0
+            _ok(IV.check_interval(emu_dice(I, P, T, deduct), BM.dice_interval(I, P, T, deduct), "dice %r" % ((I, P, T, deduct),), None))
+    assert float(emu_dice(7, 7, 7, 0)) == 1.0 and float(BM.dice_interval(7, 7, 7, 0).hi) == 1.0
+    assert float(BM.dice_interval(7, 7, 7, 1).lo) == 1.0                                         # deduct pushes it above 1: clamped
+    assert float(BM.dice_interval(18394, 50000, 50000, 0).lo) > 0.0 and float(BM.dice_interval(18394, 50000, 50001, 0).hi) == 0.0
     for (I, P, T) in ((18394, 50000, 50000), (40, 90, 130)):
-        _rejected(lambda: G.check_iv(emu_dice(I, P, T, 1, "no_deduct"), G.dice_interval(I, P, T, 1), "dice, U not reduced", None))
+        _rejected(lambda: IV.check_interval(emu_dice(I, P, T, 1, "no_deduct"), BM.dice_interval(I, P, T, 1), "dice, U not reduced", None))
     n = 4100 * 4100
     for (I, P, T) in ((n - 5, n - 3, n - 2), (2 ** 24 + 7, 2 ** 24 + 7 + 28782777, 2 ** 24 + 7 + 28782777)):
         assert 2 * I > 2 ** 25 and float(F32(2 * I)) != 2 * I
-        iv = G.dice_interval(I, P, T, 0)
+        iv = BM.dice_interval(I, P, T, 0)
         for fault in ("2I_exact", "2I_trunc24"):
-            _ok(G.check_iv(emu_dice(I, P, T, 0, fault), iv, "dice, %s (not separable)" % fault, None))
-        _rejected(lambda: G.check_iv(emu_dice(I, P, T, 0, "2I_trunc23"), iv, "dice, (float)(2I) cut to 23 bits", None))
+            _ok(IV.check_interval(emu_dice(I, P, T, 0, fault), iv, "dice, %s (not separable)" % fault, None))
+        _rejected(lambda: IV.check_interval(emu_dice(I, P, T, 0, "2I_trunc23"), iv, "dice, (float)(2I) cut to 23 bits", None))

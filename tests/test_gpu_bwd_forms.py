@@ -7,7 +7,7 @@ backward on a masked gradient.  Part 2: the distinct launches of the bench confi
 replayed standalone with the production integers against fp64 references computed on the device.
 
 Every output and partial table lives in a guarded buffer (tests/gpu_util.py): a write outside it, or an element never written,
-fails the test.  On top of the max-normalised tolerances every launch is held to the derived bounds of tests/gpu_util.py: the
+fails the test.  On top of the max-normalised tolerances every launch is held to the derived bounds of tests/bounds_conv.py: the
 input gradients element by element (check_onload_bound over the dy-on-load interval, check_dw_bound for the sweeps), the weight
 gradients and fused reduces per element / channel (check_sum_bound, check_red_bound), the merged finalize launch per channel and
 per weight (bn_bwd_finalize_intervals, check_sum_bound) and bit for bit to the standalone finalizes on the same tables.  Where include/mnas.h promises bit-identical results (RECOMP vs the stored y, masked vs plain gradients, grid
@@ -18,15 +18,17 @@ import pytest
 import torch
 
 from cases import O
-from gpu_util import (HINGE, Interval, L, act_in, act_interval, bf16r, bits_equal, bn_bwd_finalize_intervals, check_dw_bound,
-                      check_interval, check_onload_bound, check_red_bound, check_sum_bound, conv_gemm, dw_dgrad_terms, dw_wgrad_terms, dy_interval, grad_in, guarded,
-                      off_hinge, onload_dgrad_terms, pack, rand_bn_coefs, ref_dense_s2_dgrad, ref_dw_dgrad, ref_dw_wgrad,
-                      ref_dy, relerr, relu_mask, zero_on_hinge)
+from bounds_conv import (HINGE, act_interval, check_dw_bound, check_onload_bound, check_red_bound, dw_dgrad_terms, dw_wgrad_terms,
+                         dy_interval, off_hinge, onload_dgrad_terms, relu_mask, zero_on_hinge)
+from bounds_se import bn_bwd_finalize_intervals
+from gpu_util import L, act_in, bf16r, bits_equal, conv_gemm, grad_in, guarded, pack, rand_bn_coefs, relerr
+from intervals import Interval, check_interval, check_sum_bound
+from refs64 import ref_dense_dgrad, ref_dw_dgrad, ref_dw_wgrad, ref_dy
 from test_gpu_kernels import DW, PWB, TOL_BF16, TOL_F32
 
 pytestmark = pytest.mark.gpu
 TOL_RED = 1e-3          # fused BatchNorm-backward reduce sums (as test_pw_dgrad)
-_off_hinge = off_hinge  # (gpu_util: inputs are moved off the ReLU hinge |s*v+t| < HINGE, host and device then agree on every mask bit)
+_off_hinge = off_hinge  # (bounds_conv: inputs are moved off the ReLU hinge |s*v+t| < HINGE, host and device then agree on every mask bit)
 assert HINGE == 1e-3
 BOUND_ELEMS = 16 << 20  # fp64 elements of one operand chunk of the per-element bounds
 
@@ -114,7 +116,7 @@ def test_tconv_dgrad(case, fused_red):
         assert lib.mnas_tconv_parts(31, Ho, Wo, Co, Ci) == -1
     dy = _x((N, Ho, Wo, Co), 3)
     w = bf16r(O.det_param("t.conv.weight", (Co, Ci, 3, 3), 2))
-    ref = ref_dense_s2_dgrad(dy, w, H, W)
+    ref = ref_dense_dgrad(dy, w, H, W, stride=2, pad=1)
     dyd = dy.to(torch.bfloat16).cuda()
     wp = pack(w, L.PACK_TCONV)
     red = None
@@ -335,7 +337,7 @@ def _bn_task(C_, nparts, seed, table="uniform"):
             assert relerr(got[r], bn2[r].cpu().double()) < 1e-6, (what, "bnbuf row", r)
         for r in (0, 1, 5, 6):
             assert torch.equal(got[r], b[r].double()), (what, "bnbuf row %d changed" % r)
-        # every channel inside the brackets of the table as given (fp64 on the fp32 partials; gpu_util.bn_bwd_finalize_intervals)
+        # every channel inside the brackets of the table as given (fp64 on the fp32 partials; bounds_se.bn_bwd_finalize_intervals)
         ivs = bn_bwd_finalize_intervals(partial, count, b, g0, b0)
         fin = {"c1": bnbuf[2], "c2": bnbuf[3], "c3": bnbuf[4], "dgamma": dg, "dbeta": db}
         worst = max(check_interval(fin[k].cpu(), iv, "%s %s (%s table)" % (what, k, table), FAMILY_POST) for k, iv in ivs.items())
@@ -892,7 +894,7 @@ def _replay_tconv(ints, flags, gen, N):
         bn[0], bn[1], bn[5], bn[6] = 1 + 0.3 * _rand(gen, Ci), 0.2 * _rand(gen, Ci), 0.1 * _rand(gen, Ci), 1 + 0.2 * _rand(gen, Ci).abs()
         red = (bf16r(_rand(gen, N, 2 * Ho, 2 * Wo, Ci)).to(torch.bfloat16), bn)
     out, st = _tconv_launch(lib, N, Ho, Wo, Co, Ci, dyd, wp, nparts, red)
-    ref = ref_dense_s2_dgrad(dy, w, 2 * Ho, 2 * Wo, device="cuda")
+    ref = ref_dense_dgrad(dy, w, 2 * Ho, 2 * Wo, stride=2, pad=1, device="cuda")
     assert relerr(out.double(), ref) < TOL_BF16, ("tconv", ints, relerr(out.double(), ref))
     del ref
     if red is not None:

@@ -138,10 +138,11 @@ def test_bn_bwd_finalize_frozen(Cn, nparts):
 
 @pytest.mark.parametrize("nparts", [3, 1024, 1025])
 def test_bn_bwd_finalize_frozen_brackets(nparts):
-    """dgamma, dbeta and dbias inside the brackets of gpu_util.bn_bwd_finalize_intervals (fp64 on the fp32 table as given).  Up to
+    """dgamma, dbeta and dbias inside the brackets of bounds_se.bn_bwd_finalize_intervals (fp64 on the fp32 table as given).  Up to
     1024 partials every fp32 accumulator of bn_partial_sums holds one term and the bracket is _check_sums' one rounding; 1025 is
     the first table with two terms in an accumulator, which _check_sums' exact-sum model does not describe."""
-    from gpu_util import bn_bwd_finalize_intervals, check_interval
+    from bounds_se import bn_bwd_finalize_intervals
+    from intervals import check_interval
     lib = L.load()
     Cn = 24
     for acc in (0, 1):
@@ -171,11 +172,12 @@ def _wg_task(kind, seed):
 @pytest.mark.parametrize("Cn", [8, 24, 576])
 def test_bwd_post_frozen(Cn, nparts):
     """merged twin, with and without weight-gradient tasks riding in the launch; those are mnas_bwd_post's, bit for bit.  dgamma,
-    dbeta and dbias of every channel inside gpu_util.bn_bwd_finalize_intervals of the table as given and bit-equal to the
+    dbeta and dbias of every channel inside bounds_se.bn_bwd_finalize_intervals of the table as given and bit-equal to the
     standalone mnas_bn_bwd_finalize_frozen's (the same bn_bwd_finalize_body<TPC, true>); the weight gradients inside
     check_sum_bound (M = nsplit, c = 1, the accumulate target the +1).  hard: every channel of the table times a power of two
     2^-20..2^4 and the last channel exact zeros."""
-    from gpu_util import bn_bwd_finalize_intervals, check_interval, check_sum_bound
+    from bounds_se import bn_bwd_finalize_intervals
+    from intervals import check_interval, check_sum_bound
     lib = L.load()
     for tasks, hard in ((False, False), (True, False), (True, True)):
         partial, bnbuf, old, sums = _post_inputs(Cn, nparts, 300 + int(tasks))
@@ -259,7 +261,8 @@ class _FrozenBn:
     def check(self, what):
         """guards; bnbuf bitwise untouched; every channel of dgamma, dbeta, dbias inside bn_bwd_finalize_intervals(frozen) of the
         table as given and bit-equal to mnas_bn_bwd_finalize_frozen (the same bn_bwd_finalize_body<64 | 256, true>)"""
-        from gpu_util import bn_bwd_finalize_intervals, check_interval
+        from bounds_se import bn_bwd_finalize_intervals
+        from intervals import check_interval
         self.pchk(what + " partial")
         self.bchk(what + " bnbuf")
         bits_equal(self.bnbuf.cpu(), self.b, what + ": bnbuf")

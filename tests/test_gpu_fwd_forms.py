@@ -8,8 +8,8 @@ the reciprocal to exact division.  Part 2: the distinct forward / weight-gradien
 configuration's two training Programs (float and uint8 input), replayed standalone with the production integers.
 
 Every output, statistics table and partial slab lives in a guarded buffer (tests/gpu_util.py).  References are fp64, built from
-slicing and matmul (gpu_util.ref_*), on the device.  Launches whose operand needs no transform on load are held to the
-per-element bound of gpu_util.check_gemm_bound; those with act-on-load / dy-on-load to gpu_util.check_onload_bound over the
+slicing and matmul (refs64.ref_*), on the device.  Launches whose operand needs no transform on load are held to the
+per-element bound of bounds_conv.check_gemm_bound; those with act-on-load / dy-on-load to bounds_conv.check_onload_bound over the
 operand's interval (the same bound plus the interval's slack), their statistics to check_stats_bound, their fused reduce to
 check_red_bound; the depthwise forward with fp32 weights to check_dw_bound.  The max-normalised tolerances are asserted as well."""
 import ctypes as C
@@ -18,10 +18,11 @@ from fractions import Fraction
 import pytest
 import torch
 
-from gpu_util import (Interval, L, act_in, act_interval, bf16r, bits_equal, check_dw_bound, check_gemm_bound, check_onload_bound,
-                      check_red_bound, check_sum_bound, conv_gemm, dw_elem_err, dw_fwd_terms, dy_interval, grad_in, guarded,
-                      onload_dgrad_terms, onload_elem_err, onload_fwd_terms, pack, ref_dense_dgrad, ref_dense_fwd, ref_dense_wgrad,
-                      ref_dw_fwd_s, ref_dy, ref_stem, ref_stem_wgrad, relerr, route_of, stats_bound_terms)
+from bounds_conv import (act_interval, check_dw_bound, check_gemm_bound, check_onload_bound, check_red_bound, dw_elem_err, dw_fwd_terms,
+                         dy_interval, onload_dgrad_terms, onload_elem_err, onload_fwd_terms, stats_bound_terms)
+from gpu_util import L, act_in, bf16r, bits_equal, conv_gemm, grad_in, guarded, pack, relerr, route_of
+from intervals import Interval, check_sum_bound
+from refs64 import ref_dense_dgrad, ref_dense_fwd, ref_dense_wgrad, ref_dw_fwd, ref_dy, ref_stem, ref_stem_wgrad
 from test_gpu_bwd_forms import _cdiv, _check_red, _off_hinge, _rand
 from test_gpu_kernels import DENSE, DW, PW, TOL_BF16, TOL_F32
 
@@ -569,8 +570,8 @@ def _dw_check(out, st, a, w, bias, k, stride, what, plain, act=None):
     sterms = None
     for n0, n1 in _img_chunks(N, a[0].numel()):
         if plain:
-            ref = ref_dw_fwd_s(a[n0:n1], w, bias, stride, device="cuda")
-            S = ref_dw_fwd_s(a[n0:n1].abs(), w.abs(), bias.abs(), stride, device="cuda")
+            ref = ref_dw_fwd(a[n0:n1], w, bias, stride, device="cuda")
+            S = ref_dw_fwd(a[n0:n1].abs(), w.abs(), bias.abs(), stride, device="cuda")
             check_gemm_bound(out[n0:n1], ref, S, k * k, "%s images %d..%d" % (what, n0, n1))
         else:
             iv = act_interval(act[0][n0:n1], act[1], act[2], False, "cuda") if act is not None else Interval.exact(a[n0:n1], "cuda")
@@ -827,7 +828,7 @@ def _replay_wgrad(ints, flags, gen):
     gchk(what + " dW")
     ref = torch.zeros((Co, Ci, k, k), dtype=torch.float64, device="cuda")
     # check_sum_bound (c = 1) over the operands' bf16 intervals, chunk by chunk: ref over the interval mids, S over the largest
-    # magnitudes, slack = S - sum |mid||mid| (gpu_util.wgrad_terms, accumulated over the image chunks)
+    # magnitudes, slack = S - sum |mid||mid| (bounds_conv.wgrad_terms, accumulated over the image chunks)
     r64, S, Sm = torch.zeros_like(ref), torch.zeros_like(ref), torch.zeros_like(ref)
     for n0, n1 in _img_chunks(N, max(Hi * Wi * Ci, Ho * Wo * Co)):
         xs = x[n0:n1].float()

@@ -275,13 +275,13 @@ def test_ema_per_element(d, clip):
 @pytest.mark.parametrize("n", [1, 255, 257, 10007, 2048 * 256 + 300])
 @pytest.mark.parametrize("kind", ["adam", "rmsprop", "sgd"])
 def test_ex_kernels_per_element_bracket(kind, n):
-    """ONE launch of mnas_<kind>_step_ex from a given state (gpu_util.opt_case) with the fp64 partial table handed in directly
+    """ONE launch of mnas_<kind>_step_ex from a given state (bounds_tail.opt_case) with the fp64 partial table handed in directly
     (three values whose sum is exact in any order, so norm and coef are gradclip_ref's): clip active (coef < 1: gi takes one more
     rounding) and inactive, EMA off / decay 0 / decay 0.999, at element offsets 1 and 3 of guarded buffers; then a NaN and an
     Inf table under skip_nonfinite: every buffer bitwise untouched, steps and skipped_steps move."""
-    import gpu_util as G
-    assert G.OPT_SIZES[-1] > G.OPT_GRID_CAP == 2048 * 256 and n in G.OPT_SIZES
-    p, g, m, v, buf = G.opt_data(n, seed=n + 1)
+    import bounds_tail as BT
+    assert BT.OPT_SIZES[-1] > BT.OPT_GRID_CAP == 2048 * 256 and n in BT.OPT_SIZES
+    p, g, m, v, buf = BT.opt_data(n, seed=n + 1)
     st = dict(p=p, g=g, m=m, v=v, buf=buf, ema=p * 0.75 + 0.01)
     a = {"adam": dict(lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, wd=1e-2, step=2, gscale=0.125),
          "rmsprop": dict(lr=1e-2, alpha=0.99, eps=1e-8, wd=1e-2, momentum=0.9, gscale=1.0 / 3),
@@ -291,9 +291,9 @@ def test_ex_kernels_per_element_bracket(kind, n):
     for max_norm in (0.9, 1e3):
         for ema, decay in ((False, 0.0), (True, 0.0), (True, 0.999)):
             ex = dict(partial=table, max_norm=max_norm, skip=1, ema=ema, decay=decay)
-            worst, k = max(worst, G.opt_case(kind, st, a, (1, 3)[k % 2], ex, family="optimizers, _ex")), k + 1
+            worst, k = max(worst, BT.opt_case(kind, st, a, (1, 3)[k % 2], ex, family="optimizers, _ex")), k + 1
     for bad in (float("nan"), float("inf")):
-        G.opt_case(kind, st, a, 1, dict(partial=[2.25, bad, 0.0625], max_norm=0.9, skip=1, ema=True, decay=0.999))
+        BT.opt_case(kind, st, a, 1, dict(partial=[2.25, bad, 0.0625], max_norm=0.9, skip=1, ema=True, decay=0.999))
     print("%s_ex n %d: worst error / bracket %.3f" % (kind, n, worst))
     assert worst <= 1.0
 

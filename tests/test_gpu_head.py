@@ -2,7 +2,7 @@
 (oracle.head_forward_masked / F.cross_entropy, fp32) -- classifiers.py:56-89,107-111 and train.py:277,434-439.
 Tolerances: fp32 products over K <= 1000 in a different summation order than ATen's: 2e-5 relative to the tensor's
 max; the dropout keep mask must equal the oracle's restatement of the hash bit for bit.  Next to those: per-element bounds for
-the three GEMM entry points and brackets for the cross-entropy kernels (gpu_util.head_gemm_interval, ce_intervals; DESIGN.md
+the three GEMM entry points and brackets for the cross-entropy kernels (bounds_tail.head_gemm_interval, ce_intervals; DESIGN.md
 section 6), which see an error in a small element next to a large one."""
 import ctypes as Ct
 
@@ -11,8 +11,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import bounds_tail as BT
 import cases as C
 import gpu_util as G
+import intervals as IV
 from cases import O
 from gpu_util import relerr
 from mnasnet_pytorch_amd import _lib as L
@@ -114,7 +116,7 @@ def test_cross_entropy(N, Cn):
     assert int(bad) == 1 and torch.isnan(loss).item()
 
 
-# ---- per-element bounds (gpu_util.head_gemm_interval / head_rowsum_interval / ce_intervals; tests/test_bounds_cpu.py proves on the
+# ---- per-element bounds (bounds_tail.head_gemm_interval / head_rowsum_interval / ce_intervals; tests/test_bounds_cpu.py proves on the
 # CPU that they admit the kernels' arithmetic and reject the listed faults) ---------------------------------------------------------
 def _at(t, offset=0):
     """t on the device as a view at element `offset` of a larger buffer (offset 1: a 4-byte, not 16-byte, aligned address)"""
@@ -138,10 +140,10 @@ class _HeadCase:
     def __init__(self, N, I, O_, p, scaled, off_in=0, off_out=0, off_x=None):
         self.N, self.I, self.O, self.p = N, I, O_, p
         self.seed = 0x1234567890ABCDEF ^ (N * 7919 + I)
-        self.x, self.w, self.b, self.dz, self.u_prev, self.c0w, self.c0b = G.head_inputs(N, I, O_, scaled)
+        self.x, self.w, self.b, self.dz, self.u_prev, self.c0w, self.c0b = BT.head_inputs(N, I, O_, scaled)
         self.keep = _keep(self.seed, N, I, p)
-        self.xd = G.head_dropped(self.x, self.keep, p)
-        self.post = self.keep.double() * G.head_drop_scale(p) if p else None
+        self.xd = BT.head_dropped(self.x, self.keep, p)
+        self.post = self.keep.double() * BT.head_drop_scale(p) if p else None
         self.off_out = off_out
         self.xc = _at(self.x, off_in if off_x is None else off_x)
         self.wc, self.bc, self.dzc, self.uc = (_at(t, off_in) for t in (self.w, self.b, self.dz, self.u_prev))
@@ -156,9 +158,9 @@ class _HeadCase:
         a.y = y.data_ptr()
         L.check(L.load().mnas_head_linear_fwd(Ct.byref(a), L.cur_stream()))
         chk(self.tag + " y")
-        iv = G.head_gemm_interval(self.xd if A is None else A, self.w.t(), self.b if bias else None, relu=relu)
+        iv = BT.head_gemm_interval(self.xd if A is None else A, self.w.t(), self.b if bias else None, relu=relu)
         # (an output the ReLU clamps sits exactly on the lower end of its bracket, ratio 1: a family of its own)
-        return G.check_interval(y.cpu(), iv, "%s fwd relu %d bias %d" % (self.tag, relu, bias), "head gemm, ReLU" if relu else "head gemm"), iv
+        return IV.check_interval(y.cpu(), iv, "%s fwd relu %d bias %d" % (self.tag, relu, bias), "head gemm, ReLU" if relu else "head gemm"), iv
 
     def bwd_w(self, acc, B=None, dz=None):
         dw, cw = _out((self.O, self.I), self.c0w if acc else None, self.off_out)
@@ -169,9 +171,9 @@ class _HeadCase:
         cw(self.tag + " dw")
         cb(self.tag + " db")
         dzt = (self.dz if dz is None else dz).t()
-        iv = G.head_gemm_interval(dzt, self.xd if B is None else B, C0=self.c0w if acc else None)
-        r = G.check_interval(dw.cpu(), iv, "%s dW acc %d" % (self.tag, acc), "head gemm")
-        rb = G.check_interval(db.cpu(), G.head_rowsum_interval(dzt, self.c0b if acc else None), "%s db acc %d" % (self.tag, acc),
+        iv = BT.head_gemm_interval(dzt, self.xd if B is None else B, C0=self.c0w if acc else None)
+        r = IV.check_interval(dw.cpu(), iv, "%s dW acc %d" % (self.tag, acc), "head gemm")
+        rb = IV.check_interval(db.cpu(), BT.head_rowsum_interval(dzt, self.c0b if acc else None), "%s db acc %d" % (self.tag, acc),
                               "head rowsum")
         return max(r, rb), iv
 
@@ -183,12 +185,12 @@ class _HeadCase:
         L.check(L.load().mnas_head_linear_bwd_x(Ct.byref(a), L.cur_stream()))
         chk(self.tag + " dx")
         mask = self.u_prev > 0 if masked else None
-        iv = G.head_gemm_interval(self.dz if dz is None else dz, self.w, post=self.post, mask=mask)
+        iv = BT.head_gemm_interval(self.dz if dz is None else dz, self.w, post=self.post, mask=mask)
         got = dx.cpu()
         if masked:
             assert bool((got[~mask] == 0).all()), self.tag + ": dx not exactly 0 under a zero of the mask source"
             assert bool((self.u_prev == 0).any()) and (self.u_prev.numel() < 3 or bool((self.u_prev == 2.0 ** -149).any()))
-        return G.check_interval(got, iv, "%s dx masked %d" % (self.tag, masked), "head gemm"), iv
+        return IV.check_interval(got, iv, "%s dx masked %d" % (self.tag, masked), "head gemm"), iv
 
     def all(self):
         self.fwd(True)
@@ -197,19 +199,19 @@ class _HeadCase:
         return max(r)
 
 
-@pytest.mark.parametrize("N,I,O_", G.HEAD_SIZES)
-@pytest.mark.parametrize("p", G.HEAD_PS)
+@pytest.mark.parametrize("N,I,O_", BT.HEAD_SIZES)
+@pytest.mark.parametrize("p", BT.HEAD_PS)
 def test_linear_per_element_bound(N, I, O_, p):
     """EVERY element of y, dW, db, dx inside (L + 10) 2^-23 S of the fp64 result over the staged fp32 operands (derivation:
-    gpu_util.head_gemm_interval / head_rowsum_interval), plain inputs and inputs whose rows and columns are scaled by powers of
+    bounds_tail.head_gemm_interval / head_rowsum_interval), plain inputs and inputs whose rows and columns are scaled by powers of
     two 2^-12 .. 2^12 (most outputs far below the tensor's maximum); bias NULL; dx exactly 0 where the
     mask source is +0.0 / -0.0 and not where it is the smallest subnormal; outputs inside canaries."""
     worst = max(_HeadCase(N, I, O_, p, scaled).all() for scaled in (False, True))
-    print("head (%d, %d, %d) p %g: worst error / bound %.3f" % (N, I, O_, p, worst), G.WORST)
+    print("head (%d, %d, %d) p %g: worst error / bound %.3f" % (N, I, O_, p, worst), IV.WORST)
     assert worst <= 1.0
 
 
-@pytest.mark.parametrize("N,I,O_", [s for s in G.HEAD_SIZES if s[1] % 4 == 0])
+@pytest.mark.parametrize("N,I,O_", [s for s in BT.HEAD_SIZES if s[1] % 4 == 0])
 def test_linear_unaligned_operands(N, I, O_):
     """The sizes at which k_head_gemm<true> (16-byte loads) is eligible, with every operand and output at element offset 1 of
     its buffer (what Trainer's views of the flat parameter buffer look like behind a 10-class bias): k_head_gemm<false> on
@@ -228,19 +230,19 @@ def test_linear_sparse_probe():
     asserted to exceed twice the bound at one of the probed rows {0, 31, 32, M-1} x columns {0, 31, 32, N-1}."""
     N, I, O_ = 130, 133, 131
     c = _HeadCase(N, I, O_, 0.0, False)
-    x = G.head_sparse(c.x, 1, I)
+    x = BT.head_sparse(c.x, 1, I)
     c.xc = x.cuda()
     r, iv = c.fwd(False, A=x)
-    G.head_probe_visible(x, c.w.t(), iv, "fwd")
+    BT.head_probe_visible(x, c.w.t(), iv, "fwd")
     c = _HeadCase(N, I, O_, 0.0, False)
-    dz = G.head_sparse(c.dz, 0, N)
+    dz = BT.head_sparse(c.dz, 0, N)
     c.dzc = dz.cuda()
     r2, iv = c.bwd_w(0, dz=dz)
-    G.head_probe_visible(dz.t(), c.x, iv, "dW")
-    dz = G.head_sparse(c.dz, 1, O_)
+    BT.head_probe_visible(dz.t(), c.x, iv, "dW")
+    dz = BT.head_sparse(c.dz, 1, O_)
     c.dzc = dz.cuda()
     r3, iv = c.bwd_x(False, dz=dz)
-    G.head_probe_visible(dz, c.w, iv, "dx")
+    BT.head_probe_visible(dz, c.w, iv, "dx")
     print("head sparse probes: error / bound %.3f %.3f %.3f" % (r, r2, r3))
 
 
@@ -256,38 +258,38 @@ def _ce_run(x, t, meters=None):
     return dl.cpu(), rows.cpu(), loss.cpu(), int(bad)
 
 
-@pytest.mark.parametrize("N,Cn", G.CE_SIZES)
+@pytest.mark.parametrize("N,Cn", BT.CE_SIZES)
 def test_cross_entropy_per_element_bracket(N, Cn):
-    """EVERY dlogits element, every loss row and the mean inside the bracket gpu_util.ce_intervals / ce_mean_interval propagate
+    """EVERY dlogits element, every loss row and the mean inside the bracket bounds_tail.ce_intervals / ce_mean_interval propagate
     through k_head_ce's own roundings (expf, logf and the divisions at one ulp); N > 256 takes the count loop's and the mean's
     second trip; peaked rows, a common offset of +-1000 (logf(se) + mx - x[t] cancels), -inf logits, C = 1; ignored rows have
     exactly zero gradient; every row ignored: NaN loss, zero gradient."""
     worst = 0.0
-    for kind in G.CE_ROWS:
-        x = G.ce_logits(kind, N, Cn)
-        for how in G.CE_IGNORE:
-            t = G.ce_ignore(G.ce_targets(N, Cn)[0], how)
+    for kind in BT.CE_ROWS:
+        x = BT.ce_logits(kind, N, Cn)
+        for how in BT.CE_IGNORE:
+            t = BT.ce_ignore(BT.ce_targets(N, Cn)[0], how)
             dl, rows, loss, bad = _ce_run(x, t)
             what = "ce %s / %s (%d, %d)" % (kind, how, N, Cn)
-            iv = G.ce_intervals(x, t)
+            iv = BT.ce_intervals(x, t)
             assert bad == 0 and iv["count"] == int((t != -100).sum()), what
             assert bool((dl[t == -100] == 0).all()) and bool((rows[t == -100] == 0).all()), what
-            r = [G.check_iv(dl, iv["dl"], what + " dlogits", "cross-entropy"), G.check_iv(rows, iv["rows"], what + " rows", "cross-entropy"),
-                 G.check_ce_mean(loss, rows, iv["count"], what + " mean", "cross-entropy mean")]
+            r = [IV.check_interval(dl, iv["dl"], what + " dlogits", "cross-entropy"), IV.check_interval(rows, iv["rows"], what + " rows", "cross-entropy"),
+                 BT.check_ce_mean(loss, rows, iv["count"], what + " mean", "cross-entropy mean")]
             if how == "all":
                 assert bool(torch.isnan(loss)) and bool((dl == 0).all()), what
             worst = max(worst, *r)
     if N > 1:                        # `bad` as before: a label out of range is flagged, poisons the loss, has no gradient
-        x, t = G.ce_logits("uniform4", N, Cn), G.ce_targets(N, Cn)[0]
+        x, t = BT.ce_logits("uniform4", N, Cn), BT.ce_targets(N, Cn)[0]
         t[N // 2] = Cn
         dl, rows, loss, bad = _ce_run(x, t)
-        iv = G.ce_intervals(x, t)
+        iv = BT.ce_intervals(x, t)
         ok = ~iv["nan_rows"]
         assert bad == 1 and bool(torch.isnan(loss)) and bool(torch.isnan(rows[N // 2])) and int(ok.sum()) == N - 1
         assert bool((dl[N // 2] == 0).all())
-        G.check_iv(dl, iv["dl"], "ce refused row, dlogits", "cross-entropy")
-        G.check_iv(rows[ok], G.Interval(iv["rows"].lo[ok], iv["rows"].hi[ok]), "ce refused row, rows", "cross-entropy")
-    print("cross-entropy (%d, %d): worst error / bracket %.3f" % (N, Cn, worst), {k: round(v, 4) for k, v in G.WORST.items() if "entropy" in k})
+        IV.check_interval(dl, iv["dl"], "ce refused row, dlogits", "cross-entropy")
+        IV.check_interval(rows[ok], IV.Interval(iv["rows"].lo[ok], iv["rows"].hi[ok]), "ce refused row, rows", "cross-entropy")
+    print("cross-entropy (%d, %d): worst error / bracket %.3f" % (N, Cn, worst), {k: round(v, 4) for k, v in IV.WORST.items() if "entropy" in k})
     assert worst <= 1.0
 
 

@@ -4,10 +4,10 @@ max|hip - ref| <= 6e-3 * max|ref| for bf16 tensors and 2e-3 for fp32 reductions 
 gradients; limited by bf16 rounding of the staged operands, which the reference reproduces).
 
 On top of that, the conv / depthwise launches are held element by element (resp. channel by channel) to the derived bounds of
-tests/gpu_util.py against fp64 references on the device: check_onload_bound (MFMA launches, operand formed on load and known
+tests/bounds_conv.py against fp64 references on the device: check_onload_bound (MFMA launches, operand formed on load and known
 as an interval), check_dw_bound (depthwise sweeps, fp32 weights as given), check_sum_bound (weight gradients),
 check_stats_bound / check_red_bound (BatchNorm statistics, fused reduce).  Inputs that feed a ReLU mask are moved off the hinge
-(gpu_util.off_hinge).  The sparse-pixel probes at the end put a handful of live pixels at the first / last position and on
+(bounds_conv.off_hinge).  The sparse-pixel probes at the end put a handful of live pixels at the first / last position and on
 both sides of the tile and workgroup boundaries, where the same bounds see one dropped, doubled or misplaced pixel."""
 import ctypes as C
 
@@ -16,13 +16,14 @@ import torch
 import torch.nn.functional as F
 
 from cases import O
-from gpu_util import (Interval, L, act_in, act_interval, bf16r, check_dw_bound, check_onload_bound, check_red_bound,
-                      check_stats_bound, check_sum_bound, conv_gemm, dw_dgrad_terms, dw_elem_err, dw_fwd_terms, dw_wgrad_terms,
-                      dy_interval, dy_ref, from_nhwc, grad_in, guarded, nhwc, off_hinge, onload_dgrad_terms, onload_elem_err,
-                      onload_fwd_terms, pack, rand_bn_coefs, ref_dense_wgrad, relerr, wgrad_terms)
-from gpu_util import (U32, _assert_bound, add_act_interval, bn_bwd_finalize_intervals, bn_fwd_finalize_intervals, bn_fwd_partials,
-                      check_interval, check_store_bound, pool_act_terms, ref_dense_dgrad, stem_dgrad_terms, stem_wgrad_band_rows,
-                      sum_bound)
+from bounds_conv import (act_interval, check_dw_bound, check_onload_bound, check_red_bound, check_stats_bound, dw_dgrad_terms, dw_elem_err,
+                         dw_fwd_terms, dw_wgrad_terms, dy_interval, off_hinge, onload_dgrad_terms, onload_elem_err, onload_fwd_terms,
+                         wgrad_terms)
+from bounds_se import (add_act_interval, bn_bwd_finalize_intervals, bn_fwd_finalize_intervals, bn_fwd_partials, pool_act_terms,
+                       stem_dgrad_terms, stem_wgrad_band_rows)
+from gpu_util import L, act_in, bf16r, conv_gemm, dy_ref, from_nhwc, grad_in, guarded, nhwc, pack, rand_bn_coefs, relerr
+from intervals import U32, Interval, _assert_bound, check_interval, check_store_bound, check_sum_bound, sum_bound
+from refs64 import ref_dense_dgrad, ref_dense_wgrad
 
 pytestmark = pytest.mark.gpu
 TOL_BF16 = 6e-3
@@ -54,9 +55,9 @@ def _xoff(shape, seed, s, t):
                                              (8, 1, 64.0), (24, 256, 50176.0), (24, 257, 50176.0), (16, 1025, 802816.0), (8, 1, 1.0)])
 def test_bn_fwd_finalize(C_, nparts, count):
     """C_ channels of the distribution this test always had (mean ~ 0.3 u, var >= 0.5) under the max-normalised 1e-5, plus three
-    appended channels (gpu_util.bn_fwd_partials: |mean|/std = 30 and 300, a constant channel whose var takes the clamp); the table
+    appended channels (bounds_se.bn_fwd_partials: |mean|/std = 30 and 300, a constant channel whose var takes the clamp); the table
     is built in fp64 and rounded once to fp32, and ALL seven outputs of every channel are held to the brackets of
-    gpu_util.bn_fwd_finalize_intervals (fp64 on the fp32 table exactly as given to the kernel)."""
+    bounds_se.bn_fwd_finalize_intervals (fp64 on the fp32 table exactly as given to the kernel)."""
     lib = L.load()
     Ct = C_ + 3
     partial = bn_fwd_partials(O.det_uniform((2, Ct, nparts), 3), count)          # channel-major partial layout
@@ -620,7 +621,7 @@ def test_bn_bwd(C_, rows):
     L.check(lib.mnas_bn_bwd_finalize(partial.data_ptr(), nparts, C_, float(rows), bd.data_ptr(), dgamma.data_ptr(),
                                      dbeta.data_ptr(), 1, L.cur_stream()))
     assert relerr(dgamma.cpu() - 2.0, S2) < 1e-4 and relerr(dbeta.cpu() - 3.0, S1) < 1e-4
-    # the finalize alone: fp64 on the fp32 table the reduce wrote, brackets of gpu_util.bn_bwd_finalize_intervals
+    # the finalize alone: fp64 on the fp32 table the reduce wrote, brackets of bounds_se.bn_bwd_finalize_intervals
     ivs = bn_bwd_finalize_intervals(partial.cpu(), float(rows), b, torch.full((C_,), 2.0), torch.full((C_,), 3.0))
     fin = {"c1": bd[2], "c2": bd[3], "c3": bd[4], "dgamma": dgamma, "dbeta": dbeta}
     for k, iv in ivs.items():
@@ -686,38 +687,39 @@ def test_adam_matches_torch():
 
 
 def _opt_state(n):
-    import gpu_util as G
-    p, g, m, v, buf = G.opt_data(n, seed=n)
+    import bounds_tail as BT
+    p, g, m, v, buf = BT.opt_data(n, seed=n)
     return dict(p=p, g=g, m=m, v=v, buf=buf)
 
 
 @pytest.mark.parametrize("n", [1, 255, 257, 10007, 2048 * 256 + 300])
 def test_optimizer_per_element_bracket(n):
-    """ONE launch of mnas_adam_step / mnas_rmsprop_step / mnas_sgd_step from a given non-zero state (gpu_util.opt_case): every
+    """ONE launch of mnas_adam_step / mnas_rmsprop_step / mnas_sgd_step from a given non-zero state (bounds_tail.opt_case): every
     element of every output inside the bracket propagated through the kernel's own roundings, with per-element scales 2^-20 .. 2^4
     in p and g, exact zeros, elements with v = 0 and g = 0 (denom = eps) and with a tiny v; the runs start at element offsets 0, 1
     and 3 of guarded buffers.  The last size exceeds opt_blocks' grid of 2048 workgroups of 256, so a lane takes the grid-stride
     loop's second trip.  Adam: step 1 / 2 / 1000 / 100000, weight decay, grad_scale 1, 1/8, 1/3; RMSprop with and without momentum;
     SGD with momentum, dampening, Nesterov, first and second step."""
-    import gpu_util as G
-    assert G.OPT_SIZES[-1] > G.OPT_GRID_CAP == 2048 * 256 and n in G.OPT_SIZES
+    import bounds_tail as BT
+    import intervals as IV
+    assert BT.OPT_SIZES[-1] > BT.OPT_GRID_CAP == 2048 * 256 and n in BT.OPT_SIZES
     st = _opt_state(n)
     worst, k = 0.0, 0
     for step in (1, 2, 1000, 100000):
         for wd in (0.0, 1e-2):
             for gs in (1.0, 0.125, 1.0 / 3):
                 a = dict(lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, wd=wd, step=step, gscale=gs)
-                worst, k = max(worst, G.opt_case("adam", st, a, (0, 1, 3)[k % 3])), k + 1
+                worst, k = max(worst, BT.opt_case("adam", st, a, (0, 1, 3)[k % 3])), k + 1
     for mom in (0.0, 0.9):
         for wd in (0.0, 1e-2):
             a = dict(lr=1e-2, alpha=0.99, eps=1e-8, wd=wd, momentum=mom, gscale=1.0 / 3)
-            worst, k = max(worst, G.opt_case("rmsprop", st, a, (0, 1, 3)[k % 3])), k + 1
+            worst, k = max(worst, BT.opt_case("rmsprop", st, a, (0, 1, 3)[k % 3])), k + 1
         for damp in (0.0, 0.5):
             for nest in (0, 1):
                 for step in (1, 2):
                     a = dict(lr=1e-2, momentum=mom, dampening=damp, wd=1e-2 * nest, nesterov=nest, step=step, gscale=0.125)
-                    worst, k = max(worst, G.opt_case("sgd", st, a, (0, 1, 3)[k % 3])), k + 1
-    print("optimizers n %d: %d launches, worst error / bracket %.4f" % (n, k, worst), {"optimizers": G.WORST.get("optimizers")})
+                    worst, k = max(worst, BT.opt_case("sgd", st, a, (0, 1, 3)[k % 3])), k + 1
+    print("optimizers n %d: %d launches, worst error / bracket %.4f" % (n, k, worst), {"optimizers": IV.WORST.get("optimizers")})
     assert worst <= 1.0
 
 
@@ -755,7 +757,7 @@ def test_run_ops_batch():
 @pytest.mark.parametrize("C_,nparts", [(16, 1024), (40, 257), (1152, 64), (1152, 513), (8, 1), (24, 256), (16, 1025)])
 def test_bn_bwd_finalize_long_rows(C_, nparts):
     """Both finalize shapes (wave per channel / block per channel) against an fp64 sum of the same partial table; + the brackets of
-    gpu_util.bn_bwd_finalize_intervals on rows 2..4, dgamma and dbeta (1025 partials: two terms per fp32 accumulator)."""
+    bounds_se.bn_bwd_finalize_intervals on rows 2..4, dgamma and dbeta (1025 partials: two terms per fp32 accumulator)."""
     lib = L.load()
     partial = O.det_uniform((2, C_, nparts), 31)
     b = rand_bn_coefs(C_, 9, O)

@@ -8,8 +8,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import bounds_tail as BT
 import cases as C
 import gpu_util as G
+import intervals as IV
 import metrics_ref as MR
 import mix_ref as R
 from cases import O
@@ -161,7 +163,7 @@ def test_soft_cross_entropy_meters_rank_the_dominant_label(eps):
     assert 0 < rec.correct[1] < rec.correct[5] < rec.samples
 
 
-# ---- per-element brackets (gpu_util.ce_intervals: interval propagation through k_head_ce_soft's own roundings) ----------------------
+# ---- per-element brackets (bounds_tail.ce_intervals: interval propagation through k_head_ce_soft's own roundings) ----------------------
 def _lam_variants(N):
     i = torch.arange(N)
     per_row = torch.tensor([0.0, 0.5, 1.0, 0.3, 0.8125, 0.49999997])[i % 6]
@@ -170,9 +172,9 @@ def _lam_variants(N):
 
 
 def _soft_labels(N, Cn, how):
-    a, b = G.ce_targets(N, Cn)
+    a, b = BT.ce_targets(N, Cn)
     b = torch.where(torch.arange(N) % 4 == 1, a, b)                  # rows with a == b among the others
-    return G.ce_ignore(a, how), b
+    return BT.ce_ignore(a, how), b
 
 
 def _plain(z, t):
@@ -185,9 +187,9 @@ def _plain(z, t):
     return rows.cpu(), dl.cpu(), loss.cpu()
 
 
-@pytest.mark.parametrize("N,Cn", G.CE_SIZES)
+@pytest.mark.parametrize("N,Cn", BT.CE_SIZES)
 def test_soft_cross_entropy_per_element_bracket(N, Cn):
-    """EVERY dlogits element, every loss row and the mean of k_head_ce_soft inside gpu_util.ce_intervals' bracket: eps 0 / 0.1 / 1
+    """EVERY dlogits element, every loss row and the mean of k_head_ce_soft inside bounds_tail.ce_intervals' bracket: eps 0 / 0.1 / 1
     x lam 0 / 1 / 0.5 / 0.3 / per row / tb NULL / lam NULL for every kind of logit row and every way of ignoring rows (at
     N C > 10000 the way rows are ignored cycles over the 21 settings instead), rows with a == b in every batch; the same call
     with meters gives the same bits."""
@@ -196,23 +198,23 @@ def test_soft_cross_entropy_per_element_bracket(N, Cn):
     ce = _Soft(N, Cn)
     settings = [(eps, v) for eps in (0.0, 0.1, 1.0) for v in _lam_variants(N)]
     if N * Cn > 10000:
-        runs = [(k, G.CE_IGNORE[(i + j) % 4], s) for i, k in enumerate(G.CE_ROWS) for j, s in enumerate(settings)]
+        runs = [(k, BT.CE_IGNORE[(i + j) % 4], s) for i, k in enumerate(BT.CE_ROWS) for j, s in enumerate(settings)]
     else:
-        runs = [(k, h, s) for k in G.CE_ROWS for h in G.CE_IGNORE for s in settings]
+        runs = [(k, h, s) for k in BT.CE_ROWS for h in BT.CE_IGNORE for s in settings]
     worst = 0.0
     for kind, how, (eps, (name, mixing, lam)) in runs:
-        z = G.ce_logits(kind, N, Cn)
+        z = BT.ce_logits(kind, N, Cn)
         a, b = _soft_labels(N, Cn, how)
         b = b if mixing else None
         what = "soft ce %s / %s / eps %g / %s (%d, %d)" % (kind, how, eps, name, N, Cn)
         dev = [None if t is None else t.cuda() for t in (a, b, lam)]
         loss, dl, bad = ce.run(z.cuda(), *dev, eps)
         rows, loss_t = ce.rows.cpu(), ce.loss.cpu()
-        iv = G.ce_intervals(z, a, b, lam, eps)
+        iv = BT.ce_intervals(z, a, b, lam, eps)
         assert bad == 0, what
         assert bool((dl[~iv["valid"]] == 0).all()) and bool((rows[~iv["valid"]] == 0).all()), what
-        r = [G.check_iv(dl, iv["dl"], what + " dlogits", "soft cross-entropy"), G.check_iv(rows, iv["rows"], what + " rows", "soft cross-entropy"),
-             G.check_ce_mean(loss_t, rows, iv["count"], what + " mean", "cross-entropy mean")]
+        r = [IV.check_interval(dl, iv["dl"], what + " dlogits", "soft cross-entropy"), IV.check_interval(rows, iv["rows"], what + " rows", "soft cross-entropy"),
+             BT.check_ce_mean(loss_t, rows, iv["count"], what + " mean", "cross-entropy mean")]
         if iv["count"] == 0:
             assert loss != loss and bool((dl == 0).all()), what
         worst = max(worst, *r)
@@ -221,19 +223,19 @@ def test_soft_cross_entropy_per_element_bracket(N, Cn):
         G.bits_equal(ce.rows.cpu(), rows, what + " rows with meters")
         G.bits_equal(ce.loss.cpu(), loss_t, what + " loss with meters")
     print("soft cross-entropy (%d, %d): %d runs, worst error / bracket %.3f" % (N, Cn, len(runs), worst),
-          {k: round(v, 4) for k, v in G.WORST.items() if "entropy" in k})
+          {k: round(v, 4) for k, v in IV.WORST.items() if "entropy" in k})
     assert worst <= 1.0
 
 
-@pytest.mark.parametrize("N,Cn", G.CE_SIZES)
+@pytest.mark.parametrize("N,Cn", BT.CE_SIZES)
 def test_soft_cross_entropy_without_smoothing_is_the_plain_kernel(N, Cn):
     """eps = 0, tb NULL: loss_rows, dlogits and the mean equal k_head_ce's bit for bit -- for finite logits, and for rows with
     -inf at classes that are not labels (a masked class): without smoothing such a row has the plain kernel's finite loss."""
     ce = _Soft(N, Cn)
-    for kind in G.CE_ROWS:
-        z = G.ce_logits(kind, N, Cn).cuda()
-        for how in G.CE_IGNORE:
-            t = G.ce_ignore(G.ce_targets(N, Cn)[0], how).cuda()
+    for kind in BT.CE_ROWS:
+        z = BT.ce_logits(kind, N, Cn).cuda()
+        for how in BT.CE_IGNORE:
+            t = BT.ce_ignore(BT.ce_targets(N, Cn)[0], how).cuda()
             rows_p, dl_p, loss_p = _plain(z, t)
             loss, dl, bad = ce.run(z, t, None, None, 0.0)
             what = "%s / %s (%d, %d)" % (kind, how, N, Cn)

@@ -6,8 +6,8 @@ differing logf.  Loss and gradient: the bounds tests/test_gpu_head.py::test_cros
 an fp64 evaluation of the rule on the same inputs: |loss - ref| <= 2e-5 |ref| and max |dl - ref| < 1e-5 max |ref|.
 
 Per-element bounds (test_bounds*, test_dice_bounds*): every element of dlogits, every row sum, the loss and the focal factor s
-inside the brackets of gpu_util.mlabel_intervals (interval propagation through ml_elem as written, expf / log1pf / division at one
-ulp; the loss and s from the row sums the device left in the scratch), HardDice inside gpu_util.dice_interval; no element is
+inside the brackets of bounds_mlabel.mlabel_intervals (interval propagation through ml_elem as written, expf / log1pf / division at one
+ulp; the loss and s from the row sums the device left in the scratch), HardDice inside bounds_mlabel.dice_interval; no element is
 excluded.  tests/test_bounds_cpu.py proves on the same inputs that these brackets admit the kernel's arithmetic in every variant
 and reject a dropped tail element, a wrong weight, a wrong 1/(N*C), log(1 + ea) for log1pf and the other faults listed there.
 MEASURED on an MI355X, worst error / bound: dlogits 0.79, row sums 0.13 (the sparse probes 0.07), loss 0.33, s 0.33, HardDice 0.20."""
@@ -18,8 +18,9 @@ import numpy as np
 import pytest
 import torch
 
+import bounds_mlabel as BM
 import cases as C
-import gpu_util as GU
+import intervals as IV
 import multilabel_ref as R
 from gpu_util import relerr
 from mnasnet_pytorch_amd import HardDice, MultiClassBCELoss, MultiLabelMeters
@@ -276,18 +277,18 @@ def test_edge_rows():
     assert rec.tp + rec.fn == int((t == 1).sum())
 
 
-# ---- per-element bounds (gpu_util.mlabel_intervals / dice_interval; tests/test_bounds_cpu.py proves that they bite) ------------------------
+# ---- per-element bounds (bounds_mlabel.mlabel_intervals / dice_interval; tests/test_bounds_cpu.py proves that they bite) ------------------------
 def _check_bounds(call, z, t, w, focal, gamma, balance, vec, what):
     """every output of one mnas_mlabel_bce call inside its bracket: dlogits and the row sums element by element, the loss and
     (focal) s from the rows the device stored.  z, t, w where the fp64 work shall run (host, or the device for the large case)."""
     N, Cn = z.shape
     dev = z.device
-    iv = GU.mlabel_intervals(z, t, w, N, Cn, focal, gamma, balance, vec, rows_dev=call.rows)
-    r = {"dlogits": GU.check_iv(call.dl.to(dev), iv["dl"], what + " dlogits", "multi-label dlogits"),
-         "rows": GU.check_iv(call.rows.to(dev), iv["rows"], what + " row sums", "multi-label row sums"),
-         "loss": GU.check_iv(call.loss.cpu(), iv["loss"], what + " loss", "multi-label loss")}
+    iv = BM.mlabel_intervals(z, t, w, N, Cn, focal, gamma, balance, vec, rows_dev=call.rows)
+    r = {"dlogits": IV.check_interval(call.dl.to(dev), iv["dl"], what + " dlogits", "multi-label dlogits"),
+         "rows": IV.check_interval(call.rows.to(dev), iv["rows"], what + " row sums", "multi-label row sums"),
+         "loss": IV.check_interval(call.loss.cpu(), iv["loss"], what + " loss", "multi-label loss")}
     if focal:
-        r["s"] = GU.check_iv(call.s.cpu(), iv["s"], what + " s", "multi-label focal s")
+        r["s"] = IV.check_interval(call.s.cpu(), iv["s"], what + " s", "multi-label focal s")
     return r, iv
 
 
@@ -295,20 +296,20 @@ def _vec(Cn, mis=None):
     return Cn % 4 == 0 and mis is None
 
 
-@pytest.mark.parametrize("N,Cn", GU.ML_SHAPES)
+@pytest.mark.parametrize("N,Cn", BM.ML_SHAPES)
 def test_bounds(N, Cn):
     """one class; partial waves; the workgroup's second trip on the scalar path (257, 1000 misaligned, 1027: its fifth) and on the
     vector path (1028: second, 2052: third); the batch stage's second and third trip (257, 513 rows).  Every input family of
-    gpu_util.mlabel_inputs, all four variants (the confident batch under every focal setting), weights aligned (the vector path
+    bounds_mlabel.mlabel_inputs, all four variants (the confident batch under every focal setting), weights aligned (the vector path
     where C % 4 == 0) and 4 bytes off (the scalar path); guarded buffers.  The fused entry gives the plain one's bits and exact
     meters, as on the older shapes."""
     worst, small = {}, (1.0, 0.0)
-    for ki, kind in enumerate(GU.ML_KINDS):
-        z, t, w = GU.mlabel_inputs(kind, N, Cn)
+    for ki, kind in enumerate(BM.ML_KINDS):
+        z, t, w = BM.mlabel_inputs(kind, N, Cn)
         zc, tc, wc = z.cuda(), t.cuda(), w.cuda()
         f1, counts, dice = R.f1_batch(z.numpy(), t.numpy()), R.dice_counts(z.numpy(), t.numpy()), R.hard_dice(z.numpy(), t.numpy())
         for name, weighted, focal in R.LOSS_VARIANTS:
-            for gamma, balance in (GU.ML_FOCAL if (focal and kind == "confident") else (GU.ML_FOCAL[ki % 3],)):
+            for gamma, balance in (BM.ML_FOCAL if (focal and kind == "confident") else (BM.ML_FOCAL[ki % 3],)):
                 for mis in ((None, "w") if weighted else (None,)):
                     what = "%s %s (%d, %d) gamma %g mis %s" % (kind, name, N, Cn, gamma, mis)
                     m = MultiLabelMeters()
@@ -326,7 +327,7 @@ def test_bounds(N, Cn):
                     if focal and kind == "confident":
                         small = min(small, (float(iv["b"].mid), float(iv["s"].half / iv["s"].mid.abs())))
                     if kind == "sparse" and weighted and not focal:
-                        GU.mlabel_probe_visible(iv, GU.mlabel_live(N, Cn), what)
+                        BM.mlabel_probe_visible(iv, BM.mlabel_live(N, Cn), what)
                         rr = float(((a.rows.cpu().double() - iv["rows"].mid).abs() / iv["row_half"]).max())
                         worst["sparse rows"] = max(worst.get("sparse rows", 0.0), rr)
     print("(%d, %d): worst error / bound %s; smallest confident b %.3g, relative half width of s there %.3g"
@@ -341,7 +342,7 @@ def test_bounds_alignment(N, Cn):
     (3, 1024) the two orders give different bits in every row (tests/test_bounds_cpu.py's emulation, fused and unfused), so a
     misaligned run whose row sums equal the aligned run's did not change path; on (2, 2052) they happen to agree and nothing
     is asserted."""
-    z, t, w = GU.mlabel_inputs("scale8", N, Cn)
+    z, t, w = BM.mlabel_inputs("scale8", N, Cn)
     zc, tc, wc = z.cuda(), t.cuda(), w.cuda()
     for focal in (False, True):
         base = _Bce(zc, tc, wc, focal).ok()
@@ -360,11 +361,11 @@ def test_bounds_scale_second_trip():
     """(1100, 1000) focal, weighted: N*C = 1.1 M > 4096*256, so every lane of k_mlabel_scale's capped grid takes a second trip for
     the elements from 1 048 576 on.  Brackets in fp64 on the device; and separately: every element -- those at and beyond the cap
     among them -- is the unscaled gradient times the device's s, rounded once, to the bit (scaled exactly once)."""
-    N, Cn = GU.ML_BIG
+    N, Cn = BM.ML_BIG
     cap = 4096 * 256
-    z, t, w = GU.mlabel_inputs("scale8", N, Cn)
+    z, t, w = BM.mlabel_inputs("scale8", N, Cn)
     zc, tc, wc = z.cuda(), t.cuda(), w.cuda()
-    gamma, balance = GU.ML_FOCAL[1]
+    gamma, balance = BM.ML_FOCAL[1]
     a = _Bce(zc, tc, wc, True, gamma, balance).ok()
     plain = _Bce(zc, tc, wc, False).ok()
     r, _ = _check_bounds(a, zc, tc, wc, True, gamma, balance, True, "(1100, 1000) focal")
@@ -424,8 +425,8 @@ def test_dice_bounds(N, Cn, I, fp, fn, weak):
         assert (tp, fp_, fn_) == ((I, fp, fn) if th == 0.5 else (I - weak, fp, fn + weak))
         for deduct in (0, 1):
             got = _hard_dice(z, t, thr, deduct)
-            iv = GU.dice_interval(tp, tp + fp_, tp + fn_, deduct)
-            r = GU.check_iv(got, iv, "HardDice %r threshold %g deduct %d" % ((N, Cn, I, fp, fn), th, deduct), "HardDice")
+            iv = BM.dice_interval(tp, tp + fp_, tp + fn_, deduct)
+            r = IV.check_interval(got, iv, "HardDice %r threshold %g deduct %d" % ((N, Cn, I, fp, fn), th, deduct), "HardDice")
             assert abs(float(got) - R.hard_dice(zn, tn, thr, bool(deduct))) <= DICE_TOL
             if tp > 0 and fp_ == 0 and fn_ == 0:
                 assert float(got) == 1.0                                  # 2I == U: 1 + logf(1); with deduct 1 + log 2, clamped
@@ -446,13 +447,13 @@ def test_dice_bounds_rounded_conversion():
     assert float(torch.tensor(float(2 * I)).float()) != 2 * I and 2 * I > 2 ** 25
     for deduct in (0, 1):
         got = _hard_dice(z, t, 0.0, deduct)
-        r = GU.check_iv(got, GU.dice_interval(I, I + fp, I + fn, deduct), "HardDice 4100 x 4100 deduct %d" % deduct, "HardDice")
+        r = IV.check_interval(got, BM.dice_interval(I, I + fp, I + fn, deduct), "HardDice 4100 x 4100 deduct %d" % deduct, "HardDice")
         print("HardDice 4100 x 4100 deduct %d: %r, error / bound %.3f" % (deduct, float(got), r))
 
 
 def test_rejects_write_nothing():
     """every refused call returns MNAS_EINVAL and leaves the NaN / 0xA5 guards and the meter block as they were"""
-    z, t, w = GU.mlabel_inputs("scale8", 3, 8)
+    z, t, w = BM.mlabel_inputs("scale8", 3, 8)
     zc, tc, wc = z.cuda(), t.cuda(), w.cuda()
     m = MultiLabelMeters()
     m.update(zc, tc)

@@ -10,11 +10,11 @@ import torch
 
 import cases as C
 from cases import O
+from bounds_conv import act_interval, check_onload_bound, check_red_bound, check_stats_bound, off_hinge, onload_elem_err, onload_fwd_terms
+from bounds_se import (check_sigmoid, gate_nhwc, gated_act_interval, gated_fwd_inputs, se_apply_interval, se_fc_bwd_terms,
+                       se_fc_fwd_intervals, se_geom, se_proj_finalize_intervals, se_reduce_terms, sig1m_interval, sigmoid_interval)
 from gpu_util import L, act_in, bf16r, from_nhwc, nhwc, relerr
-from gpu_util import (Interval, act_interval, check_interval, check_onload_bound, check_sigmoid, check_red_bound, check_stats_bound, check_store_bound,
-                      check_sum_bound, gate_nhwc, gated_act_interval, gated_fwd_inputs, imul, off_hinge, onload_elem_err,
-                      onload_fwd_terms, se_apply_interval, se_fc_bwd_terms, se_fc_fwd_intervals, se_geom, se_proj_finalize_intervals,
-                      se_reduce_terms, sig1m_interval, sigmoid_interval, sum_interval)
+from intervals import Interval, check_interval, check_store_bound, check_sum_bound, sum_interval
 from oracle import bf16_mirror as M
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +23,7 @@ DEV = "cuda"            # where the fp64 terms of the per-element bounds are com
 
 def test_se_gate_against_fp64_sigmoid():
     """mnas_se_gate = se_sigmoid, the function every squeeze-excite kernel evaluates: v in [-30, 30] in steps of 1/64 and +-0, every
-    element inside gpu_util.sigmoid_interval -- the check of that bracket's one assumption (the hardware exponential within one
+    element inside bounds_se.sigmoid_interval -- the check of that bracket's one assumption (the hardware exponential within one
     ulp); v = +-100 gives finite values in [0, 1]"""
     lib = L.load()
     v = torch.cat([torch.arange(-30 * 64, 30 * 64 + 1).float() / 64, torch.tensor([0.0, -0.0, 100.0, -100.0])])
@@ -61,7 +61,7 @@ def _flat_views(tensors):
                                    (3, 1280, 48), (2, 8, 1)])         # + the largest supported shape, and one hidden unit
 def test_se_fused_mlp(N, E, R):
     """mnas_se_fc_fwd / mnas_se_fc_bwd (the excitation MLP in 1 + 2 kernels) against fp32 torch math; accumulate on and off, gate on
-    and off.  fp32 sums in another order: <= 1e-5 of max |ref| (measured 1e-6).  + the brackets of gpu_util.se_fc_fwd_intervals /
+    and off.  fp32 sums in another order: <= 1e-5 of max |ref| (measured 1e-6).  + the brackets of bounds_se.se_fc_fwd_intervals /
     se_fc_bwd_terms on every output.  Parameters and gradients are views at a 4-byte (not 16-byte) aligned offset of one buffer."""
     lib = L.load()
     assert lib.mnas_se_fc_supported(E, R) == 1
@@ -180,7 +180,7 @@ def _se_kernels(shape, virt, amp):
     assert relerr(du.cpu(), (gs * a).sum((2, 3)) * sg * (1 - sg)) < 2e-3
     aiv = act_interval(yn, s, t, False, DEV) if virt else Interval.exact(yn, DEV)
     r64, S, slack = se_reduce_terms(gsn, aiv, HW)
-    check_interval(du, imul(sum_interval(r64, S, HW, R + splits, 1, slack), sig1m_interval(u, DEV), 1), what + "se_bwd_reduce", "se_bwd_reduce")
+    check_interval(du, sum_interval(r64, S, HW, R + splits, 1, slack).mul(sig1m_interval(u, DEV), 1), what + "se_bwd_reduce", "se_bwd_reduce")
     del aiv, r64, S, slack
     ga = torch.full((N, H, W, Cc), float("nan"), dtype=torch.bfloat16, device="cuda")
     L.check(lib.mnas_se_bwd_apply(gsd.data_ptr(), ud.data_ptr(), dzd.data_ptr(), N, HW, Cc, ga.data_ptr(), None, None, None,
@@ -236,7 +236,7 @@ def test_sparse_probe_se_reduce(shape):
     r64, S, slack = se_reduce_terms(gs, Interval.exact(y, DEV), HW)
     assert float(slack.max()) == 0.0
     f = sig1m_interval(u, DEV)
-    iv = imul(sum_interval(r64, S, HW, R + splits, 1), f, 1)
+    iv = sum_interval(r64, S, HW, R + splits, 1).mul(f, 1)
     what = "sparse se_bwd_reduce %s" % (shape,)
     check_interval(du, iv, what, "sparse probes")
     if N > 2:

@@ -1,12 +1,13 @@
-"""CPU self-test of the fp64 references in tests/gpu_util.py (used by tests/test_gpu_bwd_forms.py on the device): each one
+"""CPU self-test of the fp64 references in tests/refs64.py (used by tests/test_gpu_bwd_forms.py on the device): each one
 against torch.nn.functional / torch.nn.grad in fp64 at small shapes, odd planes and both depthwise kernel sizes, to 1e-12.
 Also the guarded-buffer helper's two checks (a write outside the view, an element never written)."""
 import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import (Interval, bits_equal, guarded, ref_dense_s2_dgrad, ref_dw_dgrad, ref_dw_dgrad_s, ref_dw_fwd, ref_dw_wgrad,
-                      ref_dw_wgrad_s, ref_dy)
+from gpu_util import bits_equal, guarded
+from intervals import Interval
+from refs64 import ref_dense_dgrad, ref_dw_dgrad, ref_dw_fwd, ref_dw_wgrad, ref_dy
 
 
 def _r(shape, seed):
@@ -39,9 +40,9 @@ def test_strided_depthwise_gradient_references(N, H, W, C_, k, stride):
     Ho, Wo = (H + 2 * p - k) // stride + 1, (W + 2 * p - k) // stride + 1
     x, dy, w = _r((N, H, W, C_), 1), _r((N, Ho, Wo, C_), 2), _r((C_, k, k), 3)
     w4 = w.view(C_, 1, k, k)
-    _close(_nchw(ref_dw_dgrad_s(dy, w, H, W, stride)),
+    _close(_nchw(ref_dw_dgrad(dy, w, H, W, stride)),
            torch.nn.grad.conv2d_input((N, C_, H, W), w4, _nchw(dy), stride=stride, padding=p, groups=C_))
-    _close(ref_dw_wgrad_s(x, dy, k, stride),
+    _close(ref_dw_wgrad(x, dy, k, stride),
            torch.nn.grad.conv2d_weight(_nchw(x), (C_, 1, k, k), _nchw(dy), stride=stride, padding=p, groups=C_).view(C_, k, k))
 
 
@@ -57,7 +58,7 @@ def test_dense_s2_dgrad_reference(N, H, W, Ci, Co):
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     dy, w = _r((N, Ho, Wo, Co), 4), _r((Co, Ci, 3, 3), 5)
     ref = torch.nn.grad.conv2d_input((N, Ci, H, W), w, _nchw(dy), stride=2, padding=1)
-    _close(_nchw(ref_dense_s2_dgrad(dy, w, H, W)), ref)
+    _close(_nchw(ref_dense_dgrad(dy, w, H, W, stride=2, pad=1)), ref)
 
 
 def test_dy_reference():
