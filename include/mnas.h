@@ -126,6 +126,17 @@ int mnas_conv_img_parts(int mode, int N, int Hi, int Wi, int Ci, int Ho, int Wo,
 #define MNAS_ROUTE_C3X   6   /* csrc/mnas_c3x.hip: stride-2 3x3 forward on the large maps */
 #define MNAS_ROUTE_IGEMM 7   /* csrc/mnas_gemm.hip: k_igemm, every other shape */
 int mnas_conv_gemm_route(const MnasConvGemm* a, int* out);
+/* Which template instance of that family runs (host-side, no launch; additive within ABI 8).  The query IS the launch function,
+ * stopped where it would launch, so it also refuses what a family's own run function refuses.  Returns MNAS_ROUTE_* or
+ * -MNAS_EINVAL; out (or NULL): int[8], the template arguments followed by the plan values that pick a code path, zeros beyond:
+ *   MNAS_ROUTE_PWS              {NT, KSW, NW, GATE}
+ *   MNAS_ROUTE_PWF, _PWD        {NT, PT, WRES (weight block resident), K chunks}
+ *   MNAS_ROUTE_PWX              {TPW, KS, NW}
+ *   MNAS_ROUTE_DIMG             {PXW, CG bound of the instantiation, images per pass, K chunks}
+ *   MNAS_ROUTE_C3R              {NT, KSW, PTW, KQ, cout slices (grid.y)}
+ *   MNAS_ROUTE_C3X              {TPW, KS}
+ *   MNAS_ROUTE_IGEMM            as mnas_conv_gemm_route (refusals of a single k_igemm instance still come from the launch) */
+int mnas_conv_gemm_instance(const MnasConvGemm* a, int* out);
 
 /* ---- input gradient of the stride-2 dense 3x3 convs as a transposed convolution (csrc/mnas_tconv.hip): one GEMM per 2x2
  * output block over the four dy pixels it depends on; no per-element gather.  dy: bf16 (N,Ho,Wo,Co), MATERIALISED
@@ -144,6 +155,13 @@ typedef struct MnasTconvDgrad {
 int mnas_tconv_dgrad(const MnasTconvDgrad* a, void* stream);
 int mnas_tconv_supported(int Ho, int Wo, int Co, int Ci);
 int mnas_tconv_parts(int N, int Ho, int Wo, int Co, int Ci);     /* preferred nparts (persistent workgroups) */
+/* Which kernel and template instance mnas_tconv_dgrad runs (host-side: the launch function stopped where it would launch).  Returns
+ * MNAS_TCONV_* or -MNAS_EINVAL; out (or NULL): int[8] = {TPW, KSM, channel blocks} (k_tcx), {KQ0, KQ1, KQ3, channel slices}
+ * (k_tcr), {NT, PT} (k_tconv), zeros beyond. */
+#define MNAS_TCONV_TCX   0   /* csrc/mnas_tcx.hip: weight-stationary, the large maps */
+#define MNAS_TCONV_TCR   1   /* csrc/mnas_tcx.hip: weight rows register-resident, onto the 7x7 plane */
+#define MNAS_TCONV_TCONV 2   /* csrc/mnas_tconv.hip */
+int mnas_tconv_dgrad_instance(const MnasTconvDgrad* a, int* out);
 
 /* ---- weight gradient of the same convs: dW[co][tap][ci] = sum_pix dy[pix][co] * act(x)[src(pix,tap)][ci]
  * Replaces ATen conv2d weight-gradient.  x = (N,Hi,Wi,Ci) forward input, dy = (N,Ho,Wo,Co).
@@ -162,6 +180,9 @@ int mnas_conv_wgrad(const MnasConvWgrad* a, void* stream);
 /* Number of (cout x k) slabs mnas_conv_wgrad splits dW[Co][taps*Ci] into (the slab shape is chosen per (Co, K)): a launch
  * runs nsplit x slabs workgroups, so callers size nsplit as (workgroup budget) / slabs. */
 int mnas_conv_wgrad_slabs(int Co, int Ci, int taps);
+/* Slab shape of the k_wgrad_t instance a launch runs (host-side: the launch function stopped where it would launch): 0 or
+ * -MNAS_EINVAL; out (or NULL): int[2] = {CT, KT}, 32-cout x 32-k tiles per slab. */
+int mnas_conv_wgrad_instance(const MnasConvWgrad* a, int* out);
 
 /* grad[co][ci][kh][kw] (reference layout, fp32) (+)= sum_s partial[s][co][tap*Ci+ci].  Deterministic (fixed summation
  * order, no atomics).  `partial` is scratch: with more than 256 splits the first row of every 128-row chunk is
@@ -209,6 +230,9 @@ int mnas_pw_bwd_supported(int Ci, int Co);
 int mnas_pw_bwd_tile_pixels(int Ci, int Co);
 int mnas_pw_bwd_slices(int Ci, int Co);
 int mnas_pw_bwd_forms(int Ci, int Co);      /* bit 1: RECOMP available for this channel pair, bit 2: out-stage form (gin_masked) */
+/* The k_pw_bwd instance a launch runs (host-side: the launch function stopped where it would launch): 0 or -MNAS_EINVAL; out (or
+ * NULL): int[8] = {NTO, NTI per slice, PT, channel slices, OS (out-stage form), FORM (2 = RECOMP)}, zeros beyond. */
+int mnas_pw_bwd_instance(const MnasPwBwd* a, int* out);
 
 /* ---- depthwise kxk (k in {3,5}, stride 1, pad k/2), LDS-tiled direct conv on the vector ALU ----------
  * Replaces ATen conv2d fwd/bwd for ConvBlock's groups==C convs (mnasnet.py:122-125, 76-81). */

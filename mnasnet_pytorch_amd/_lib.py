@@ -143,6 +143,7 @@ OP_BN_FROZEN_BATCH, OP_BWD_POST_FROZEN, OP_BN_BWD_FINALIZE_FROZEN = 40, 41, 42  
 PACK_FWD, PACK_DGRAD, PACK_DW, PACK_TCONV = 0, 1, 2, 3
 EINVAL = 10001      # MNAS_EINVAL
 ROUTE_PWX, ROUTE_PWS, ROUTE_PWF, ROUTE_PWD, ROUTE_C3R, ROUTE_DIMG, ROUTE_C3X, ROUTE_IGEMM = range(8)     # MNAS_ROUTE_*
+TCONV_TCX, TCONV_TCR, TCONV_TCONV = range(3)     # MNAS_TCONV_*
 
 
 def _act(n):
@@ -351,14 +352,17 @@ SYMBOLS = {
     "mnas_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "mnas_conv_gemm": (c_int, [C.POINTER(MnasConvGemm), c_void_p]),
     "mnas_conv_gemm_route": (c_int, [C.POINTER(MnasConvGemm), C.POINTER(c_int)]),
+    "mnas_conv_gemm_instance": (c_int, [C.POINTER(MnasConvGemm), C.POINTER(c_int)]),
     "mnas_conv_gemm_tile_pixels": (c_int, [c_int, c_int, c_int]),
     "mnas_conv_gemm_parts": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "mnas_conv_wgrad": (c_int, [C.POINTER(MnasConvWgrad), c_void_p]),
+    "mnas_conv_wgrad_instance": (c_int, [C.POINTER(MnasConvWgrad), C.POINTER(c_int)]),
     "mnas_conv_wgrad_slabs": (c_int, [c_int, c_int, c_int]),
     "mnas_wgrad_finalize": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mnas_pw_bwd": (c_int, [C.POINTER(MnasPwBwd), c_void_p]),
     "mnas_pw_bwd_supported": (c_int, [c_int, c_int]),
     "mnas_pw_bwd_forms": (c_int, [c_int, c_int]),
+    "mnas_pw_bwd_instance": (c_int, [C.POINTER(MnasPwBwd), C.POINTER(c_int)]),
     "mnas_pw_bwd_tile_pixels": (c_int, [c_int, c_int]),
     "mnas_pw_bwd_slices": (c_int, [c_int, c_int]),
     "mnas_dw_fwd": (c_int, [C.POINTER(MnasDwFwd), c_void_p]),
@@ -372,6 +376,7 @@ SYMBOLS = {
                                      c_void_p, c_float, c_float, c_int, c_void_p, c_void_p]),
     "mnas_bn_bwd_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "mnas_tconv_dgrad": (c_int, [C.POINTER(MnasTconvDgrad), c_void_p]),
+    "mnas_tconv_dgrad_instance": (c_int, [C.POINTER(MnasTconvDgrad), C.POINTER(c_int)]),
     "mnas_tconv_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "mnas_tconv_parts": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "mnas_bwd_post": (c_int, [C.POINTER(MnasBwdPost), c_void_p]),

@@ -272,7 +272,9 @@ static bool c3r_plan(int mode, int N, int Hi, int Wi, int Ci, int Ho, int Wo, in
         // three cout tiles with the 8-way split where that saves passes (192 -> 320 forward: 7 slices of 48 instead of 10 of 32)
         p->kq = 8; p->ptw = 4; p->nt = 3; ksw = (ksteps + 7) / 8; p->ksw = 7;
     } else {
-        if (p->nt * ksw > 28 && !(p->nt == 1 && ksw <= 24)) return false;
+        // a wave's k-steps must fit the KSW fragments of the instantiation (NT = 2 has ksw <= 14 by construction).  A bound of 28 here
+        // once let 25..28 steps per wave (Ci = 344..392) run on the 24-fragment kernel, which drops every k-step past the 96th
+        if (ksw > 24) return false;
         p->ksw = ksw <= 14 ? 14 : 24;
     }
     const int nb = p->nt * 16;
@@ -295,11 +297,12 @@ int mnas_c3r_parts(int mode, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int 
     return p.parts;
 }
 
-int mnas_c3r_run(const MnasConvGemm* c, void* stream) {
+int mnas_c3r_run(const MnasConvGemm* c, void* stream, int* inst) {
     C3rPlan p;
     if (!c3r_plan(c->mode, c->N, c->Hi, c->Wi, c->Ci, c->Ho, c->Wo, c->Co, c->kh, c->kw, c->stride, c->pad, &p)) return MNAS_EINVAL;
     if (c->mode == 1 && (c->grad.coef || c->grad.y)) return MNAS_EINVAL;          // materialised dy only
     if (c->resid || c->gate || c->nparts < 1) return MNAS_EINVAL;
+    if (inst) { inst[0] = p.nt; inst[1] = p.ksw; inst[2] = p.ptw; inst[3] = p.kq; inst[4] = p.slices; return MNAS_OK; }
     C3rArgs a = {};
     a.N = c->N; a.Hi = c->Hi; a.Wi = c->Wi; a.Ci = c->Ci; a.Ho = c->Ho; a.Wo = c->Wo; a.Co = c->Co;
     a.stride = c->stride;

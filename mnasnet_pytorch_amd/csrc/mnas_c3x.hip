@@ -168,10 +168,11 @@ int mnas_c3x_ok(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int kh, i
     return c3x_plan(N, Hi, Wi, Ci, Ho, Wo, Co, kh, kw, stride, pad, &p) ? 1 : 0;
 }
 
-int mnas_c3x_run(const MnasConvGemm* c, void* stream) {
+int mnas_c3x_run(const MnasConvGemm* c, void* stream, int* inst) {
     C3xPlan p;
     if (c->mode != 0 || c->resid || c->gate || !c->act.data || !c->out || c->nparts < 1 ||
         !c3x_plan(c->N, c->Hi, c->Wi, c->Ci, c->Ho, c->Wo, c->Co, c->kh, c->kw, c->stride, c->pad, &p)) return MNAS_EINVAL;
+    if (inst) { inst[0] = p.tpw; inst[1] = p.ks; return MNAS_OK; }
     C3xArgs a;
     a.N = c->N; a.Hi = c->Hi; a.Wi = c->Wi; a.Ci = c->Ci; a.Ho = c->Ho; a.Wo = c->Wo; a.Co = c->Co;
     a.stride = c->stride;

@@ -223,39 +223,41 @@ __device__ __forceinline__ void st_u4(void* p, uint4 v, bool nt) {
 #define MNAS_NT_ADD_ACT 32
 #define MNAS_NT_STEM 64
 #define MNAS_NT_PWF 128
+// `inst` (the run functions below): NULL launches; otherwise nothing is launched -- the function stops where it would launch and
+// writes the template arguments and plan values it would launch with (mnas_conv_gemm_instance / mnas_tconv_dgrad_instance)
 int mnas_nt_mask();
 // DMA-pipelined 1x1 forward (mnas_pwf.hip): mnas_conv_gemm dispatches mode 0 / 1x1 here unless MNAS_PWF=0
 int mnas_pwf_enabled();
 int mnas_pwf_parts(int M, int Ci, int Co);
-int mnas_pwf_forward(const MnasConvGemm* c, void* stream);
+int mnas_pwf_forward(const MnasConvGemm* c, void* stream, int* inst = nullptr);
 int mnas_stem_fwd_band(const MnasStemFwd* c, void* stream);      // csrc/mnas_stem.hip; MNAS_EINVAL = not a band shape
 int mnas_stem_wgrad_band(const MnasStemWgrad* c, void* stream);
 int mnas_dimg_parts(int mode, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int kh, int kw, int stride, int pad);
-int mnas_dimg_run(const MnasConvGemm* c, void* stream);          // csrc/mnas_dimg.hip: dense 3x3 on the small feature maps
+int mnas_dimg_run(const MnasConvGemm* c, void* stream, int* inst = nullptr);          // csrc/mnas_dimg.hip: dense 3x3 on the small feature maps
 int mnas_c3r_parts(int mode, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int kh, int kw, int stride, int pad);
-int mnas_c3r_run(const MnasConvGemm* c, void* stream);           // csrc/mnas_c3r.hip: weight-heavy dense 3x3 on the 7x7 planes, weights register-resident
+int mnas_c3r_run(const MnasConvGemm* c, void* stream, int* inst = nullptr);           // csrc/mnas_c3r.hip: weight-heavy dense 3x3 on the 7x7 planes, weights register-resident
 int mnas_pwd_enabled();      // MNAS_PWD (default 1): DMA-pipelined 1x1 input gradient for the few-dy-channel convs
 int mnas_pwd_parts(int M, int Ci, int Co);
-int mnas_pwd_dgrad(const MnasConvGemm* c, void* stream);
+int mnas_pwd_dgrad(const MnasConvGemm* c, void* stream, int* inst = nullptr);
 // K-streaming 1x1 GEMM (mnas_pws.hip): long-K forward / input gradient on the small-M stages (diagnosis build: MNAS_PWS=0 off, 1 forward only)
 int mnas_dw2_rows(int N, int H, int W, int C, int k, int nparts, int which);      // csrc/mnas_dw2.hip: stride-2 depthwise (SepConv reduce)
 int mnas_dw2_fwd(const MnasDwFwd* c, void* stream);
 int mnas_dw2_bwd(const MnasDwBwd* c, void* stream);
 int mnas_pws_enabled();
 int mnas_pws_parts(int mode, int M, int K, int N);
-int mnas_pws_run(const MnasConvGemm* c, void* stream);
+int mnas_pws_run(const MnasConvGemm* c, void* stream, int* inst = nullptr);
 int mnas_pws_accepts(const MnasConvGemm* c);
 int mnas_pws_gate_ok(int M, int K, int N);
 int mnas_c3x_ok(int N, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int kh, int kw, int stride, int pad);
-int mnas_c3x_run(const MnasConvGemm* c, void* stream);           // csrc/mnas_c3x.hip: stride-2 3x3 forward on the large maps, weight-stationary
+int mnas_c3x_run(const MnasConvGemm* c, void* stream, int* inst = nullptr);           // csrc/mnas_c3x.hip: stride-2 3x3 forward on the large maps, weight-stationary
 int mnas_tcx_ok(int Ho, int Wo, int Co, int Ci);                 // csrc/mnas_tcx.hip: stride-2 3x3 input gradient, weight-stationary
 int mnas_tcx_parts(int N, int Ho, int Wo, int Co, int Ci);
-int mnas_tcx_dgrad(const MnasTconvDgrad* c, void* stream);
+int mnas_tcx_dgrad(const MnasTconvDgrad* c, void* stream, int* inst = nullptr);
 int mnas_tcr_ok(int Ho, int Wo, int Co, int Ci);
 int mnas_tcr_parts(int N, int Ho, int Wo, int Co, int Ci);
-int mnas_tcr_dgrad(const MnasTconvDgrad* c, void* stream);
+int mnas_tcr_dgrad(const MnasTconvDgrad* c, void* stream, int* inst = nullptr);
 int mnas_pwx_parts(int M, int Ci, int Co);                       // csrc/mnas_pwx.hip: widening 1x1 forward, weight-stationary
-int mnas_pwx_forward(const MnasConvGemm* c, void* stream);
+int mnas_pwx_forward(const MnasConvGemm* c, void* stream, int* inst = nullptr);
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

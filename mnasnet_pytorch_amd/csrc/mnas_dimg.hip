@@ -327,11 +327,14 @@ int mnas_dimg_parts(int mode, int N, int Hi, int Wi, int Ci, int Ho, int Wo, int
     return (N + p.ni - 1) / p.ni;
 }
 
-int mnas_dimg_run(const MnasConvGemm* c, void* stream) {
+int mnas_dimg_run(const MnasConvGemm* c, void* stream, int* inst) {
     DimgPlan p;
     if (!dimg_plan(c->mode, c->N, c->Hi, c->Wi, c->Ci, c->Ho, c->Wo, c->Co, c->kh, c->kw, c->stride, c->pad, &p)) return MNAS_EINVAL;
     if (c->mode == 1 && (c->grad.coef || c->grad.y)) return MNAS_EINVAL;          // materialised dy only
     if (c->mode == 0 && c->resid) return MNAS_EINVAL;
+    // the instantiation's cout-tile bound: the smallest one that fits (the register arrays are sized by it)
+    const int cgb = p.pxw == 4 ? (p.cg <= 3 ? 3 : (p.cg <= 6 ? 6 : 0)) : (p.cg <= 12 ? 12 : 0);
+    if (inst) { inst[0] = p.pxw; inst[1] = cgb; inst[2] = p.ni; inst[3] = p.nkc; return MNAS_OK; }
     DimgArgs a = {};
     a.N = c->N; a.Hi = c->Hi; a.Wi = c->Wi; a.Ci = c->Ci; a.Ho = c->Ho; a.Wo = c->Wo; a.Co = c->Co;
     a.stride = c->stride;
@@ -347,12 +350,12 @@ int mnas_dimg_run(const MnasConvGemm* c, void* stream) {
     const dim3 grid(c->nparts, p.groups);            // workgroups beyond N only write their (zero) statistics column
     hipStream_t s = (hipStream_t)stream;
 #define MNAS_DIMG(M_, P_, C_) \
-    if (c->mode == M_ && p.pxw == P_ && p.cg <= C_) { \
+    if (c->mode == M_ && p.pxw == P_ && cgb == C_) { \
         hipLaunchKernelGGL((k_dimg<M_, P_, C_>), grid, dim3(256), p.lds, s, a); \
         MNAS_CHECK_LAUNCH(); \
         return MNAS_OK; \
     }
-    MNAS_DIMG(0, 4, 3) MNAS_DIMG(1, 4, 3)            // (smallest fitting cout-tile bound first: the register arrays are sized by it)
+    MNAS_DIMG(0, 4, 3) MNAS_DIMG(1, 4, 3)
     MNAS_DIMG(0, 4, 6) MNAS_DIMG(0, 2, 12) MNAS_DIMG(0, 1, 12) MNAS_DIMG(1, 4, 6) MNAS_DIMG(1, 2, 12) MNAS_DIMG(1, 1, 12)
 #undef MNAS_DIMG
     return MNAS_EINVAL;

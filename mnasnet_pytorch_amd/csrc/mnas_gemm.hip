@@ -657,20 +657,25 @@ extern "C" int mnas_conv_gemm_route(const MnasConvGemm* c, int* out) {
     return route;
 }
 
-extern "C" int mnas_conv_gemm(const MnasConvGemm* c, void* stream) {
+// Launch path and instance query in one function: with `inst` set, every family's run function stops where it would launch and
+// writes the template arguments and plan values it would launch with (int[8], see mnas_conv_gemm_instance in include/mnas.h).
+static int conv_gemm_go(const MnasConvGemm* c, void* stream, int* inst, int* route_out) {
     IgemmArgs a;
     int best_nt = 0, nblocks = 0, pt = 0;
-    switch (conv_gemm_plan(c, &a, &best_nt, &nblocks, &pt)) {
-        case MNAS_ROUTE_PWX: return mnas_pwx_forward(c, stream);
-        case MNAS_ROUTE_PWS: return mnas_pws_run(c, stream);
-        case MNAS_ROUTE_PWF: return mnas_pwf_forward(c, stream);
-        case MNAS_ROUTE_PWD: return mnas_pwd_dgrad(c, stream);
-        case MNAS_ROUTE_C3R: return mnas_c3r_run(c, stream);
-        case MNAS_ROUTE_DIMG: return mnas_dimg_run(c, stream);
-        case MNAS_ROUTE_C3X: return mnas_c3x_run(c, stream);
+    const int route = conv_gemm_plan(c, &a, &best_nt, &nblocks, &pt);
+    if (route_out) *route_out = route;
+    switch (route) {
+        case MNAS_ROUTE_PWX: return mnas_pwx_forward(c, stream, inst);
+        case MNAS_ROUTE_PWS: return mnas_pws_run(c, stream, inst);
+        case MNAS_ROUTE_PWF: return mnas_pwf_forward(c, stream, inst);
+        case MNAS_ROUTE_PWD: return mnas_pwd_dgrad(c, stream, inst);
+        case MNAS_ROUTE_C3R: return mnas_c3r_run(c, stream, inst);
+        case MNAS_ROUTE_DIMG: return mnas_dimg_run(c, stream, inst);
+        case MNAS_ROUTE_C3X: return mnas_c3x_run(c, stream, inst);
         case MNAS_ROUTE_IGEMM: break;
         default: return MNAS_EINVAL;
     }
+    if (inst) { inst[0] = best_nt; inst[1] = pt; inst[2] = a.kch; inst[3] = a.s2; return MNAS_OK; }
     hipStream_t s = (hipStream_t)stream;
 #define MNAS_IG(MODE_, NT_) \
     if (c->mode == MODE_ && best_nt == NT_) return pt == 2 ? launch_igemm<MODE_, NT_, 2>(a, c->nparts, nblocks, s) \
@@ -679,6 +684,16 @@ extern "C" int mnas_conv_gemm(const MnasConvGemm* c, void* stream) {
     MNAS_IG(1, 1) MNAS_IG(1, 2) MNAS_IG(1, 3) MNAS_IG(1, 4) MNAS_IG(1, 6) MNAS_IG(1, 8)
 #undef MNAS_IG
     return MNAS_EINVAL;
+}
+
+extern "C" int mnas_conv_gemm(const MnasConvGemm* c, void* stream) { return conv_gemm_go(c, stream, nullptr, nullptr); }
+
+extern "C" int mnas_conv_gemm_instance(const MnasConvGemm* c, int* out) {
+    int inst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, route = -MNAS_EINVAL;
+    const int rc = conv_gemm_go(c, nullptr, inst, &route);
+    if (out) for (int i = 0; i < 8; ++i) out[i] = rc == MNAS_OK ? inst[i] : 0;
+    if (route < 0) return route;
+    return rc == MNAS_OK ? route : -rc;
 }
 
 // Stem: dense 3x3 stride-2 conv on the fp32 NCHW image (mnasnet.py:179) = the same GEMM with an im2col

@@ -529,7 +529,8 @@ __global__ __launch_bounds__(256, 2) void k_pw_bwd(PwBwdArgs a) {
 
 static MNAS_SWITCH(pw_bwd_outstage, mnas_diag_env("MNAS_PWB_OS", 2))  // 0 off, 1 narrowing convs, 2 + the 14x14 channel slices
 template <int NTO, int NTI, int PT>
-static int launch_pw_bwd(const PwBwdArgs& a, int nparts, hipStream_t stream, int nslices = 1) {
+// inst (or NULL): nothing is launched; inst[4], inst[5] receive the OS and FORM template arguments of the kernel that would run
+static int launch_pw_bwd(const PwBwdArgs& a, int nparts, hipStream_t stream, int nslices = 1, int* inst = nullptr) {
     constexpr int BP = 64 * PT, COP = NTO * 16, CIP = NTI * 16;
     constexpr bool PF = MNAS_PWB_PF && NTO != 15 && !(NTO == 1 && NTI == 2);    // loads one tile ahead (see the tile walk)
     const bool recomp = a.dy.y == nullptr;
@@ -545,6 +546,7 @@ static int launch_pw_bwd(const PwBwdArgs& a, int nparts, hipStream_t stream, int
         // reduce target is the depthwise conv that produced x); anything else takes the plain epilogue below
         const bool redx = !a.red_partial || a.red_y == a.x.data;
         if (pw_bwd_outstage() >= (NTI == NTO ? 2 : 1) && !a.resid && redx) {
+            if (inst) { inst[4] = 1; inst[5] = 0; return MNAS_OK; }
             hipLaunchKernelGGL((k_pw_bwd<NTO, NTI, PT, true, 0, PF>), dim3(nparts, nslices), dim3(256), lds, stream, a);
             MNAS_CHECK_LAUNCH();
             return MNAS_OK;
@@ -553,12 +555,14 @@ static int launch_pw_bwd(const PwBwdArgs& a, int nparts, hipStream_t stream, int
     if (a.gin_masked) return MNAS_EINVAL;                     // only the out-stage kernel masks (a -DMNAS_DIAG build can switch it off)
     if constexpr (NTO > NTI && NTI <= 2) {                    // the expand convs of the 112x112 / 56x56 stages
         if (recomp) {
+            if (inst) { inst[4] = 0; inst[5] = 2; return MNAS_OK; }
             hipLaunchKernelGGL((k_pw_bwd<NTO, NTI, PT, false, 2, PF>), dim3(nparts, nslices), dim3(256), lds, stream, a);
             MNAS_CHECK_LAUNCH();
             return MNAS_OK;
         }
     }
     if (recomp) return MNAS_EINVAL;
+    if (inst) { inst[4] = 0; inst[5] = 0; return MNAS_OK; }
     hipLaunchKernelGGL((k_pw_bwd<NTO, NTI, PT, false, 0, PF>), dim3(nparts, nslices), dim3(256), lds, stream, a);
     MNAS_CHECK_LAUNCH();
     return MNAS_OK;
@@ -598,7 +602,7 @@ extern "C" int mnas_pw_bwd_forms(int Ci, int Co) {
     return f;
 }
 
-extern "C" int mnas_pw_bwd(const MnasPwBwd* c, void* stream) {
+static int pw_bwd_go(const MnasPwBwd* c, void* stream, int* inst) {
     if (!c || c->M < 1 || c->nparts < 1 || c->nparts > 65535 || !mnas_pw_bwd_supported(c->Ci, c->Co)) return MNAS_EINVAL;
     if (!c->x.data || !c->dy.g || !c->dy.coef || !c->w || !c->wpartial || !c->gin) return MNAS_EINVAL;
     if (!c->dy.y && !c->w_fwd) return MNAS_EINVAL;           // RECOMP needs the forward weights
@@ -614,10 +618,18 @@ extern "C" int mnas_pw_bwd(const MnasPwBwd* c, void* stream) {
     if (a.seg_px < 0 || (a.seg_px > 0 && ((int64_t)a.seg_px * c->nparts < c->M || (int64_t)a.seg_px * (c->nparts - 1) >= c->M))) return MNAS_EINVAL;
     if (a.gin_masked && (!c->red_partial || c->resid || c->red_y != c->x.data || !(mnas_pw_bwd_forms(c->Ci, c->Co) & 4))) return MNAS_EINVAL;
     const PwCfg* cfg = pw_cfg(c->Ci, c->Co);
+    if (inst) { inst[0] = cfg->nto; inst[1] = cfg->nti_slice; inst[2] = cfg->pt; inst[3] = cfg->nslices; }
     hipStream_t s = (hipStream_t)stream;
-#define MNAS_PWB(O_, I_, P_) if (cfg->nto == O_ && cfg->nti_slice == I_ && cfg->pt == P_) return launch_pw_bwd<O_, I_, P_>(a, c->nparts, s, cfg->nslices);
+#define MNAS_PWB(O_, I_, P_) if (cfg->nto == O_ && cfg->nti_slice == I_ && cfg->pt == P_) return launch_pw_bwd<O_, I_, P_>(a, c->nparts, s, cfg->nslices, inst);
     MNAS_PWB(1, 2, 2) MNAS_PWB(1, 3, 2) MNAS_PWB(3, 1, 2) MNAS_PWB(5, 2, 1) MNAS_PWB(2, 5, 2) MNAS_PWB(15, 3, 1)
     MNAS_PWB(3, 5, 1) MNAS_PWB(5, 5, 1) MNAS_PWB(6, 6, 1) MNAS_PWB(8, 3, 1) MNAS_PWB(3, 4, 1)
 #undef MNAS_PWB
     return MNAS_EINVAL;
+}
+extern "C" int mnas_pw_bwd(const MnasPwBwd* c, void* stream) { return pw_bwd_go(c, stream, nullptr); }
+extern "C" int mnas_pw_bwd_instance(const MnasPwBwd* c, int* out) {
+    int inst[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int rc = pw_bwd_go(c, nullptr, inst);
+    if (out) for (int i = 0; i < 8; ++i) out[i] = rc == MNAS_OK ? inst[i] : 0;
+    return rc == MNAS_OK ? 0 : -rc;
 }

@@ -445,10 +445,11 @@ static int pwf_launch2(const PwfArgs& a, const PwfPlan& p, int nparts, hipStream
 }
 
 // called by mnas_conv_gemm for mode 0, 1x1, stride 1
-int mnas_pwf_forward(const MnasConvGemm* c, void* stream) {
+int mnas_pwf_forward(const MnasConvGemm* c, void* stream, int* inst) {
     PwfPlan p;
     const int M = c->N * c->Ho * c->Wo;
     if (!pwf_plan(M, c->Ci, c->Co, &p)) return MNAS_EINVAL;
+    if (inst) { inst[0] = p.nt; inst[1] = p.pt; inst[2] = p.wres; inst[3] = p.nkc; return MNAS_OK; }
     PwfArgs a;
     a.M = M; a.Ci = c->Ci; a.Co = c->Co;
     a.Kpad = (c->Ci + 31) / 32 * 32;
@@ -466,11 +467,12 @@ int mnas_pwf_forward(const MnasConvGemm* c, void* stream) {
 }
 
 // called by mnas_conv_gemm for mode 1, 1x1, stride 1, no residual (MNAS_EINVAL: not this kernel's shape, caller falls back)
-int mnas_pwd_dgrad(const MnasConvGemm* c, void* stream) {
+int mnas_pwd_dgrad(const MnasConvGemm* c, void* stream, int* inst) {
     PwfPlan p;
     const int M = c->N * c->Ho * c->Wo;
     if (c->resid || c->bias || !pwd_plan(M, c->Ci, c->Co, &p)) return MNAS_EINVAL;
     if ((c->grad.coef == nullptr) != (c->grad.y == nullptr)) return MNAS_EINVAL;
+    if (inst) { inst[0] = p.nt; inst[1] = p.pt; inst[2] = p.wres; inst[3] = p.nkc; return MNAS_OK; }
     PwfArgs a;
     a.M = M; a.Ci = c->Ci; a.Co = c->Co;
     a.Kpad = (c->Ci + 31) / 32 * 32;

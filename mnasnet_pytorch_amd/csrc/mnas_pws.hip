@@ -340,7 +340,7 @@ int mnas_pws_accepts(const MnasConvGemm* c) {
     if (c->mode == 0 && c->gate && (!c->act.scale || p.ksw > 3)) return 0;
     return 1;
 }
-int mnas_pws_run(const MnasConvGemm* c, void* stream) {
+int mnas_pws_run(const MnasConvGemm* c, void* stream, int* inst) {
     const int M = c->N * c->Ho * c->Wo;
     PwsPlan p;
     if (!mnas_pws_accepts(c) || !pws_plan(c->mode, M, c->Ci, c->Co, &p)) return MNAS_EINVAL;
@@ -352,6 +352,7 @@ int mnas_pws_run(const MnasConvGemm* c, void* stream) {
     a.stats = c->stats; a.red_y = c->mode == 1 ? c->red_y : nullptr; a.red_bn = c->red_bn;
     a.gate = c->mode == 0 ? c->gate : nullptr; a.hw = c->Ho * c->Wo;
     if (a.gate && (!c->act.scale || p.ksw > 3)) return MNAS_EINVAL;
+    if (inst) { inst[0] = p.nt; inst[1] = p.ksw; inst[2] = p.nw; inst[3] = a.gate ? 1 : 0; return MNAS_OK; }
     hipStream_t s = (hipStream_t)stream;
     return c->mode == 0 ? pws_dispatch<0>(a, p, c->nparts, s) : pws_dispatch<1>(a, p, c->nparts, s);
 }

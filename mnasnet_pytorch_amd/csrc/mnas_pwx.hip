@@ -198,10 +198,11 @@ int mnas_pwx_parts(int M, int Ci, int Co) {
     return ngroups < want ? ngroups : want;
 }
 
-int mnas_pwx_forward(const MnasConvGemm* c, void* stream) {
+int mnas_pwx_forward(const MnasConvGemm* c, void* stream, int* inst) {
     PwxPlan p;
     const int M = c->N * c->Ho * c->Wo;
     if (!pwx_plan(M, c->Ci, c->Co, &p) || c->resid || c->gate || !c->act.data || !c->out) return MNAS_EINVAL;
+    if (inst) { inst[0] = p.tpw; inst[1] = p.ks; inst[2] = p.nw; return MNAS_OK; }
     PwxArgs a;
     a.M = M; a.Ci = c->Ci; a.Co = c->Co;
     a.Kpad = p.ks * 32;

@@ -257,14 +257,19 @@ extern "C" int mnas_tconv_parts(int N, int Ho, int Wo, int Co, int Ci) {
     return ntiles < want ? ntiles : want;
 }
 
-extern "C" int mnas_tconv_dgrad(const MnasTconvDgrad* c, void* stream) {
+// Launch path and instance query in one function (`inst`, `which`: see mnas_tconv_dgrad_instance in include/mnas.h)
+static int tconv_dgrad_go(const MnasTconvDgrad* c, void* stream, int* inst, int* which) {
     if (!c || !c->dy || !c->w || !c->out || c->nparts < 1) return MNAS_EINVAL;
     if (c->red_y && (!c->red_bn || !c->stats)) return MNAS_EINVAL;
-    if (mnas_tcx_parts(c->N, c->Ho, c->Wo, c->Co, c->Ci) > 0) return mnas_tcx_dgrad(c, stream);    // (incl. the 32-bit offset limit)
-    if (mnas_tcr_parts(c->N, c->Ho, c->Wo, c->Co, c->Ci) > 0) return mnas_tcr_dgrad(c, stream);
+    *which = MNAS_TCONV_TCX;
+    if (mnas_tcx_parts(c->N, c->Ho, c->Wo, c->Co, c->Ci) > 0) return mnas_tcx_dgrad(c, stream, inst);    // (incl. the 32-bit offset limit)
+    *which = MNAS_TCONV_TCR;
+    if (mnas_tcr_parts(c->N, c->Ho, c->Wo, c->Co, c->Ci) > 0) return mnas_tcr_dgrad(c, stream, inst);
+    *which = MNAS_TCONV_TCONV;
     int nt, pt; size_t lds;
     const long long M2 = (long long)c->N * c->Ho * c->Wo;
     if (M2 * 4 * c->Ci > 0x7fffffff || !tconv_ok(c->Ho, c->Wo, c->Co, c->Ci, &nt, &pt, &lds, M2)) return MNAS_EINVAL;
+    if (inst) { inst[0] = nt; inst[1] = pt; return MNAS_OK; }
     TconvArgs a;
     a.M2 = (int)M2; a.Ho = c->Ho; a.Wo = c->Wo; a.Co = c->Co; a.Ci = c->Ci;
     a.K = 4 * c->Co; a.Kpad = (a.K + 31) / 32 * 32; a.nch = a.Kpad / 8; a.N4 = 4 * c->Ci;
@@ -280,4 +285,14 @@ extern "C" int mnas_tconv_dgrad(const MnasTconvDgrad* c, void* stream) {
     MNAS_TC(2) MNAS_TC(3) MNAS_TC(4) MNAS_TC(5) MNAS_TC(6)
 #undef MNAS_TC
     return MNAS_EINVAL;
+}
+extern "C" int mnas_tconv_dgrad(const MnasTconvDgrad* c, void* stream) {
+    int which;
+    return tconv_dgrad_go(c, stream, nullptr, &which);
+}
+extern "C" int mnas_tconv_dgrad_instance(const MnasTconvDgrad* c, int* out) {
+    int inst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, which = 0;
+    const int rc = tconv_dgrad_go(c, nullptr, inst, &which);
+    if (out) for (int i = 0; i < 8; ++i) out[i] = rc == MNAS_OK ? inst[i] : 0;
+    return rc == MNAS_OK ? which : -rc;
 }

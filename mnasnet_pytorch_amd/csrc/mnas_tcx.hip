@@ -225,10 +225,11 @@ int mnas_tcx_parts(int N, int Ho, int Wo, int Co, int Ci) {
     return (int)(groups < want ? groups : want);
 }
 
-int mnas_tcx_dgrad(const MnasTconvDgrad* c, void* stream) {
+int mnas_tcx_dgrad(const MnasTconvDgrad* c, void* stream, int* inst) {
     TcxPlan p;
     const long long M2 = (long long)c->N * c->Ho * c->Wo;
     if (M2 * 4 * c->Ci > 0x7fffffff || !tcx_plan(c->Ho, c->Wo, c->Co, c->Ci, &p)) return MNAS_EINVAL;
+    if (inst) { inst[0] = p.tpw; inst[1] = p.ksm; inst[2] = p.nblocks; return MNAS_OK; }
     TcxArgs a;
     a.M2 = (int)M2; a.Ho = c->Ho; a.Wo = c->Wo; a.Co = c->Co; a.Ci = c->Ci;
     a.Kpad = (4 * c->Co + 31) / 32 * 32; a.rows_pad = (4 * c->Ci + 15) / 16 * 16; a.cib = p.cib;
@@ -458,10 +459,11 @@ int mnas_tcr_parts(int N, int Ho, int Wo, int Co, int Ci) {
     if ((long long)N * 4 * Ho * Wo * Ci > 0x7fffffff) return -1;     // 32-bit element offsets (as mnas_tcr_dgrad checks)
     return pm < N ? pm : N;
 }
-int mnas_tcr_dgrad(const MnasTconvDgrad* c, void* stream) {
+int mnas_tcr_dgrad(const MnasTconvDgrad* c, void* stream, int* inst) {
     int pm; size_t lds;
     if (c->N < 32 || !tcr_plan(c->Ho, c->Wo, c->Co, c->Ci, &pm, &lds)) return MNAS_EINVAL;
     if ((long long)c->N * 4 * c->Ho * c->Wo * c->Ci > 0x7fffffff) return MNAS_EINVAL;
+    if (inst) { inst[0] = 2; inst[1] = 3; inst[2] = 6; inst[3] = c->Ci / 16; return MNAS_OK; }     // the one instantiation; channel slices
     TcrArgs a;
     a.N = c->N; a.Ho = c->Ho; a.Wo = c->Wo; a.Co = c->Co; a.Ci = c->Ci;
     a.Kpad = (4 * c->Co + 31) / 32 * 32; a.rows_pad = (4 * c->Ci + 15) / 16 * 16;

@@ -490,7 +490,7 @@ static void wgrad_t_launch(const WgradArgs& a, int nsplit, hipStream_t s) {
     hipLaunchKernelGGL((k_wgrad_t<CT, KT>), grid, dim3(256), lds, s, a);
 }
 
-extern "C" int mnas_conv_wgrad(const MnasConvWgrad* c, void* stream) {
+static int conv_wgrad_go(const MnasConvWgrad* c, void* stream, int* inst) {
     if (!c || (c->Ci & 7) || (c->Co & 7) || c->nsplit < 1) return MNAS_EINVAL;
     WgradArgs a;
     a.M = c->N * c->Ho * c->Wo;
@@ -506,6 +506,7 @@ extern "C" int mnas_conv_wgrad(const MnasConvWgrad* c, void* stream) {
     a.x = c->x; a.dy = c->dy; a.partial = c->partial;
     int ct, kt;
     wgrad_pick_tiles(a.Co, a.Ktot, &ct, &kt);
+    if (inst) { inst[0] = ct; inst[1] = kt; return MNAS_OK; }
     hipStream_t s = (hipStream_t)stream;
 #define MNAS_WT(C_, K_) if (ct == C_ && kt == K_) wgrad_t_launch<C_, K_>(a, c->nsplit, s);
 #define MNAS_WTC(C_) MNAS_WT(C_, 1) MNAS_WT(C_, 2) MNAS_WT(C_, 3) MNAS_WT(C_, 4)
@@ -514,6 +515,13 @@ extern "C" int mnas_conv_wgrad(const MnasConvWgrad* c, void* stream) {
 #undef MNAS_WT
     MNAS_CHECK_LAUNCH();
     return MNAS_OK;
+}
+extern "C" int mnas_conv_wgrad(const MnasConvWgrad* c, void* stream) { return conv_wgrad_go(c, stream, nullptr); }
+extern "C" int mnas_conv_wgrad_instance(const MnasConvWgrad* c, int* out) {
+    int inst[2] = {0, 0};
+    const int rc = conv_wgrad_go(c, nullptr, inst);
+    if (out) { out[0] = rc == MNAS_OK ? inst[0] : 0; out[1] = rc == MNAS_OK ? inst[1] : 0; }
+    return rc == MNAS_OK ? 0 : -rc;
 }
 
 // Stem weight gradient: partial[split][co][27] already in the reference's [co][ci][kh][kw] order
