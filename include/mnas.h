@@ -56,7 +56,7 @@ typedef struct MnasGradIn {
     const float* coef;    /* float[5][C] */
 } MnasGradIn;
 
-int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, and + mnas_grad_sqnorm / mnas_*_step_ex, and + mnas_head_cross_entropy_soft / mnas_img_mix, all additive: no layout or opcode changed, so still 8; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
+int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, and + mnas_grad_sqnorm / mnas_*_step_ex, and + mnas_head_cross_entropy_soft / mnas_img_mix, and + mnas_img_aug, all additive: no layout or opcode changed, so still 8; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
                                          * 5 = squeeze-excite on load: MnasConvGemm.gate, MnasPwBwd.seg_px -- and in round 5: 6 = the opt-in
                                          * forms that lost their A/B are gone (MnasPwBwd.dy_out / red4, MnasDwBwd.src_* / g_gate / g_bias,
                                          * mnas_dw_exp_*, mnas_irb_*, mnas_gram*, mnas_se_bn_assemble); their opcode numbers stay retired) */
@@ -925,6 +925,71 @@ int mnas_img_mix_check(const MnasImgMix* items_host, int n, int H, int W);
  * by byte otherwise.  Run the host check first; the kernel re-checks each descriptor it reads and writes nothing for one it
  * refuses. */
 int mnas_img_mix(const MnasImgMix* items, int n, int H, int W, const void* in, void* out, void* stream);
+
+/* ---- augmentation-policy ops on uint8 images (csrc/mnas_imga.hip; additive within ABI 8, outside the launch lists): what
+ * RandAugment and the AutoAugment policies are made of, on the (n, 3, H, W) uint8 NCHW batch the stem reads.  Each item holds one
+ * image's chain of up to MNAS_IMGA_MAX_OPS ops, applied in order; each op is byte for byte the Pillow call
+ *     IDENTITY      copy
+ *     AFFINE        img.transform(img.size, Image.AFFINE, (a, b, c, d, e, f), Image.NEAREST, fillcolor=fill), as 16.16 fixed point:
+ *                   arg = {a0, a1, a2, a3, a4, a5} with FIX(v) = floor(v * 65536 + 0.5), a0, a1, a3, a4 = FIX(a, b, d, e),
+ *                   a2 = FIX(c + a/2 + b/2), a5 = FIX(f + d/2 + e/2); output (x, y) takes the source pixel
+ *                   ((a2 + x a0 + y a1) >> 16, (a5 + x a3 + y a4) >> 16) when it lies inside the image, the fill colour otherwise.
+ *                   With a1 == a3 == 0 Pillow takes a route of its own that agrees with this one for unit scale and whole-pixel
+ *                   translations, so such a matrix must have a0 == a4 == 65536 and a2, a5 = (whole pixels << 16) + 32768.
+ *     BRIGHTNESS / COLOR / CONTRAST   ImageEnhance.*(img).enhance(factor): MNAS_IMGC_BRIGHTNESS / _SATURATION / _CONTRAST's arithmetic
+ *     SHARPNESS     ImageEnhance.Sharpness(img).enhance(factor) = Image.blend(img.filter(ImageFilter.SMOOTH), img, factor); SMOOTH is
+ *                   (1 1 1 / 1 5 1 / 1 1 1) / 13 rounded to nearest on interior pixels, the outermost rows and columns copied,
+ *                   an image with H < 3 or W < 3 unchanged
+ *     POSTERIZE     ImageOps.posterize(img, bits), bits = arg[0] in [1, 8]
+ *     SOLARIZE      ImageOps.solarize(img, threshold), threshold = arg[0] in [0, 256]
+ *     INVERT        ImageOps.invert(img)
+ *     AUTOCONTRAST  ImageOps.autocontrast(img) (cutoff 0, per channel)
+ *     EQUALIZE      ImageOps.equalize(img) (per channel)
+ * CONTRAST, AUTOCONTRAST and EQUALIZE take their statistics (grey mean, per-channel histograms) over the image as the ops before
+ * them left it. */
+#define MNAS_IMGA_IDENTITY     0
+#define MNAS_IMGA_AFFINE       1
+#define MNAS_IMGA_BRIGHTNESS   2
+#define MNAS_IMGA_COLOR        3
+#define MNAS_IMGA_CONTRAST     4
+#define MNAS_IMGA_SHARPNESS    5
+#define MNAS_IMGA_POSTERIZE    6
+#define MNAS_IMGA_SOLARIZE     7
+#define MNAS_IMGA_INVERT       8
+#define MNAS_IMGA_AUTOCONTRAST 9
+#define MNAS_IMGA_EQUALIZE     10
+#define MNAS_IMGA_MAX_OPS      4
+typedef struct MnasImgAug {            /* 136 bytes */
+    int32_t nops;                      /* 0..MNAS_IMGA_MAX_OPS, applied in order; 0 = copy */
+    int32_t op[MNAS_IMGA_MAX_OPS];     /* MNAS_IMGA_* */
+    float factor[MNAS_IMGA_MAX_OPS];   /* BRIGHTNESS / COLOR / CONTRAST / SHARPNESS: finite and >= 0; other ops: not read */
+    int32_t arg[MNAS_IMGA_MAX_OPS][6]; /* AFFINE: a0..a5; POSTERIZE: bits; SOLARIZE: threshold; other ops: not read */
+    int32_t reserved;                  /* 0 */
+} MnasImgAug;
+/* Host-side validation, no launch: every item's nops in [0, MAX_OPS], ops known, enhancer factors finite and >= 0, bits in [1, 8],
+ * threshold in [0, 256], reserved 0, and every AFFINE matrix in range: a1 == a3 == 0 only in the form above, and a2 + x a0 + y a1
+ * and a5 + x a3 + y a4 inside (-2^31, 2^31) at the four corners x in {0, W}, y in {0, H} (so the device's int32 arithmetic cannot
+ * overflow, and Pillow, which leaves fixed point outside that range, is still what the bytes equal); n in [0, 65535], H, W in
+ * [1, MNAS_IMGX_MAX_OUT].  0 or MNAS_EINVAL.  items_host: HOST. */
+int mnas_img_aug_check(const MnasImgAug* items_host, int n, int H, int W);
+/* Bytes of device workspace mnas_img_aug needs: one spare batch (16-byte rounded) when max_ops >= 2, plus, when need_stats != 0
+ * (some item has CONTRAST, AUTOCONTRAST or EQUALIZE), 769 uint32 per (image, 16384-pixel chunk).  max_ops: the longest chain of the
+ * batch, in [0, MAX_OPS].  0 is a valid answer; -1 for a bad shape or max_ops. */
+int64_t mnas_img_aug_workspace_bytes(int n, int H, int W, int max_ops, int need_stats);
+/* items (n descriptors), in and out (n*3*H*W bytes each, contiguous NCHW) and workspace: device; no two of the three buffers may
+ * overlap (out of place only).  The ops run stage by stage, S = max(1, max_ops) stages, each one launch over the whole batch that
+ * applies one op per image out of place, ping-ponging between out and the workspace so that the last stage writes out.  Chains
+ * are right-aligned: an image of L ops (an empty chain counts as one IDENTITY) sits out the first S - L stages and then reads `in`,
+ * so its last op lands in out with no copy stage.  stats_stages: bit s set when some image's op of stage s is CONTRAST,
+ * AUTOCONTRAST or EQUALIZE; such a stage is preceded by a statistics launch over its input (LDS histograms, per (image, chunk)
+ * partial tables in the workspace, no global atomics), and the apply launch reduces them into the image's mean or 3 x 256 table.
+ * max_ops and stats_stages are the caller's, computed from the same descriptors it checked: a stage or statistics launch no image
+ * needs is not launched.  fill_rgb: AFFINE's fill colour, r | g << 8 | b << 16.  workspace: mnas_img_aug_workspace_bytes(n, H, W,
+ * max_ops, stats_stages != 0) bytes, 16-byte aligned, or null when that is 0.  16-byte loads and stores when H*W % 16 == 0 and the
+ * buffers are 16-byte aligned, byte by byte otherwise.  Run the host check first; the kernels re-check each descriptor they read
+ * and write nothing for one they refuse (a chain longer than max_ops, or a statistics op at a stage whose bit is clear, included). */
+int mnas_img_aug(const MnasImgAug* items, int n, int H, int W, int max_ops, int stats_stages, int fill_rgb, const void* in,
+                 void* out, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

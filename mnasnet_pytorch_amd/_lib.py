@@ -126,6 +126,16 @@ class MnasImgMix(C.Structure):
 IMGM_NONE, IMGM_MIXUP, IMGM_CUTMIX = 0, 1, 2         # MNAS_IMGM_*
 
 
+class MnasImgAug(C.Structure):
+    _fields_ = [("nops", C.c_int32), ("op", C.c_int32 * 4), ("factor", C.c_float * 4), ("arg", (C.c_int32 * 6) * 4),
+                ("reserved", C.c_int32)]
+
+
+(IMGA_IDENTITY, IMGA_AFFINE, IMGA_BRIGHTNESS, IMGA_COLOR, IMGA_CONTRAST, IMGA_SHARPNESS, IMGA_POSTERIZE, IMGA_SOLARIZE, IMGA_INVERT,
+ IMGA_AUTOCONTRAST, IMGA_EQUALIZE) = range(11)         # MNAS_IMGA_*
+IMGA_MAX_OPS = 4
+
+
 class MnasOp(C.Structure):
     _fields_ = [("opcode", C.c_int32), ("i", C.c_int32 * 15), ("d", C.c_double * 4), ("p", c_void_p * 16)]
 
@@ -424,6 +434,9 @@ SYMBOLS = {
     "mnas_img_color": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "mnas_img_mix_check": (c_int, [C.POINTER(MnasImgMix), c_int, c_int, c_int]),
     "mnas_img_mix": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "mnas_img_aug_check": (c_int, [C.POINTER(MnasImgAug), c_int, c_int, c_int]),
+    "mnas_img_aug_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "mnas_img_aug": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
