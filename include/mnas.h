@@ -56,7 +56,7 @@ typedef struct MnasGradIn {
     const float* coef;    /* float[5][C] */
 } MnasGradIn;
 
-int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, and + mnas_grad_sqnorm / mnas_*_step_ex, and + mnas_head_cross_entropy_soft / mnas_img_mix, and + mnas_img_aug, all additive: no layout or opcode changed, so still 8; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
+int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, and + mnas_grad_sqnorm / mnas_*_step_ex, and + mnas_head_cross_entropy_soft / mnas_img_mix, and + mnas_img_aug, and + mnas_head_cross_entropy_kd, all additive: no layout or opcode changed, so still 8; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
                                          * 5 = squeeze-excite on load: MnasConvGemm.gate, MnasPwBwd.seg_px -- and in round 5: 6 = the opt-in
                                          * forms that lost their A/B are gone (MnasPwBwd.dy_out / red4, MnasDwBwd.src_* / g_gate / g_bias,
                                          * mnas_dw_exp_*, mnas_irb_*, mnas_gram*, mnas_se_bn_assemble); their opcode numbers stay retired) */
@@ -531,6 +531,46 @@ int mnas_head_cross_entropy_soft(const void* logits, const void* target_a, const
                                  float label_smoothing, int N, int C, int64_t ignore_index, void* loss_rows, void* loss,
                                  void* dlogits, void* bad_flag, const int* ks, int nk, void* rank_rows, MnasMeters* meters,
                                  void* stream);
+
+/* ---- distillation cross-entropy (csrc/mnas_head.hip; additive within ABI 8, outside the launch lists): class weights and a dense
+ * teacher distribution (knowledge distillation, Hinton et al. 2015) on top of the soft-target loss above.  Labels a, b, weight l,
+ * eps and the target row q are those of mnas_head_cross_entropy_soft; class_weight w (device fp32 [C], finite and >= 0; NULL: every
+ * weight 1) and teacher_logits t (device fp32 [N][C]; NULL: no distillation term) are optional.  With p = softmax(z[n]):
+ *     hard_n = -sum_c w[c] q[c] log p[c]
+ *            = (1 - eps) (l w[a] (lse - z[a]) + (1 - l) w[b] (lse - z[b])) + eps (Wm lse - sum_c w[c] z[c] / C),   Wm = mean_c w[c]
+ *     s_n    = l w[a] + (1 - l) w[b],   D = sum of s_n over the rows not ignored,   hard = sum_n hard_n / D
+ * which for a plain class vector is F.cross_entropy(z, y, weight=w, label_smoothing=eps) and with w == 1 the value of
+ * mnas_head_cross_entropy_soft; and with pT = softmax(t[n] / T), pS = softmax(z[n] / T), T = temperature > 0:
+ *     kd_n = sum_c pT[c] (log pT[c] - log pS[c]),   kd = T^2 sum_n kd_n / N       (all N rows, ignored ones included)
+ * which is T^2 F.kl_div(log_softmax(z / T), softmax(t / T), reduction='batchmean').  *loss = (1 - alpha) hard + alpha kd;
+ *     dlogits[n][c] = (1 - alpha) (p[c] S_n - w[c] q[c]) / D + alpha T (pS[c] - pT[c]) / N,   S_n = sum_c w[c] q[c]   (NULL: forward only)
+ * loss_rows: device fp32 [2 N], hard_n in the first half and kd_n in the second; loss_parts: device fp32 [2] = (hard, kd), or NULL.
+ * Rules:
+ *   - a class with pT[c] == 0 (a -inf teacher logit: a masked class) adds exactly 0 to kd_n, never 0 * inf;
+ *   - a -inf student logit where pT[c] > 0 makes the row's kd_n +inf; its gradient stays finite;
+ *   - alpha == 1: the hard term is left out of *loss and of dlogits (no 0 * inf; the eps == 0 precedent); loss_rows' first half and
+ *     loss_parts[0] are still written;
+ *   - alpha == 0 or t == NULL: the distillation term is left out, t is not read, *loss = hard (whatever alpha is when t == NULL),
+ *     kd_n and loss_parts[1] are 0;
+ *   - NaN logits give NaN results;
+ *   - an ignored row (a or, with mixing, b == ignore_index) adds 0 to the hard term, to D and to the hard gradient; it takes part
+ *     in the distillation term like any other row;
+ *   - a refused row -- a label outside [0, C), an l that is NaN or outside [0, 1] -- sets *bad_flag and poisons *loss and both
+ *     parts with NaN; its dlogits row is all zeros; it indexes no memory (neither z nor w);
+ *   - D == 0: hard = 0/0 = NaN (every row ignored, or every counted weight 0); the hard gradient is then 0;
+ *   - eps == 0: no smoothing term, as in mnas_head_cross_entropy_soft;
+ *   - temperature not > 0, alpha or label_smoothing outside [0, 1] (NaN included), a NULL logits / target_a / loss_rows / loss /
+ *     bad_flag, N or C < 1: MNAS_EINVAL, no launch.  The class weights are NOT checked on the device (the Python layer refuses
+ *     negative and non-finite ones).
+ * Two launches (one 256-lane workgroup per row, one workgroup for the two means and the meters), fixed summation order, no float
+ * atomics: bit-identical from run to run; no allocation and no host read: capturable.  Any N >= 1, C >= 1.  meters as for
+ * mnas_head_cross_entropy_soft (a row is ranked against its heavier label); the loss meter receives *loss.  The kernel's operation
+ * order is written out above k_head_ce_kd. */
+int mnas_head_cross_entropy_kd(const void* logits, const void* target_a, const void* target_b, const float* lam,
+                               float label_smoothing, const float* class_weight, const void* teacher_logits, float temperature,
+                               float alpha, int N, int C, int64_t ignore_index, void* loss_rows, void* loss, void* loss_parts,
+                               void* dlogits, void* bad_flag, const int* ks, int nk, void* rank_rows, MnasMeters* meters,
+                               void* stream);
 
 /* ---- the multi-label branch of the step (csrc/mnas_mlabel.hip): MultiClassBCELoss (src/models/multi_class_loss.py), HardDice
  * and the per-sample macro-F1 of batch_metrics (src/utils/metric.py) as train.py:274-279, 453-463, 577-587 use them, with the three

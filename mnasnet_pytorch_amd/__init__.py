@@ -12,7 +12,7 @@ from .sampler import ClusterRandomSampler, DistributedClusterSampler  # noqa: F4
 from .transforms import (DeviceColorJitter, DevicePipeline, DeviceRandomGrayscale, DeviceTransform, ImageBatch,  # noqa: F401
                          collate_decoded)
 from .metrics import DeviceMeters, MultiLabelMeters, accuracy  # noqa: F401
-from .losses import HardDice, MixCrossEntropyLoss, MultiClassBCELoss  # noqa: F401
+from .losses import DistillCrossEntropyLoss, DistillTarget, HardDice, MixCrossEntropyLoss, MultiClassBCELoss  # noqa: F401
 from .mixing import DeviceMix, MixedTarget  # noqa: F401
 from .augment import DeviceRandAugment, aug_apply  # noqa: F401
 
@@ -20,4 +20,4 @@ __all__ = ["Mnasnet", "ConvBlock", "SepConv", "MBConv_block", "MBConv", "load_mo
            "ClusterRandomSampler", "DistributedClusterSampler", "DeviceTransform", "ImageBatch", "collate_decoded",
            "DevicePipeline", "DeviceColorJitter", "DeviceRandomGrayscale", "DeviceMeters", "accuracy",
            "MultiLabelMeters", "MultiClassBCELoss", "HardDice", "MixCrossEntropyLoss", "DeviceMix", "MixedTarget",
-           "DeviceRandAugment", "aug_apply"]
+           "DeviceRandAugment", "aug_apply", "DistillCrossEntropyLoss", "DistillTarget"]

@@ -336,6 +336,9 @@ SYMBOLS = {
                                   c_void_p]),
     "mnas_head_cross_entropy_soft": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int64, c_void_p,
                                              c_void_p, c_void_p, c_void_p, C.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
+    "mnas_head_cross_entropy_kd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_float, c_float, c_int,
+                                           c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.POINTER(c_int), c_int,
+                                           c_void_p, c_void_p, c_void_p]),
     "mnas_mlabel_scratch_bytes": (c_int64, [c_int]),
     "mnas_mlabel_bce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_int64, c_int64, c_int64, c_void_p]),

@@ -566,6 +566,200 @@ extern "C" int mnas_head_cross_entropy_soft(const void* logits, const void* targ
     return MNAS_OK;
 }
 
+// ---- class weights and knowledge distillation on top of the soft-target loss (include/mnas.h "distillation cross-entropy") ------------
+// Labels a, b, weight l, smoothing eps and the target row q of k_head_ce_soft; class weights w[C] (NULL: all 1) and teacher logits
+// t (NULL: no distillation term) are new.  The same launch shape: one workgroup per row, one workgroup for the means.
+//
+// Operation order (every line one fp32 operation unless it says otherwise; "sum" = the lane's strided sum, the six butterfly levels
+// and the three adds of the four waves of head_wg_reduce: ceil(n / 256) + 9 adds; tests/bounds_kd.py brackets exactly this):
+//   row weight   s_i = 0 for an ignored row, 1 without w, else w[a] when a == b, else fmaf(l, w[a] - w[b], w[b]);  D = sum_i s_i
+//   pass 1       mx = max_c z (exact);  swz = sum_c fmaf(w_c, z_c, .) (the fma IS the add);  sw = sum_c w_c;  KD: mt = max_c t
+//                Wm = sw / C (1 without w);  invT = 1 / T
+//   pass 2       d_c = z_c - mx;  se = sum_c expf(d_c);   KD: eS_c = expf(d_c invT), seS = sum eS;  dt_c = t_c - mt,
+//                eT_c = expf(dt_c invT), seT = sum eT;  sA = sum_c eT_c (dt_c - d_c), a class with eT_c == 0 adds exactly 0
+//   scalars      rse = 1 / se, rseS = 1 / seS, rseT = 1 / seT;  wa, wb, u = eps / C as in k_head_ce_soft;
+//                S = fmaf(eps, Wm - s_n, s_n)  (= sum_c w_c q_c; exactly 1 when every weight is 1);
+//                invD = 1 / D (0 when the row is not valid or D is not > 0);  ch = (1 - alpha) invD;  ck = (alpha T) / N
+//   gradient     p = expf(d_c) rse;  q = (qa + qb) + u;  g = (p S - w_c q) ch   (0: row not valid, or alpha == 1)
+//                KD: pS = eS_c rseS, pT = eT_c rseT (both exponentials evaluated again), g = g + ck (pS - pT)
+//   hard row     lse = logf(se) + mx;  sm = Wm lse - swz / C (0 when eps == 0);
+//                (wa w[a]) (lse - z[a]) + (wb w[b]) (lse - z[b]) + eps sm          (0: ignored row; NaN: refused row)
+//   kd row       (sA rseT) invT + (logf(seS) - logf(seT))                          (NaN: refused row; 0: no distillation term)
+// The build contracts a * b + c into an fma where it likes (-ffp-contract=fast); the bracket of the uncontracted form holds either.
+// Without w and t every factor above that involves them is exactly 1 or 0: the results are those of k_head_ce_soft's expressions.
+__device__ __forceinline__ bool head_kd_refused(long long a, long long b, float l, int C) {
+    return !(a >= 0 && a < C && b >= 0 && b < C && l >= 0.f && l <= 1.f);                   // a NaN l fails both
+}
+
+__device__ __forceinline__ float head_kd_mix_weight(float wa, float wb, float l, bool same) { return same ? wa : fmaf(l, wa - wb, wb); }
+
+// s_i: what row i adds to the divisor D.  A refused row indexes nothing (its NaN loss row poisons the mean anyway)
+__device__ __forceinline__ float head_kd_row_weight(const long long* ta, const long long* tb, const float* lam, const float* w, int i,
+                                                    int C, long long ignore_index) {
+    if (!head_soft_counts(ta, tb, i, ignore_index)) return 0.f;
+    if (!w) return 1.f;
+    const long long a = ta[i], b = tb ? tb[i] : a;
+    const float l = (tb && lam) ? lam[i] : 1.f;
+    if (head_kd_refused(a, b, l, C)) return 0.f;
+    return head_kd_mix_weight(w[a], w[b], l, a == b);
+}
+
+template <bool METRICS>
+__global__ __launch_bounds__(256) void k_head_ce_kd(const float* x, const long long* ta, const long long* tb, const float* lam, float eps,
+                                                    const float* w, const float* t, float T, float alpha, int N, int C,
+                                                    long long ignore_index, float* loss_rows, float* dlogits, int* bad, int* rank_rows) {
+    __shared__ float red[4];
+    __shared__ int redi[4];
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const float* row = x + (size_t)n * C;
+    const bool kd = t != nullptr;                       // the host passes NULL when alpha == 0: t is not read
+    const float* trow = kd ? t + (size_t)n * C : nullptr;
+    float D = 0.f;
+    for (int i = tid; i < N; i += 256) D += head_kd_row_weight(ta, tb, lam, w, i, C, ignore_index);
+    D = head_wg_reduce(D, red, false);
+    const long long a = ta[n], b = tb ? tb[n] : a;
+    const float l = (tb && lam) ? lam[n] : 1.f;
+    const bool ignored = a == ignore_index || b == ignore_index;
+    const bool refused = !ignored && head_kd_refused(a, b, l, C);
+    const bool valid = !ignored && !refused;
+    if (refused) {
+        if (tid == 0) atomicExch(bad, 1);
+    }
+    float mx = -INFINITY, mt = -INFINITY, swz = 0.f, sw = 0.f;
+    {
+        const int ti = (int)(l >= 0.5f ? a : b);
+        const float zt = (METRICS && valid) ? row[ti] : 0.f;
+        int above = 0;
+        for (int c = tid; c < C; c += 256) {
+            const float z = row[c], wc = w ? w[c] : 1.f;
+            mx = fmaxf(mx, z);
+            swz = fmaf(wc, z, swz);
+            sw += wc;
+            if (kd) mt = fmaxf(mt, trow[c]);
+            if (METRICS) above += (z > zt || (z == zt && c < ti)) ? 1 : 0;
+        }
+        if (METRICS) {
+            above = head_wg_reduce_int(above, redi);
+            if (tid == 0) rank_rows[n] = (valid && isfinite(zt)) ? above : HEAD_RANK_WRONG;
+        }
+    }
+    mx = head_wg_reduce(mx, red, true);
+    swz = head_wg_reduce(swz, red, false);
+    float Wm = 1.f;
+    if (w) Wm = head_wg_reduce(sw, red, false) / (float)C;
+    const float invT = 1.f / T;
+    float se = 0.f, seS = 0.f, seT = 0.f, sA = 0.f;
+    if (kd) {
+        mt = head_wg_reduce(mt, red, true);
+        for (int c = tid; c < C; c += 256) {
+            const float d = row[c] - mx, dt = trow[c] - mt;
+            const float eT = expf(dt * invT);
+            se += expf(d);
+            seS += expf(d * invT);
+            seT += eT;
+            sA += eT > 0.f ? eT * (dt - d) : 0.f;       // pT == 0 (a masked teacher class): exactly 0, never 0 * inf
+        }
+        seS = head_wg_reduce(seS, red, false);
+        seT = head_wg_reduce(seT, red, false);
+        sA = head_wg_reduce(sA, red, false);
+    } else {
+        for (int c = tid; c < C; c += 256) se += expf(row[c] - mx);
+    }
+    se = head_wg_reduce(se, red, false);
+    const float rse = 1.f / se, rseS = 1.f / seS, rseT = 1.f / seT;
+    // the target row's weights, as k_head_ce_soft forms them
+    const bool same = a == b;
+    const float wa = same ? 1.f - eps : (1.f - eps) * l, wb = same ? 0.f : (1.f - eps) - wa, u = eps / (float)C;
+    const float wA = (valid && w) ? w[a] : 1.f, wB = (valid && w) ? w[b] : 1.f;
+    const float sn = head_kd_mix_weight(wA, wB, l, same), S = fmaf(eps, Wm - sn, sn);
+    const bool hard_on = !(kd && alpha == 1.f);         // alpha == 1: the hard term is left out, no 0 * inf
+    const float invD = valid && D > 0.f ? 1.f / D : 0.f;
+    const float ch = kd ? (1.f - alpha) * invD : invD, ck = kd ? alpha * T / (float)N : 0.f;
+    if (dlogits)
+        for (int c = tid; c < C; c += 256) {
+            const float d = row[c] - mx, wc = w ? w[c] : 1.f;
+            const float p = expf(d) * rse;
+            const float q = (c == (int)a ? wa : 0.f) + (c == (int)b && !same ? wb : 0.f) + u;
+            float g = (valid && hard_on) ? (p * S - wc * q) * ch : 0.f;
+            if (kd) {
+                const float pS = expf(d * invT) * rseS, pT = expf((trow[c] - mt) * invT) * rseT;
+                g = g + ck * (pS - pT);
+            }
+            dlogits[(size_t)n * C + c] = refused ? 0.f : g;
+        }
+    if (tid == 0) {
+        float rh = ignored ? 0.f : NAN, rk = 0.f;          // a refused row poisons both parts
+        if (valid) {
+            const float lse = logf(se) + mx;
+            // eps == 0: no smoothing term, as in k_head_ce_soft (a -inf logit at a class that is no label leaves the row finite)
+            const float sm = eps != 0.f ? Wm * lse - swz / (float)C : 0.f;
+            rh = (wa * wA) * (lse - row[a]) + (wb * wB) * (lse - row[b]) + eps * sm;
+        }
+        if (kd) rk = refused ? NAN : sA * rseT * invT + (logf(seS) - logf(seT));
+        loss_rows[n] = rh;
+        loss_rows[(size_t)N + n] = rk;
+    }
+}
+
+// hard = sum(hard rows) / D, kd = (T T) (sum(kd rows) / N), loss = (1 - alpha) hard + alpha kd  (hard alone without the distillation
+// term, kd alone at alpha == 1); the three sums as in k_head_loss_mean_soft
+template <bool METRICS>
+__global__ __launch_bounds__(256) void k_head_loss_mean_kd(const float* loss_rows, const long long* ta, const long long* tb, const float* lam,
+                                                           const float* w, int N, int C, long long ignore_index, int kd, float T,
+                                                           float alpha, float* loss, float* parts, const int* rank_rows, HeadKs ks,
+                                                           MnasMeters* meters) {
+    __shared__ float red[4];
+    __shared__ int redi[4];
+    float sh = 0.f, sk = 0.f, D = 0.f;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        sh += loss_rows[i];
+        sk += loss_rows[(size_t)N + i];
+        D += head_kd_row_weight(ta, tb, lam, w, i, C, ignore_index);
+    }
+    sh = head_wg_reduce(sh, red, false);
+    sk = head_wg_reduce(sk, red, false);
+    D = head_wg_reduce(D, red, false);
+    if (threadIdx.x == 0) {
+        const float hard = sh / D;                      // 0/0 = nan when every row is ignored (or every counted weight is 0)
+        const float kdv = kd ? (T * T) * (sk / (float)N) : 0.f;
+        *loss = !kd ? hard : (alpha == 1.f ? kdv : (1.f - alpha) * hard + alpha * kdv);
+        if (parts) { parts[0] = hard; parts[1] = kdv; }
+    }
+    if (METRICS) head_meters_update(rank_rows, N, ks, loss, meters, redi);   // thread 0 reads back its own store
+}
+
+extern "C" int mnas_head_cross_entropy_kd(const void* logits, const void* target_a, const void* target_b, const float* lam,
+                                          float label_smoothing, const float* class_weight, const void* teacher_logits, float temperature,
+                                          float alpha, int N, int C, int64_t ignore_index, void* loss_rows, void* loss, void* loss_parts,
+                                          void* dlogits, void* bad_flag, const int* ks, int nk, void* rank_rows, MnasMeters* meters,
+                                          void* stream) {
+    if (!logits || !target_a || !loss_rows || !loss || !bad_flag || N < 1 || C < 1) return MNAS_EINVAL;
+    if (!(label_smoothing >= 0.f && label_smoothing <= 1.f) || !(alpha >= 0.f && alpha <= 1.f) || !(temperature > 0.f)) return MNAS_EINVAL;
+    HeadKs k = {};
+    if (meters && (!rank_rows || head_ks(ks, nk, C, &k) != MNAS_OK)) return MNAS_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const float* x = (const float*)logits;
+    const float* t = alpha != 0.f ? (const float*)teacher_logits : nullptr;      // alpha == 0: no distillation term, t is not read
+    const long long *ta = (const long long*)target_a, *tb = (const long long*)target_b;
+    if (meters) {
+        hipLaunchKernelGGL(k_head_ce_kd<true>, dim3(N), dim3(256), 0, s, x, ta, tb, lam, label_smoothing, class_weight, t, temperature, alpha,
+                           N, C, (long long)ignore_index, (float*)loss_rows, (float*)dlogits, (int*)bad_flag, (int*)rank_rows);
+        MNAS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_head_loss_mean_kd<true>, dim3(1), dim3(256), 0, s, (const float*)loss_rows, ta, tb, lam, class_weight, N, C,
+                           (long long)ignore_index, t ? 1 : 0, temperature, alpha, (float*)loss, (float*)loss_parts, (const int*)rank_rows, k,
+                           meters);
+    } else {
+        hipLaunchKernelGGL(k_head_ce_kd<false>, dim3(N), dim3(256), 0, s, x, ta, tb, lam, label_smoothing, class_weight, t, temperature, alpha,
+                           N, C, (long long)ignore_index, (float*)loss_rows, (float*)dlogits, (int*)bad_flag, (int*)nullptr);
+        MNAS_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_head_loss_mean_kd<false>, dim3(1), dim3(256), 0, s, (const float*)loss_rows, ta, tb, lam, class_weight, N, C,
+                           (long long)ignore_index, t ? 1 : 0, temperature, alpha, (float*)loss, (float*)loss_parts, (const int*)nullptr,
+                           HeadKs{}, (MnasMeters*)nullptr);
+    }
+    MNAS_CHECK_LAUNCH();
+    return MNAS_OK;
+}
+
 // ---- the same counts for logits from anywhere (module path, another criterion, no loss at all): one workgroup per row for the
 // ranks, one workgroup for the block.  No ignore_index here: a target outside [0, C) is a wrong row.
 __global__ __launch_bounds__(256) void k_head_rank(const float* x, const long long* target, int C, int* rank_rows) {

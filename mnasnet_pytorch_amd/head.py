@@ -7,7 +7,9 @@ Two entry points share the same kernels:
   ``model(x)`` / ``criterion(out, target)`` / ``loss.backward()`` of train.py:434-439 work unchanged;
 * :meth:`NativeHead.loss_and_grad` -- logits, cross-entropy, and the whole backward of the head in 8 launches without
   autograd; ``Trainer.step`` takes this path when the criterion is a plain ``nn.CrossEntropyLoss`` or this package's
-  ``MultiClassBCELoss`` (the multi-label branch: :meth:`NativeHead.bce`, csrc/mnas_mlabel.hip).
+  ``MultiClassBCELoss`` (the multi-label branch: :meth:`NativeHead.bce`, csrc/mnas_mlabel.hip), ``MixCrossEntropyLoss``
+  (:meth:`NativeHead.cross_entropy_soft`) or ``DistillCrossEntropyLoss`` (class weights and a teacher's logits:
+  :meth:`NativeHead.cross_entropy_kd`).
 
 Dropout masks are a counter-based hash of (seed, element index) evaluated inside the GEMM kernels (never stored).  The seed
 of a call is derived from ``torch.initial_seed()``, the rank and a per-head call counter, so runs are reproducible under
@@ -104,6 +106,7 @@ class NativeHead:
             rank = torch.distributed.get_rank()
         self.seed0 = _mix(torch.initial_seed() & _MASK64, rank, 0x48454144)
         self._scratch = {}
+        self._kd_rows = {}               # (N, device) -> the 2 N loss rows of cross_entropy_kd
 
     @staticmethod
     def build(seq: nn.Module) -> Optional["NativeHead"]:
@@ -219,6 +222,33 @@ class NativeHead:
         rows, bad = self._scratch[key]
         return soft_cross_entropy(logits, a, b, lam, label_smoothing, ignore_index, rows=rows, bad=bad, need_grad=need_grad, meters=meters)
 
+    def cross_entropy_kd(self, logits, target, criterion, need_grad=True, meters=None):
+        """-> (loss 0-d tensor, dlogits or None) of a losses.DistillCrossEntropyLoss ``criterion``: class weights, label smoothing
+        and the distillation term in two launches (mnas_head_cross_entropy_kd).  ``target``: a class vector, a mixing.MixedTarget
+        or a losses.DistillTarget around either (only that one carries teacher logits).  Without a weight and without a teacher
+        it is :meth:`cross_entropy_soft` (and through it the plain kernel): such a criterion steps bit for bit like a
+        MixCrossEntropyLoss or an nn.CrossEntropyLoss with the same settings.  ``criterion.last_parts`` names (hard, kd) on the
+        device afterwards (None after the fall-through case, which has no parts)."""
+        from .losses import DistillTarget, kd_cross_entropy, split_distill_target
+        N, dev = logits.shape[0], logits.device
+        if isinstance(target, DistillTarget):
+            target.check_device(dev)
+        a, b, lam, teacher = split_distill_target(target)
+        weight = criterion.class_weight(logits)
+        if weight is None and teacher is None:
+            plain = target.target if isinstance(target, DistillTarget) else target
+            criterion.last_parts = None
+            return self.cross_entropy_soft(logits, plain, criterion.label_smoothing, criterion.ignore_index, need_grad=need_grad,
+                                           meters=meters)
+        if b is not None:
+            (target.target if isinstance(target, DistillTarget) else target).check_device(dev)
+        key = (N, dev)
+        if key not in self._kd_rows:
+            self._kd_rows[key] = torch.empty(2 * N, dtype=torch.float32, device=dev)
+        bad, parts = criterion.buffers_for(dev)
+        return kd_cross_entropy(logits, a, b, lam, criterion.label_smoothing, weight, teacher, criterion.temperature, criterion.alpha,
+                                criterion.ignore_index, rows=self._kd_rows[key], bad=bad, parts=parts, need_grad=need_grad, meters=meters)
+
     def bce(self, logits, target, criterion, weights=None, need_grad=True, meters=None, f1_n=None):
         """-> (loss 0-d tensor, dlogits or None) of a losses.MultiClassBCELoss ``criterion`` (csrc/mnas_mlabel.hip).  target: (N, C),
         converted with .float() as train.py:429 does.  ``meters`` (a metrics.MultiLabelMeters): the same launches also update its
@@ -251,14 +281,17 @@ class NativeHead:
         """Forward, loss and full backward of the head without autograd.  Parameter gradients are ACCUMULATED into
         ``p.grad`` (which must exist: Trainer points them into its flat gradient buffer).  -> (logits, loss, dx).
         ``criterion``: None / an nn.CrossEntropyLoss -> cross-entropy with ``ignore_index``; a losses.MultiClassBCELoss -> :meth:`bce`;
-        a losses.MixCrossEntropyLoss -> :meth:`cross_entropy_soft` (``target``: a class vector or a mixing.MixedTarget)."""
-        from .losses import MixCrossEntropyLoss, MultiClassBCELoss
+        a losses.MixCrossEntropyLoss -> :meth:`cross_entropy_soft` (``target``: a class vector or a mixing.MixedTarget); a
+        losses.DistillCrossEntropyLoss -> :meth:`cross_entropy_kd` (``target``: either of those, or a losses.DistillTarget)."""
+        from .losses import DistillCrossEntropyLoss, MixCrossEntropyLoss, MultiClassBCELoss
         seeds = self.next_seeds()
         us, logits = self.forward_layers(x, seeds)
         if type(criterion) is MultiClassBCELoss:             # the class itself, as Trainer routes it
             loss, dl = self.bce(logits, target, criterion, meters=meters, f1_n=f1_n)
         elif type(criterion) is MixCrossEntropyLoss:
             loss, dl = self.cross_entropy_soft(logits, target, criterion.label_smoothing, criterion.ignore_index, meters=meters)
+        elif type(criterion) is DistillCrossEntropyLoss:
+            loss, dl = self.cross_entropy_kd(logits, target, criterion, meters=meters)
         else:
             loss, dl = self.cross_entropy(logits, target, ignore_index, meters=meters)
         grads = []

@@ -9,6 +9,9 @@ builds ``MultiClassBCELoss()`` and ``HardDice(threshold=0.5)`` when ``--multi_cl
 * :class:`MixCrossEntropyLoss` -- not from the reference: cross-entropy with label smoothing over class indices or over the two
   labels per row of a mixed batch (mixing.MixedTarget; csrc/mnas_head.hip, include/mnas.h "soft-target cross-entropy").  ``Trainer``
   recognises this class too (head.NativeHead.cross_entropy_soft).
+* :class:`DistillCrossEntropyLoss` / :class:`DistillTarget` -- not from the reference either: class weights, label smoothing and a
+  knowledge-distillation term against a teacher's logits in the same two launches (include/mnas.h "distillation cross-entropy";
+  head.NativeHead.cross_entropy_kd).  ``Trainer(teacher=...)`` runs the teacher's forward and wraps the target.
 
 Deviations: the Dice prediction is ``outputs > logit(threshold)`` instead of ``sigmoid(outputs) > threshold`` (equal except where
 the fp32 sigmoid rounds onto the threshold), so the threshold must lie inside (0, 1); ``focus_param < 1`` is refused (the gradient
@@ -199,6 +202,199 @@ class MixCrossEntropyLoss(nn.Module):
 
     def extra_repr(self):
         return "label_smoothing=%g, ignore_index=%d" % (self.label_smoothing, self.ignore_index)
+
+
+class DistillTarget:
+    """The target of a distilled step: ``target`` -- an int64 class vector ``(N,)`` or a ``mixing.MixedTarget`` -- together with the
+    teacher's logits ``(N, C)`` fp32 for the same rows, all on one MI355X device.  ``Trainer(teacher=...)`` builds it from the
+    teacher's forward; build it by hand for cached teacher logits.  No gradient flows to the teacher logits."""
+
+    def __init__(self, target, teacher_logits: torch.Tensor):
+        from .mixing import MixedTarget
+        if isinstance(target, DistillTarget):
+            raise TypeError("DistillTarget.target must be a class vector or a MixedTarget, not another DistillTarget")
+        if not isinstance(target, MixedTarget):
+            if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or target.dim() != 1:
+                raise TypeError("DistillTarget.target must be a 1-D int64 class vector or a mixing.MixedTarget")
+        if not isinstance(teacher_logits, torch.Tensor) or teacher_logits.dtype != torch.float32 or teacher_logits.dim() != 2:
+            raise TypeError("DistillTarget.teacher_logits must be a 2-D fp32 tensor (N, C)")
+        if teacher_logits.shape[0] != target.shape[0]:
+            raise ValueError("the target has %d rows, the teacher logits %d" % (target.shape[0], teacher_logits.shape[0]))
+        if teacher_logits.device != target.device:
+            raise RuntimeError("target and teacher logits must be on one device, got %s and %s" % (target.device, teacher_logits.device))
+        self.target, self.teacher_logits = target, teacher_logits.detach().contiguous()
+
+    @property
+    def device(self):
+        return self.teacher_logits.device
+
+    @property
+    def shape(self):
+        return self.target.shape
+
+    def __len__(self):
+        return self.target.shape[0]
+
+    def to(self, device, non_blocking: bool = False) -> "DistillTarget":
+        return DistillTarget(self.target.to(device, non_blocking=non_blocking), self.teacher_logits.to(device, non_blocking=non_blocking))
+
+    def check_device(self, device):
+        """the kernels take raw device pointers: everything on ``device``, an MI355X"""
+        if self.device.type != "cuda":
+            raise RuntimeError("a DistillTarget must be on the MI355X (no CPU path)")
+        if self.device != torch.device(device):
+            raise RuntimeError("the DistillTarget is on %s, the logits on %s (the kernels take raw device pointers)" % (self.device, device))
+
+    def __repr__(self):
+        return "DistillTarget(N=%d, C=%d, device=%s)" % (len(self), self.teacher_logits.shape[1], self.device)
+
+
+def split_distill_target(target):
+    """a class vector, a mixing.MixedTarget or a DistillTarget around either -> (a, b or None, lam or None, teacher logits or None)"""
+    teacher = None
+    if isinstance(target, DistillTarget):
+        target, teacher = target.target, target.teacher_logits
+    return split_target(target) + (teacher,)
+
+
+def check_class_weight(weight):
+    """class weights: a 1-D tensor of finite values >= 0 (the kernel does not check them) -> fp32 contiguous, or None"""
+    if weight is None:
+        return None
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or weight.numel() < 1:
+        raise ValueError("weight must be a 1-D tensor with one entry per class, got %s"
+                         % (tuple(weight.shape) if isinstance(weight, torch.Tensor) else type(weight).__name__,))
+    weight = weight.detach().float().contiguous()
+    if not bool(torch.isfinite(weight).all()) or bool((weight < 0).any()):
+        raise ValueError("class weights must be finite and >= 0")
+    return weight
+
+
+def kd_cross_entropy(logits, a, b=None, lam=None, label_smoothing=0.0, weight=None, teacher=None, temperature=1.0, alpha=0.5,
+                     ignore_index=-100, rows=None, bad=None, parts=None, need_grad=True, meters=None):
+    """mnas_head_cross_entropy_kd on (N, C) fp32 contiguous device logits -> (loss 0-d tensor, dlogits or None).  ``a`` / ``b`` /
+    ``lam`` as for :func:`soft_cross_entropy`; ``weight``: fp32 (C,) class weights or None; ``teacher``: fp32 (N, C) teacher logits
+    or None (then the loss is the hard term alone).  ``rows``: the fp32 (2 N,) scratch (hard and distillation rows), ``bad``: the
+    int32 "target refused" flag, ``parts``: fp32 (2,) receiving (hard, kd) -- each allocated when not given."""
+    lib = L.load()
+    N, Cn = logits.shape
+    dev = logits.device
+    for name, t, dt, shape in (("target", a, torch.int64, (N,)), ("second target", b, torch.int64, (N,)), ("lam", lam, torch.float32, (N,)),
+                               ("weight", weight, torch.float32, (Cn,)), ("teacher logits", teacher, torch.float32, (N, Cn))):
+        if t is None:
+            continue
+        _on_device(name, t, dev)
+        if t.dtype != dt or tuple(t.shape) != shape:
+            raise ValueError("%s must be %s of shape %s, got %s %s" % (name, dt, shape, t.dtype, tuple(t.shape)))
+    eps, T, al = float(label_smoothing), float(temperature), float(alpha)
+    check_distill_settings(T, al, eps)
+    if rows is None:
+        rows = torch.empty(2 * N, dtype=torch.float32, device=dev)
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if parts is None:
+        parts = torch.empty(2, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dl = torch.empty_like(logits) if need_grad else None
+    ks, nk, ranks, blk = (None, 0, 0, 0) if meters is None else meters.kernel_args(N, dev)
+    cont = lambda t: None if t is None else t.contiguous()
+    a, b, lam, weight, teacher = (cont(t) for t in (a, b, lam, weight, teacher))
+    L.check(lib.mnas_head_cross_entropy_kd(logits.data_ptr(), a.data_ptr(), L.ptr(b), L.ptr(lam), eps, L.ptr(weight), L.ptr(teacher), T, al,
+                                           N, Cn, int(ignore_index), rows.data_ptr(), loss.data_ptr(), parts.data_ptr(), L.ptr(dl),
+                                           bad.data_ptr(), ks, nk, ranks, blk, L.cur_stream()), "head_cross_entropy_kd")
+    return loss, dl
+
+
+def check_distill_settings(temperature, alpha, label_smoothing):
+    if not float(temperature) > 0.0:
+        raise ValueError("temperature must be > 0, got %r" % (temperature,))
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError("alpha must lie in [0, 1], got %r" % (alpha,))
+    if not 0.0 <= float(label_smoothing) <= 1.0:
+        raise ValueError("label_smoothing must lie in [0, 1], got %r" % (label_smoothing,))
+
+
+class _KDFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, a, b, lam, label_smoothing, weight, teacher, temperature, alpha, ignore_index, bad, parts):
+        loss, dl = kd_cross_entropy(logits.detach().float().contiguous(), a, b, lam, label_smoothing, weight, teacher, temperature, alpha,
+                                    ignore_index, bad=bad, parts=parts, need_grad=ctx.needs_input_grad[0])
+        ctx.dl, ctx.dtype = dl, logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return ((ctx.dl * grad_output).to(ctx.dtype),) + (None,) * 11
+
+
+class DistillCrossEntropyLoss(nn.Module):
+    """Cross-entropy with class weights, label smoothing and a knowledge-distillation term (Hinton et al. 2015):
+    ``(1 - alpha) hard + alpha kd`` with ``hard = F.cross_entropy(logits, y, weight=weight, label_smoothing=label_smoothing)`` (over
+    class indices, or per row ``lam CE(a) + (1 - lam) CE(b)`` over a ``mixing.MixedTarget``, normalised by the labels' weights) and
+    ``kd = T^2 F.kl_div(log_softmax(logits / T), softmax(teacher / T), reduction='batchmean')`` (include/mnas.h "distillation
+    cross-entropy").  ``forward(logits, target)``: ``target`` a :class:`DistillTarget`; a bare class vector or ``MixedTarget`` means
+    no teacher, and the loss is the hard term alone.  ``alpha=0`` with a ``weight`` is class-weighted cross-entropy on its own.
+    ``weight``: a registered buffer (it moves with ``.to()`` / ``.cuda()``) or None.  ``last_parts``: a device tensor ``(hard, kd)``
+    of the last call, for logging without a host read (None after a call without weight and teacher, which is the soft-target loss
+    itself and has no parts).  Differentiable with respect to the logits only.  ``Trainer`` recognises this
+    class and runs the whole step without autograd (head.NativeHead.cross_entropy_kd).  No CPU path."""
+
+    def __init__(self, temperature: float = 1.0, alpha: float = 0.5, label_smoothing: float = 0.0, weight=None, ignore_index: int = -100):
+        super().__init__()
+        check_distill_settings(temperature, alpha, label_smoothing)
+        self.temperature, self.alpha, self.label_smoothing = float(temperature), float(alpha), float(label_smoothing)
+        self.ignore_index = int(ignore_index)
+        self.register_buffer("weight", check_class_weight(weight))
+        self._bad = {}                   # device -> int32 flag raised by a refused label or weight
+        self._parts = {}                 # device -> fp32 (2,): (hard, kd) of the last call
+        self.last_parts = None
+
+    def buffers_for(self, device):
+        """(refused-target flag, parts) on ``device``; ``last_parts`` then names that device's parts tensor"""
+        bad = self._bad.get(device)
+        if bad is None:
+            bad = self._bad[device] = torch.zeros(1, dtype=torch.int32, device=device)
+            self._parts[device] = torch.zeros(2, dtype=torch.float32, device=device)
+        self.last_parts = self._parts[device]
+        return bad, self.last_parts
+
+    def class_weight(self, logits):
+        """the weight buffer checked against the logits' class count and device, or None"""
+        w = self.weight
+        if w is None:
+            return None
+        if w.numel() != logits.shape[1]:
+            raise ValueError("weight has %d entries, the logits %d classes" % (w.numel(), logits.shape[1]))
+        _on_device("weight", w, logits.device)
+        return w
+
+    def forward(self, logits, target):
+        _on_device("logits", logits)
+        if logits.dim() != 2:
+            raise ValueError("logits must be (N, C), got %s" % (tuple(logits.shape),))
+        if isinstance(target, DistillTarget):
+            target.check_device(logits.device)
+        a, b, lam, teacher = split_distill_target(target)
+        _on_device("target", a, logits.device)
+        bad, parts = self.buffers_for(logits.device)
+        if teacher is None and self.weight is None:           # the soft-target loss itself, bit for bit a MixCrossEntropyLoss
+            self.last_parts = None
+            return _SoftCEFn.apply(logits, a, b, lam, self.label_smoothing, self.ignore_index, bad)
+        return _KDFn.apply(logits, a, b, lam, self.label_smoothing, self.class_weight(logits), teacher, self.temperature, self.alpha,
+                           self.ignore_index, bad, parts)
+
+    def check_targets(self):
+        """Host check of the device-side flag a label outside [0, C) or a weight outside [0, 1] raises (the loss is NaN from that
+        call on).  Synchronises; resets the flag."""
+        for bad in self._bad.values():
+            if int(bad.item()) != 0:
+                bad.zero_()
+                raise ValueError("DistillCrossEntropyLoss: a label was outside [0, num_classes) and not ignore_index, or a weight outside [0, 1]")
+
+    def extra_repr(self):
+        return "temperature=%g, alpha=%g, label_smoothing=%g, weight=%s, ignore_index=%d" % (
+            self.temperature, self.alpha, self.label_smoothing, "None" if self.weight is None else "(%d,)" % self.weight.numel(),
+            self.ignore_index)
 
 
 class HardDice(nn.Module):

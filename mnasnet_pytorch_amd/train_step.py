@@ -366,18 +366,23 @@ class Trainer:
 
     def __init__(self, model: nn.Module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  criterion: Optional[nn.Module] = None, distributed: bool = False, process_group=None,
-                 early_bucket_stage: int = 5, optimizer: str = "adam", meters=None, **optimizer_kwargs):
+                 early_bucket_stage: int = 5, optimizer: str = "adam", meters=None, teacher: Optional[nn.Module] = None,
+                 **optimizer_kwargs):
         self.model = model
+        self.teacher = teacher           # knowledge distillation: step() runs it in eval mode and wraps the target (_teach)
         self.meters = meters             # metrics.DeviceMeters / MultiLabelMeters or None: train.py:447,453-468 on the device
         self.native_step = True          # see _native_head()
         self.last_logits = None
         self.criterion = criterion if criterion is not None else nn.CrossEntropyLoss()   # train.py:277
         self._check_meters(meters)
+        self._check_teacher()
         self.lib = L.load()
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("Trainer needs the model on an MI355X device (no CPU path)")
         self.device = dev
+        if self._distill():
+            self.criterion.to(dev)       # its class-weight buffer: the kernel takes a raw device pointer
         feats = model.features if hasattr(model, "features") else model
         self.engine = feats._engine()
         eng_params = list(self.engine.params)
@@ -523,20 +528,71 @@ class Trainer:
         from .losses import MixCrossEntropyLoss
         return type(self.criterion) is MixCrossEntropyLoss
 
+    def _distill(self):
+        """the criterion is this package's DistillCrossEntropyLoss itself (class weights, smoothing, mixed batches, a teacher's
+        logits); a subclass keeps the module path, as for the other criteria"""
+        from .losses import DistillCrossEntropyLoss
+        return type(self.criterion) is DistillCrossEntropyLoss
+
     def _check_target(self, target):
-        """a mixing.MixedTarget goes to a MixCrossEntropyLoss (or a subclass of it) only: refused before anything is launched"""
-        from .losses import MixCrossEntropyLoss
+        """a mixing.MixedTarget goes to a MixCrossEntropyLoss or a DistillCrossEntropyLoss (or a subclass of either) only, a
+        losses.DistillTarget to a DistillCrossEntropyLoss (or a subclass) only: refused before anything is launched"""
+        from .losses import DistillCrossEntropyLoss, DistillTarget, MixCrossEntropyLoss
         from .mixing import MixedTarget
-        if isinstance(target, MixedTarget) and not isinstance(self.criterion, MixCrossEntropyLoss):
-            raise TypeError("a MixedTarget (two labels and a weight per row) needs criterion=MixCrossEntropyLoss(...); %s takes no "
-                            "mixed batch" % type(self.criterion).__name__)
+        if isinstance(target, DistillTarget):
+            if not isinstance(self.criterion, DistillCrossEntropyLoss):
+                raise TypeError("a DistillTarget (labels and a teacher's logits) needs criterion=DistillCrossEntropyLoss(...); %s takes "
+                                "no teacher logits" % type(self.criterion).__name__)
+            return
+        if isinstance(target, MixedTarget) and not isinstance(self.criterion, (MixCrossEntropyLoss, DistillCrossEntropyLoss)):
+            raise TypeError("a MixedTarget (two labels and a weight per row) needs criterion=MixCrossEntropyLoss(...) or "
+                            "DistillCrossEntropyLoss(...); %s takes no mixed batch" % type(self.criterion).__name__)
+
+    def _check_teacher(self):
+        """a teacher needs the criterion that takes its logits (the constructor and every step call it: both are plain attributes)"""
+        from .losses import DistillCrossEntropyLoss
+        if self.teacher is None:
+            return
+        if not isinstance(self.teacher, nn.Module):
+            raise TypeError("teacher must be an nn.Module, got %s" % type(self.teacher).__name__)
+        if not isinstance(self.criterion, DistillCrossEntropyLoss):
+            raise TypeError("Trainer(teacher=...) needs criterion=DistillCrossEntropyLoss(...); %s takes no teacher logits"
+                            % type(self.criterion).__name__)
+
+    def _teach(self, x, target):
+        """``teacher(x)`` in eval mode under ``torch.no_grad()`` -> a losses.DistillTarget around ``target``.  The teacher's
+        train/eval flags are restored on the way out, also when its forward raises; nothing of the teacher is written (eval mode:
+        its BatchNorm statistics stay, its engine runs the eval program).  A target that already is a DistillTarget (cached teacher
+        logits) is taken as it is and the teacher is not run."""
+        from .losses import DistillTarget
+        from .mixing import MixedTarget
+        if isinstance(target, DistillTarget):
+            return target
+        if not isinstance(target, (torch.Tensor, MixedTarget)) or target.device != x.device:
+            raise RuntimeError("target must be a tensor on the input's device (%s)" % (x.device,))
+        teacher = self.teacher
+        modes = [(mod, mod.training) for mod in teacher.modules()]
+        try:
+            teacher.eval()
+            with torch.no_grad():
+                out = teacher(x)
+        finally:
+            for mod, flag in modes:
+                mod.training = flag
+        if (not isinstance(out, torch.Tensor) or out.dim() != 2 or out.shape[0] != x.shape[0] or out.dtype != torch.float32
+                or out.device != x.device):
+            raise ValueError("the teacher must return (N, C) fp32 logits on the batch's device (%s), got %s"
+                             % (x.device, "%s %s on %s" % (out.dtype, tuple(out.shape), out.device) if isinstance(out, torch.Tensor)
+                                else type(out).__name__))
+        return DistillTarget(target, out)
 
     def _check_meters(self, meters):
         """the meters' kind against the criterion's, before anything is launched (the constructor, every forward_backward and
         validate call it: ``criterion`` and ``meters`` are plain attributes)"""
-        from .losses import MixCrossEntropyLoss, MultiClassBCELoss
+        from .losses import DistillCrossEntropyLoss, MixCrossEntropyLoss, MultiClassBCELoss
         from .metrics import MultiLabelMeters
-        if isinstance(meters, MultiLabelMeters) and isinstance(self.criterion, (nn.CrossEntropyLoss, MixCrossEntropyLoss)):
+        if isinstance(meters, MultiLabelMeters) and isinstance(self.criterion, (nn.CrossEntropyLoss, MixCrossEntropyLoss,
+                                                                               DistillCrossEntropyLoss)):
             raise ValueError("MultiLabelMeters count (N, C) multi-label targets; a cross-entropy criterion takes class indices "
                              "(use DeviceMeters)")
         if meters is not None and isinstance(self.criterion, MultiClassBCELoss) and not isinstance(meters, MultiLabelMeters):
@@ -545,7 +601,7 @@ class Trainer:
     def _native_head(self):
         """The model's NativeHead when the whole step can bypass autograd: FineTuneModelPool-like model in training mode
         (fused pool, Dropout/Linear/ReLU classifier) and a plain mean-reduced nn.CrossEntropyLoss (train.py:277), this package's
-        MultiClassBCELoss or its MixCrossEntropyLoss.  The features may
+        MultiClassBCELoss, its MixCrossEntropyLoss or its DistillCrossEntropyLoss.  The features may
         be entirely in eval mode under a training model (FineTuneModelPool.freeze_bn): forward_backward then runs the engine's
         frozen-statistics program; a subtree in mixed modes is refused by Engine._check_modes."""
         m = self.model
@@ -577,9 +633,9 @@ class Trainer:
         m, c = self.model, self.criterion
         if not self.native_step:
             return None
-        if self._multilabel() or self._mixce():
-            pass                   # losses.MultiClassBCELoss / MixCrossEntropyLoss: every setting is covered (head.NativeHead.bce,
-                                   # .cross_entropy_soft)
+        if self._multilabel() or self._mixce() or self._distill():
+            pass                   # losses.MultiClassBCELoss / MixCrossEntropyLoss / DistillCrossEntropyLoss: every setting is
+                                   # covered (head.NativeHead.bce, .cross_entropy_soft, .cross_entropy_kd)
         elif type(c) is not nn.CrossEntropyLoss:
             return None
         elif c.weight is not None or c.reduction != "mean" or getattr(c, "label_smoothing", 0.0) != 0.0:
@@ -605,8 +661,13 @@ class Trainer:
 
     def step(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """One iteration of train.py:427-440.  Returns the loss tensor (no host sync).  ``target``: what the criterion takes -- class
-        indices, an (N, C) label matrix (MultiClassBCELoss) or a mixing.MixedTarget (MixCrossEntropyLoss, on either path)."""
+        indices, an (N, C) label matrix (MultiClassBCELoss), a mixing.MixedTarget (MixCrossEntropyLoss, DistillCrossEntropyLoss) or a
+        losses.DistillTarget (DistillCrossEntropyLoss), on either path.  With ``teacher=`` given the teacher's eval forward runs
+        first and the target is wrapped into a DistillTarget (:meth:`_teach`)."""
         self._check_target(target)                           # before zero_grad: a refused target leaves the step untouched
+        if self.teacher is not None:
+            self._check_teacher()
+            target = self._teach(x, target)
         self.optimizer.zero_grad()                           # train.py:438
         if self.schedule is not None:
             eng = self.engine
@@ -621,6 +682,7 @@ class Trainer:
         """train.py:427-439 without the optimizer: forward, loss, backward INTO the flat gradient buffer (accumulating into what is
         already there: two calls between ``optimizer.zero_grad()`` and ``optimizer.step()`` sum their gradients, which is what
         the world-2 test uses to emulate two data-parallel ranks in one process).  Fires the engine's stage-done callback."""
+        from .losses import DistillTarget
         from .mixing import MixedTarget
         self._check_meters(self.meters)                      # before any launch, on either path
         self._check_target(target)
@@ -632,7 +694,7 @@ class Trainer:
             if hasattr(self.model, "_sync_input_norm"):
                 self.model._sync_input_norm()
             eng.check_input(x)                               # same checks as Engine.forward: the launch lists take raw pointers
-            if not isinstance(target, (torch.Tensor, MixedTarget)) or target.device != x.device:
+            if not isinstance(target, (torch.Tensor, MixedTarget, DistillTarget)) or target.device != x.device:
                 raise RuntimeError("target must be a tensor on the input's device (%s)" % (x.device,))
             u8 = x.dtype == torch.uint8 and eng._in_norm is not None
             x = x.contiguous() if u8 else x.float().contiguous()
@@ -649,7 +711,8 @@ class Trainer:
                 # input.size(1) for F1 (train.py:447, 454, 463)
                 self.last_logits, loss, df = head.loss_and_grad(f.view(f.size(0), -1), target, meters=self._ml_meters(),
                                                                 criterion=self.criterion, f1_n=x.shape[1])
-            else:                                            # (a MixCrossEntropyLoss: its smoothing and a MixedTarget's two labels)
+            else:                                            # (a MixCrossEntropyLoss: its smoothing and a MixedTarget's two labels; a
+                                                             # DistillCrossEntropyLoss: also its weights and a DistillTarget's logits)
                 self.last_logits, loss, df = head.loss_and_grad(f.view(f.size(0), -1), target, self.criterion.ignore_index,
                                                                 meters=self.meters, criterion=self.criterion)
             accumulate = eng.prepare_grads()
@@ -659,6 +722,8 @@ class Trainer:
             out = self.model(x.float())
             loss = self.criterion(out, target)
             loss.backward()
+            if isinstance(target, DistillTarget):
+                target = target.target                       # the meters count the labels
             if self._ml_meters() is not None:
                 if self._label_matrix(out, target):
                     self.meters.update(out.detach(), target, loss.detach(), f1_n=x.shape[1])
@@ -692,7 +757,8 @@ class Trainer:
         native head without dropout, and the cross-entropy kernels that also move ``meters`` (default: a fresh DeviceMeters with
         top-1 / top-5).  With this package's MultiClassBCELoss as the criterion it is the multi-label pass (train.py:575-587): (N, C)
         targets, the BCE kernels, and a MultiLabelMeters (loss, HardDice(0.5), macro-F1; the default is a fresh one).  With this package's
-        MixCrossEntropyLoss it is the single-label pass with the smoothed loss, on plain int64 targets.  Any input shape works: the engine keeps one eval program per shape.  A model or criterion the native head
+        MixCrossEntropyLoss it is the single-label pass with the smoothed loss, on plain int64 targets; with its DistillCrossEntropyLoss
+        the hard term alone (class weights and smoothing applied; there is no teacher in validation).  Any input shape works: the engine keeps one eval program per shape.  A model or criterion the native head
         does not cover runs as ``model(x)`` / ``criterion`` / ``meters.update``.  Distributed trainers broadcast rank 0's
         BatchNorm statistics first and sum the meters over the ranks at the end (``reduce=False``: neither).  The modules'
         train/eval flags are restored on the way out, also when a batch raises.  Returns ``meters.read()``.  The same pass under the
@@ -729,6 +795,8 @@ class Trainer:
                         elif self._mixce():                                # the smoothed loss on plain class indices
                             head.cross_entropy_soft(logits, target, self.criterion.label_smoothing, self.criterion.ignore_index,
                                                     need_grad=False, meters=meters)
+                        elif self._distill():                              # the hard term: weights and smoothing, no teacher
+                            head.cross_entropy_kd(logits, target, self.criterion, need_grad=False, meters=meters)
                         else:
                             head.cross_entropy(logits, target, self.criterion.ignore_index, need_grad=False, meters=meters)
                     else:
