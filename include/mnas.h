@@ -56,7 +56,7 @@ typedef struct MnasGradIn {
     const float* coef;    /* float[5][C] */
 } MnasGradIn;
 
-int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, and + mnas_grad_sqnorm / mnas_*_step_ex, and + mnas_head_cross_entropy_soft / mnas_img_mix, and + mnas_img_aug, and + mnas_head_cross_entropy_kd, all additive: no layout or opcode changed, so still 8; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
+int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, and + mnas_grad_sqnorm / mnas_*_step_ex, and + mnas_head_cross_entropy_soft / mnas_img_mix, and + mnas_img_aug, and + mnas_head_cross_entropy_kd, and + mnas_*_step_seg, all additive: no layout or opcode changed, so still 8; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
                                          * 5 = squeeze-excite on load: MnasConvGemm.gate, MnasPwBwd.seg_px -- and in round 5: 6 = the opt-in
                                          * forms that lost their A/B are gone (MnasPwBwd.dy_out / red4, MnasDwBwd.src_* / g_gate / g_bias,
                                          * mnas_dw_exp_*, mnas_irb_*, mnas_gram*, mnas_se_bn_assemble); their opcode numbers stay retired) */
@@ -777,6 +777,101 @@ int mnas_rmsprop_step_ex(float* p, const float* g, float* square_avg, float* mom
                          float eps, float weight_decay, float momentum, float grad_scale, const MnasOptExtra* extra, void* stream);
 int mnas_sgd_step_ex(float* p, const float* g, float* momentum_buf, int64_t n, float lr, float momentum, float dampening,
                      float weight_decay, int nesterov, int step, float grad_scale, const MnasOptExtra* extra, void* stream);
+
+/* ---- parameter groups, decoupled weight decay and layer-wise trust ratios (LAMB / LARS) on the flat buffers ----------
+ * Additive: three new symbols and four new structs; no existing entry point, struct layout, opcode or kernel changes, so the ABI
+ * version stays 8.
+ *
+ * The whole flat buffer is updated by ONE call, and the update itself is one launch, whatever the number of parameter tensors
+ * and groups.  Two DEVICE tables, built by the caller and uploaded only when they change, tell the kernels which tensor an
+ * element belongs to:
+ *   segment = one trainable parameter tensor: elements [begin, begin + n) of the flat buffers, its group, and its tiles
+ *             [tile0, tile0 + ntiles) of the tile table.  A frozen tensor has no segment: nothing of it is read or written.
+ *   tile    = at most MNAS_OPT_TILE consecutive elements of ONE segment: [begin, begin + n), its segment.  The tiles of a segment
+ *             are consecutive in the table and in increasing element order, and the tiles cover every segment exactly once.
+ * Segments (and so tiles) start at any element: 4-byte alignment only, as for mnas_grad_sqnorm.  The tables are NOT checked on the
+ * device: a tile outside the buffers is an out-of-bounds access, a group index >= ngroups reads an unset group.
+ * The groups are a HOST array read at every call: lr, weight_decay and the two flags travel to the kernels by value (as lr reaches
+ * mnas_adam_step), so a scheduler costs no upload.  The other hyper-parameters (betas, eps, alpha, momentum, ...) are per call.
+ *
+ * Per element, all in fp32, fmaf exactly where the plain kernels use it;  gs = g[i] * grad_scale,  with an extra that clips:
+ * gs = (g[i] * grad_scale) * coef  (MnasOptExtra above; extra NULL or not clipping: no further multiply / coef == 1):
+ *   coupled decay (decoupled == 0, trust_kind == 0): bit for bit the update mnas_<kind>_step / _step_ex applies to that element
+ *       with the group's lr and weight_decay;
+ *   decoupled decay (decoupled != 0): p' = p * f with f = (float)(1.0 - (double)lr * (double)weight_decay) formed on the host
+ *       (torch's param.mul_(1 - lr * weight_decay)), then the optimizer's update of p' from gs with weight_decay = 0: for Adam
+ *       torch.optim.AdamW; the same for RMSprop and SGD;
+ *   LAMB (trust_kind == MNAS_TRUST_LAMB, Adam only):  m = fmaf(b1, m, (1 - b1) * gs), v = fmaf(b2, v, (1 - b2) * gs * gs),
+ *       u = (m / bc1) / (sqrtf(v) / bc2_sqrt + eps), and with weight_decay != 0  u = fmaf(weight_decay, p, u);
+ *       p = p - (lr * r) * u.   Over the element's segment  w = (float)sqrt(sum (double)p^2),  un = (float)sqrt(sum (double)u^2),
+ *       r = (w > 0 && un > 0) ? w / un : 1;
+ *   LARS (trust_kind == MNAS_TRUST_LARS, SGD only):  gn = (float)sqrt(sum (double)gs^2),  w as above,
+ *       r = (w > 0 && gn > 0) ? (trust_coef * w) / (fmaf(weight_decay, w, gn) + trust_eps) : 1;
+ *       gi = (weight_decay != 0 ? fmaf(weight_decay, p, gs) : gs) * r, then momentum / dampening / nesterov and p = p - lr * gi
+ *       as in mnas_sgd_step;
+ *   a group with trust == 0 in a trust-ratio step: r = 1 (exactly; no norm is taken of its segments), and, if it is decoupled,
+ *       p' = p * f first and weight_decay = 0 in u / gi.
+ * Norms (trust_kind != 0 only): no atomics.  A read-only pass ahead of the update recomputes m, v in registers and leaves, per
+ * tile, two fp64 partial sums in tile_partial[2 t], [2 t + 1]: every lane adds the squares of its elements t.begin + lane + 256 j in
+ * increasing j in fp64 (the fp32 value widened first), then the wave-64 butterfly and the four waves in wave order, as in
+ * mnas_grad_sqnorm.  A small finalize launch (one lane per segment) adds each segment's tile partials in tile order and writes
+ * ratio[segment] once; the update launch reads it.  All of it is a function of the tables and the data only, not of the grid: the
+ * same input gives the same bits on every run and on every rank.
+ * extra (may be NULL) means what it means for mnas_*_step_ex, with ema pointing at the BASE of the shadow buffer and update_stats
+ * honoured by the update launch alone.  With skip_nonfinite and a non-finite global norm, none of the launches writes anything but
+ * the stats block: p, the moments, the EMA, tile_partial and ratio stay as they were.
+ * Launches of one call: [norm pass, ratio finalize,] update; 256-thread workgroups grid-stride over the tiles, at most 2048 of
+ * them.  Nothing is allocated, uploaded, read back or synchronised: the call can be captured.
+ * MNAS_EINVAL, before anything is launched: a NULL segs / tiles / groups / p / g (or moment buffer the optimizer needs), nsegs
+ * outside [0, MNAS_OPT_MAX_SEGS], ngroups outside [1, MNAS_OPT_MAX_GROUPS], ntiles < 0 (or < nsegs), trust_kind outside 0..2, LAMB
+ * on anything but Adam, LARS on anything but SGD, any trust_kind != 0 on RMSprop, trust_kind != 0 without tile_partial / ratio, a
+ * group with decoupled and trust both set, trust_eps < 0, a NaN lr / weight_decay / trust_coef / trust_eps / grad_scale, step < 1
+ * (Adam, SGD), and whatever mnas_*_step_ex refuses of a non-NULL extra.  nsegs == 0 is valid and launches nothing. */
+#define MNAS_OPT_TILE 4096
+#define MNAS_OPT_MAX_GROUPS 32
+#define MNAS_OPT_MAX_SEGS 4096
+#define MNAS_TRUST_NONE 0
+#define MNAS_TRUST_LAMB 1
+#define MNAS_TRUST_LARS 2
+typedef struct MnasOptSeg {          /* DEVICE table entry, 32 bytes */
+    int64_t begin;                   /* first element inside the flat buffers */
+    int64_t n;                       /* elements, >= 1 */
+    int32_t group;                   /* 0 .. ngroups - 1 */
+    int32_t tile0;                   /* the segment's first tile */
+    int32_t ntiles;                  /* ceil(n / MNAS_OPT_TILE) */
+    int32_t reserved;                /* 0 */
+} MnasOptSeg;
+typedef struct MnasOptTile {         /* DEVICE table entry, 16 bytes */
+    int64_t begin;                   /* first element inside the flat buffers */
+    int32_t n;                       /* 1 .. MNAS_OPT_TILE */
+    int32_t seg;                     /* the segment the tile belongs to */
+} MnasOptTile;
+typedef struct MnasOptGroup {        /* HOST array entry, 16 bytes */
+    float   lr;
+    float   weight_decay;
+    int32_t decoupled;               /* != 0: decoupled decay (not together with trust) */
+    int32_t trust;                   /* != 0: the group's segments take the step's trust ratio */
+} MnasOptGroup;
+typedef struct MnasOptSegs {         /* HOST struct */
+    const MnasOptSeg*   segs;        /* DEVICE, nsegs entries */
+    const MnasOptTile*  tiles;       /* DEVICE, ntiles entries */
+    const MnasOptGroup* groups;      /* HOST, ngroups entries */
+    int32_t             nsegs;
+    int32_t             ntiles;
+    int32_t             ngroups;
+    int32_t             trust_kind;  /* MNAS_TRUST_* */
+    double*             tile_partial;/* DEVICE workspace, 2 * ntiles doubles; may be NULL when trust_kind == 0 */
+    float*              ratio;       /* DEVICE, nsegs floats: the step's trust ratios; may be NULL when trust_kind == 0 */
+    float               trust_coef;  /* LARS */
+    float               trust_eps;   /* LARS, >= 0 */
+} MnasOptSegs;
+/* The plain entry points' arguments with p / g / the moments as the BASE of the flat buffers and without n, lr, weight_decay. */
+int mnas_adam_step_seg(float* p, const float* g, float* m, float* v, float beta1, float beta2, float eps, int step,
+                       float grad_scale, const MnasOptSegs* segs, const MnasOptExtra* extra, void* stream);
+int mnas_rmsprop_step_seg(float* p, const float* g, float* square_avg, float* momentum_buf, float alpha, float eps, float momentum,
+                          float grad_scale, const MnasOptSegs* segs, const MnasOptExtra* extra, void* stream);
+int mnas_sgd_step_seg(float* p, const float* g, float* momentum_buf, float momentum, float dampening, int nesterov, int step,
+                      float grad_scale, const MnasOptSegs* segs, const MnasOptExtra* extra, void* stream);
 
 /* ---- batched launch: run a pre-built list of the calls above with ONE host->library transition ------- */
 #define MNAS_OP_CONV_GEMM 1

@@ -321,6 +321,33 @@ class MnasOptExtra(C.Structure):
                 ("ema", c_void_p), ("ema_decay", c_float), ("stats", c_void_p), ("update_stats", C.c_int32)]
 
 
+OPT_TILE, OPT_MAX_GROUPS, OPT_MAX_SEGS = 4096, 32, 4096          # MNAS_OPT_TILE, MNAS_OPT_MAX_GROUPS, MNAS_OPT_MAX_SEGS
+TRUST_NONE, TRUST_LAMB, TRUST_LARS = 0, 1, 2                    # MNAS_TRUST_*
+
+
+class MnasOptSeg(C.Structure):
+    """include/mnas.h: DEVICE table entry of the *_step_seg calls, one trainable parameter tensor (32 bytes)"""
+    _fields_ = [("begin", c_int64), ("n", c_int64), ("group", C.c_int32), ("tile0", C.c_int32), ("ntiles", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class MnasOptTile(C.Structure):
+    """include/mnas.h: DEVICE table entry, at most OPT_TILE consecutive elements of one segment (16 bytes)"""
+    _fields_ = [("begin", c_int64), ("n", C.c_int32), ("seg", C.c_int32)]
+
+
+class MnasOptGroup(C.Structure):
+    """include/mnas.h: HOST array entry, one parameter group's scalars as they are at this step"""
+    _fields_ = [("lr", c_float), ("weight_decay", c_float), ("decoupled", C.c_int32), ("trust", C.c_int32)]
+
+
+class MnasOptSegs(C.Structure):
+    """include/mnas.h: HOST struct of a *_step_seg call: the tables, the groups, the trust-ratio workspaces and scalars"""
+    _fields_ = [("segs", c_void_p), ("tiles", c_void_p), ("groups", C.POINTER(MnasOptGroup)), ("nsegs", C.c_int32),
+                ("ntiles", C.c_int32), ("ngroups", C.c_int32), ("trust_kind", C.c_int32), ("tile_partial", c_void_p),
+                ("ratio", c_void_p), ("trust_coef", c_float), ("trust_eps", c_float)]
+
+
 SYMBOLS = {
     "mnas_conv_img_parts": (c_int, [c_int] * 11),
     "mnas_stem_parts": (c_int, [c_int, c_int, c_int, c_int, c_int]),
@@ -419,6 +446,12 @@ SYMBOLS = {
                                      c_float, C.POINTER(MnasOptExtra), c_void_p]),
     "mnas_sgd_step_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int, c_int, c_float,
                                  C.POINTER(MnasOptExtra), c_void_p]),
+    "mnas_adam_step_seg": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_int, c_float,
+                                   C.POINTER(MnasOptSegs), C.POINTER(MnasOptExtra), c_void_p]),
+    "mnas_rmsprop_step_seg": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
+                                      C.POINTER(MnasOptSegs), C.POINTER(MnasOptExtra), c_void_p]),
+    "mnas_sgd_step_seg": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_float,
+                                  C.POINTER(MnasOptSegs), C.POINTER(MnasOptExtra), c_void_p]),
     "mnas_run_ops": (c_int, [C.POINTER(MnasOp), c_int, c_void_p, C.POINTER(c_int)]),
     "mnas_run_ops_multi": (c_int, [C.POINTER(MnasOp), c_int, C.POINTER(c_void_p), c_int, C.POINTER(c_int)]),
     "mnas_event_create": (c_int, [C.POINTER(c_void_p)]),

@@ -113,6 +113,29 @@ class GradStats(NamedTuple):
     skipped_steps: int
 
 
+class OptTables(NamedTuple):
+    """build_opt_tables(): the two tables of the ``mnas_*_step_seg`` calls (include/mnas.h) as host tuples"""
+    segs: list        # (begin, n, group, tile0, ntiles, parameter index), one per trainable non-empty parameter tensor
+    tiles: list       # (begin, n, segment index): at most `tile` consecutive elements of one segment
+
+
+def build_opt_tables(ranges, requires_grad, group_index, tile=L.OPT_TILE) -> OptTables:
+    """Pure host logic (tests/test_param_groups_cpu.py drives it without a device).  ``ranges``: the [begin, end) element range of
+    every parameter tensor inside the flat buffers, in address order; ``requires_grad`` and ``group_index`` per tensor.  A frozen (or
+    empty) tensor gets no segment, so nothing of it is read or written; a segment's tiles are consecutive, in element order, and
+    never cross into the next tensor."""
+    segs, tiles = [], []
+    for i, ((a, b), rg, gi) in enumerate(zip(ranges, requires_grad, group_index)):
+        if not rg or a == b:
+            continue
+        n, t0 = b - a, len(tiles)
+        nt = -(-n // tile)
+        for k in range(nt):
+            tiles.append((a + k * tile, min(tile, n - k * tile), len(segs)))
+        segs.append((a, n, int(gi), t0, nt, i))
+    return OptTables(segs, tiles)
+
+
 class FlatAdam(torch.optim.Optimizer):
     """``torch.optim.Adam`` (train.py:219-221) over ONE flat fp32 buffer: a single fused launch (``mnas_adam_step``) instead
     of ~110 per-tensor updates.  It is a real ``torch.optim.Optimizer``:
@@ -142,26 +165,66 @@ class FlatAdam(torch.optim.Optimizer):
     (rolling it back would take the host read this path exists to avoid).  After a skip, Adam's bias correction and the native
     head's dropout seeds are therefore one step ahead of a torch run that skipped the same step, and SGD with ``dampening != 0``
     differs from it when step 1 is the skipped one (torch would seed the momentum buffer with the next gradient, undamped).
+
+    Parameter groups, decoupled decay, trust ratios (include/mnas.h: ``mnas_*_step_seg``).  ``params`` may be
+    a torch-style list of group dicts ``{"params": [...], "lr": ..., "weight_decay": ..., "decoupled": bool, "trust": bool}`` (what
+    a group leaves out comes from the constructor); the union of the groups' parameters, ordered by address, must tile ``flat_p``
+    exactly.  ``param_groups`` stays a real torch list read at every step, so a scheduler scales every group.  Per group: ``lr``,
+    ``weight_decay``, ``decoupled`` (``p *= 1 - lr * weight_decay`` ahead of an update that sees the undecayed gradient: for Adam
+    ``torch.optim.AdamW``; the constructor's ``decoupled_weight_decay`` is the default) and ``trust``.  The other hyper-parameters
+    (betas, eps, alpha, momentum, ...) are per optimizer and read from ``param_groups[0]``.  ``trust_ratio="lamb"`` (FlatAdam) /
+    ``"lars"`` (FlatSGD) scales every tensor's update by a layer-wise ratio of deterministic fp64 norms; a group with
+    ``trust=False`` (BatchNorm parameters, biases) keeps ratio 1, and a group cannot be decoupled and take a trust ratio (LAMB and
+    LARS carry the decay inside the ratio'd update).  :meth:`trust_ratios` reads the last step's ratios.
+
+    Routing: ONE group with none of these options takes exactly the launches described above (same launches, same bits).
+    Anything else is one ``mnas_*_step_seg`` call per step that updates the whole buffer in one launch -- two short launches more
+    for the norms of a trust-ratio step -- from device tables (one segment per trainable tensor) that are rebuilt only when the
+    ``requires_grad`` pattern or the groups' membership changes.  The global gradient norm is ``mnas_grad_sqnorm`` per trainable
+    run, unchanged.
     """
+    _trust_name = "lamb"                  # the trust ratio this optimizer supports (FlatRMSprop: none, FlatSGD: "lars")
 
     def __init__(self, params, flat_p, flat_g, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0,
-                 clip_grad_norm=None, skip_nonfinite=False, ema_decay=None):
+                 clip_grad_norm=None, skip_nonfinite=False, ema_decay=None, decoupled_weight_decay=False, trust_ratio=None,
+                 trust_coef=1e-3, trust_eps=1e-8):
         params = list(params)
-        n = sum(p.numel() for p in params)
+        grouped = bool(params) and isinstance(params[0], dict)
+        if grouped:
+            if len(params) > L.OPT_MAX_GROUPS:
+                raise ValueError("at most %d parameter groups (MNAS_OPT_MAX_GROUPS), got %d" % (L.OPT_MAX_GROUPS, len(params)))
+            groups = [dict(g, params=list(g["params"])) for g in params]
+            every = [p for g in groups for p in g["params"]]
+            if len({id(p) for p in every}) != len(every):
+                raise ValueError("a parameter appears in more than one parameter group")
+            every.sort(key=lambda p: p.data_ptr())
+        else:
+            groups, every = None, params
+        n = sum(p.numel() for p in every)
         if flat_p.numel() != n or flat_g.numel() != n:
             raise ValueError("flat buffers must hold exactly the parameters handed to FlatAdam")
         off = 0
         self._ranges = []                 # element range of every parameter inside the flat buffers
-        for p in params:
+        for p in every:
             if p.data_ptr() != flat_p.data_ptr() + 4 * off:
-                raise ValueError("parameters must be views of flat_p in order")
+                raise ValueError("parameters must be views of flat_p in order" if not grouped else
+                                 "the groups' parameters, ordered by address, must tile flat_p exactly")
             self._ranges.append((off, off + p.numel()))
             off += p.numel()
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self._all_params = every          # every parameter, in ADDRESS order: what _ranges is indexed by (a group dict may list
+                                          # its parameters in any order, so param_groups[k]['params'] is not)
+        self.trust_ratio, self.trust_coef, self.trust_eps = trust_ratio, trust_coef, trust_eps
+        self._check_trust()
+        super().__init__(groups if grouped else params,
+                         dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled=bool(decoupled_weight_decay),
+                              trust=trust_ratio is not None))
+        self._check_groups()
+        self._seg_key, self._seg = None, None     # the device tables of the _seg path and what they were built for
         self.flat_p, self.flat_g = flat_p, flat_g
         self.flat_m = torch.zeros_like(flat_p)
         self.flat_v = torch.zeros_like(flat_p)
         self.step_count = 0
+        self.seg_calls = 0                # mnas_*_step_seg calls issued so far (0 for ever on the one-group path)
         self.grad_scale = grad_scale      # 1/world_size: the all-reduce sums, Adam sees the mean (DataParallel semantics)
         self._lib = L.load()
         self._runs_key, self._runs = None, []
@@ -207,11 +270,123 @@ class FlatAdam(torch.optim.Optimizer):
         ctypes.memmove(ctypes.byref(raw), host.data_ptr(), ctypes.sizeof(raw))
         return GradStats(float(raw.last_norm), float(raw.last_coef), int(raw.steps), int(raw.clipped_steps), int(raw.skipped_steps))
 
-    def _step_extras(self, g, runs):
-        """the step with clipping, the skip or the EMA on: norm launches into consecutive slots of one table, then the _ex launches"""
+    # ---- parameter groups / decoupled decay / trust ratios ------------------------------------------------------------------
+    def _check_trust(self):
+        """the trust-ratio attributes, before anything is launched"""
+        t = self.trust_ratio
+        if t not in (None, "lamb", "lars"):
+            raise ValueError("trust_ratio must be None, 'lamb' or 'lars', got %r" % (t,))
+        if t is not None and t != self._trust_name:
+            raise ValueError("trust_ratio=%r is not available on %s (LAMB is Adam's, LARS is SGD's, RMSprop has none)"
+                             % (t, type(self).__name__))
+        if t is not None:
+            c, e = float(self.trust_coef), float(self.trust_eps)
+            if c != c or e != e or e < 0.0:
+                raise ValueError("trust_coef must be a number and trust_eps >= 0, got %r, %r" % (self.trust_coef, self.trust_eps))
+
+    def _check_groups(self):
+        """every group's flags and scalars (the constructor and every grouped step call it: the groups are plain dicts)"""
+        if len(self.param_groups) > L.OPT_MAX_GROUPS:
+            raise ValueError("at most %d parameter groups (MNAS_OPT_MAX_GROUPS), got %d" % (L.OPT_MAX_GROUPS, len(self.param_groups)))
+        for k, g in enumerate(self.param_groups):
+            if self.trust_ratio is not None and g["decoupled"] and g["trust"]:
+                raise ValueError("parameter group %d: decoupled weight decay and a trust ratio exclude each other (LAMB / LARS carry "
+                                 "the decay inside the ratio'd update)" % k)
+            if float(g["lr"]) != float(g["lr"]) or float(g["weight_decay"]) != float(g["weight_decay"]):
+                raise ValueError("parameter group %d: lr / weight_decay is NaN" % k)
+
+    def _grouped(self):
+        """False: one group with none of the new options -- today's launches"""
+        return len(self.param_groups) > 1 or self.trust_ratio is not None or bool(self.param_groups[0]["decoupled"])
+
+    def _seg_tables(self):
+        """the device tables of the _seg call, rebuilt when the requires_grad pattern or the groups' membership changes"""
+        member = {}
+        for k, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                if id(p) in member:
+                    raise ValueError("a parameter appears in more than one parameter group")
+                member[id(p)] = k
+        try:
+            gidx = tuple(member[id(p)] for p in self._all_params)
+        except KeyError:
+            raise ValueError("the parameter groups no longer hold every parameter of the flat buffer") from None
+        if len(member) != len(self._all_params):
+            raise ValueError("the parameter groups hold a parameter that is not in the flat buffer")
+        key = (tuple(p.requires_grad for p in self._all_params), gidx, self.trust_ratio is not None)
+        if key != self._seg_key:
+            tb = build_opt_tables(self._ranges, key[0], gidx)
+            if len(tb.segs) > L.OPT_MAX_SEGS:
+                raise ValueError("%d trainable parameter tensors: more than MNAS_OPT_MAX_SEGS = %d" % (len(tb.segs), L.OPT_MAX_SEGS))
+            dev = self.flat_p.device
+
+            def upload(cls, rows):
+                arr = (cls * max(1, len(rows)))(*[cls(*r) for r in rows])
+                return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+
+            seg = {"tables": tb, "segs": upload(L.MnasOptSeg, [s[:5] + (0,) for s in tb.segs]), "tiles": upload(L.MnasOptTile, tb.tiles),
+                   "partial": None, "ratio": None, "groups": (L.MnasOptGroup * L.OPT_MAX_GROUPS)()}
+            if self.trust_ratio is not None:
+                seg["partial"] = torch.zeros(2 * max(1, len(tb.tiles)), dtype=torch.float64, device=dev)
+                seg["ratio"] = torch.ones(max(1, len(tb.segs)), dtype=torch.float32, device=dev)
+            self._seg_key, self._seg = key, seg
+        return self._seg
+
+    @property
+    def last_trust_ratios(self):
+        """device tensor: the last trust-ratio step's ratio of every segment (trainable tensor, address order, as that step's
+        tables had them); None without ``trust_ratio`` or before the first such step.  A plain read: no sync, and the tables are
+        not rebuilt here, so a ``requires_grad`` or membership change shows from the next step on."""
+        seg = self._seg
+        if self.trust_ratio is None or seg is None or seg["ratio"] is None or not self.seg_calls:
+            return None
+        return seg["ratio"][:len(seg["tables"].segs)]
+
+    def trust_ratios(self):
+        """{parameter index (address order, as in the flat buffer): ratio of the last step} from ONE host read; frozen tensors
+        are absent, a ``trust=False`` group's tensors read 1.0.  {} without ``trust_ratio`` or before the first step.  The
+        indices and the frozen set are the LAST STEP's (see :attr:`last_trust_ratios`)."""
+        dev = self.last_trust_ratios
+        if dev is None:
+            return {}
+        return {s[5]: r for s, r in zip(self._seg["tables"].segs, dev.cpu().tolist())}
+
+    def _step_seg(self, runs):
+        """one mnas_*_step_seg call: every group, the whole buffer"""
         self._check_extras()
-        if self.ema_decay is not None and self.flat_ema is None:
-            self.reset_ema()
+        self._check_trust()
+        self._check_groups()
+        seg = self._seg_tables()
+        tb = seg["tables"]
+        if not tb.segs:
+            return
+        ex = None
+        if self.clip_grad_norm is not None or self.skip_nonfinite or self.ema_decay is not None:
+            if self.ema_decay is not None and self.flat_ema is None:
+                self.reset_ema()
+            ex = self._extra(self._norm_launches(runs))
+            ex.ema = self.flat_ema.data_ptr() if self.ema_decay is not None else None
+            ex.update_stats = 1
+        trust = self.trust_ratio is not None
+        for k, g in enumerate(self.param_groups):
+            seg["groups"][k] = L.MnasOptGroup(float(g["lr"]), float(g["weight_decay"]), 1 if g["decoupled"] else 0,
+                                              1 if trust and g["trust"] else 0)
+        segs = L.MnasOptSegs(segs=seg["segs"].data_ptr(), tiles=seg["tiles"].data_ptr(), groups=seg["groups"], nsegs=len(tb.segs),
+                             ntiles=len(tb.tiles), ngroups=len(self.param_groups),
+                             trust_kind={None: L.TRUST_NONE, "lamb": L.TRUST_LAMB, "lars": L.TRUST_LARS}[self.trust_ratio],
+                             tile_partial=L.ptr(seg["partial"]), ratio=L.ptr(seg["ratio"]),
+                             trust_coef=float(self.trust_coef), trust_eps=float(self.trust_eps))
+        self.seg_calls += 1
+        self._launch_seg(self.param_groups[0], segs, ex)
+
+    def _launch_seg(self, g, segs, ex):
+        L.check(self._lib.mnas_adam_step_seg(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.flat_m.data_ptr(),
+                                             self.flat_v.data_ptr(), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                                             self.step_count, float(self.grad_scale), ctypes.byref(segs),
+                                             ctypes.byref(ex) if ex is not None else None, L.cur_stream()), "adam_step_seg")
+
+    def _norm_launches(self, runs):
+        """mnas_grad_sqnorm per trainable run into consecutive slots of one table (clipping or the skip on) -> used slots"""
         stream = L.cur_stream()
         nparts = 0
         if self.clip_grad_norm is not None or self.skip_nonfinite:
@@ -222,20 +397,29 @@ class FlatAdam(torch.optim.Optimizer):
                 L.check(self._lib.mnas_grad_sqnorm(self.flat_g.data_ptr() + 4 * a, b - a, float(self.grad_scale),
                                                    self._partial.data_ptr(), nparts, ctypes.byref(got), stream), "grad_sqnorm")
                 nparts += got.value
+        return nparts
+
+    def _extra(self, nparts):
         clip = self.clip_grad_norm
-        ex = L.MnasOptExtra(partial=L.ptr(self._partial) if nparts else None, nparts=nparts,
-                            max_norm=float(clip) if clip is not None and math.isfinite(float(clip)) else 0.0,
-                            skip_nonfinite=1 if self.skip_nonfinite else 0, ema=None,
-                            ema_decay=float(self.ema_decay) if self.ema_decay is not None else 0.0,
-                            stats=self._stats_block().data_ptr(), update_stats=0)
+        return L.MnasOptExtra(partial=L.ptr(self._partial) if nparts else None, nparts=nparts,
+                              max_norm=float(clip) if clip is not None and math.isfinite(float(clip)) else 0.0,
+                              skip_nonfinite=1 if self.skip_nonfinite else 0, ema=None,
+                              ema_decay=float(self.ema_decay) if self.ema_decay is not None else 0.0,
+                              stats=self._stats_block().data_ptr(), update_stats=0)
+
+    def _step_extras(self, g, runs):
+        """the step with clipping, the skip or the EMA on: norm launches into consecutive slots of one table, then the _ex launches"""
+        self._check_extras()
+        if self.ema_decay is not None and self.flat_ema is None:
+            self.reset_ema()
+        ex = self._extra(self._norm_launches(runs))
         for k, (a, b) in enumerate(runs):
             ex.ema = self.flat_ema.data_ptr() + 4 * a if self.ema_decay is not None else None
             ex.update_stats = 1 if k == 0 else 0
             self._launch(a, b, g, ex)
 
     def _trainable_runs(self):
-        ps = self.param_groups[0]["params"]
-        key = tuple(p.requires_grad for p in ps)
+        key = tuple(p.requires_grad for p in self._all_params)      # address order, like _ranges
         if key != self._runs_key:
             runs = []
             for (a, b), rg in zip(self._ranges, key):
@@ -261,6 +445,9 @@ class FlatAdam(torch.optim.Optimizer):
         g = self.param_groups[0]
         self.step_count += 1
         runs = self._trainable_runs()
+        if self._grouped():
+            self._step_seg(runs)
+            return loss
         if self.clip_grad_norm is not None or self.skip_nonfinite or self.ema_decay is not None:
             self._step_extras(g, runs)
             return loss
@@ -280,14 +467,16 @@ class FlatAdam(torch.optim.Optimizer):
             L.check(self._lib.mnas_adam_step_ex(*args, ctypes.byref(ex), L.cur_stream()), "adam_step_ex")
 
     def state_dict(self):
-        g = self.param_groups[0]
         state = {"step": self.step_count, "exp_avg": self.flat_m.clone(), "exp_avg_sq": self.flat_v.clone()}
         if self.ema_decay is not None:
             if self.flat_ema is None:
                 self.reset_ema()
             state["ema"] = self.flat_ema.clone()
-        return {"state": state,
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} | {"params": list(range(len(g["params"])))}]}
+        groups, k = [], 0                 # torch's layout: every group, its parameters numbered consecutively in group order
+        for g in self.param_groups:
+            groups.append({key: v for key, v in g.items() if key != "params"} | {"params": list(range(k, k + len(g["params"])))})
+            k += len(g["params"])
+        return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
         st = sd["state"]
@@ -304,22 +493,33 @@ class FlatAdam(torch.optim.Optimizer):
             self.flat_ema.copy_(st["ema"].to(self.flat_ema.device))
         elif self.ema_decay is not None:
             self.reset_ema()              # a checkpoint written with the EMA off: the shadow restarts from the current parameters
-        for k, v in sd["param_groups"][0].items():
-            if k != "params":
-                self.param_groups[0][k] = v
+        if len(sd["param_groups"]) != len(self.param_groups):
+            raise ValueError("loaded state dict has %d parameter groups, this optimizer %d" % (len(sd["param_groups"]), len(self.param_groups)))
+        for g, saved in zip(self.param_groups, sd["param_groups"]):
+            if len(saved["params"]) != len(g["params"]):
+                raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
+            for k, v in saved.items():      # (a checkpoint from before the groups has no 'decoupled' / 'trust': they stay as constructed)
+                if k != "params":
+                    g[k] = v
 
 
 class FlatRMSprop(FlatAdam):
     """``torch.optim.RMSprop`` (train.py:222-224: ``--optimizer rmsprop``; alpha 0.99, eps 1e-8, centered = False) over the flat
-    buffers: one fused launch (``mnas_rmsprop_step``).  Same Optimizer contract as :class:`FlatAdam`."""
+    buffers: one fused launch (``mnas_rmsprop_step``).  Same Optimizer contract as :class:`FlatAdam`, parameter groups and
+    decoupled decay included; no trust ratio."""
+    _trust_name = None
 
     def __init__(self, params, flat_p, flat_g, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, centered=False,
                  grad_scale=1.0, **extras):
         if centered:
             raise NotImplementedError("centered RMSprop is not fused (the reference never asks for it: train.py:222-224)")
         super().__init__(params, flat_p, flat_g, lr=lr, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale, **extras)
-        self.param_groups[0].pop("betas", None)
-        self.param_groups[0].update(alpha=alpha, momentum=momentum, centered=False)
+        self.defaults.pop("betas", None)
+        self.defaults.update(alpha=alpha, momentum=momentum, centered=False)
+        for g in self.param_groups:
+            g.pop("betas", None)
+            for k in ("alpha", "momentum", "centered"):
+                g.setdefault(k, self.defaults[k])
         # flat_m = momentum buffer, flat_v = square average (same checkpoint layout as FlatAdam: exp_avg / exp_avg_sq)
 
     def _launch(self, a, b, g, ex=None):
@@ -331,10 +531,18 @@ class FlatRMSprop(FlatAdam):
         else:
             L.check(self._lib.mnas_rmsprop_step_ex(*args, ctypes.byref(ex), L.cur_stream()), "rmsprop_step_ex")
 
+    def _launch_seg(self, g, segs, ex):
+        L.check(self._lib.mnas_rmsprop_step_seg(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.flat_v.data_ptr(),
+                                                self.flat_m.data_ptr(), float(g["alpha"]), float(g["eps"]), float(g["momentum"]),
+                                                float(self.grad_scale), ctypes.byref(segs),
+                                                ctypes.byref(ex) if ex is not None else None, L.cur_stream()), "rmsprop_step_seg")
+
 
 class FlatSGD(FlatAdam):
     """``torch.optim.SGD`` (train.py:226-228: ``--optimizer sgd``; momentum 0 by default) over the flat buffers
-    (``mnas_sgd_step``).  ``flat_m`` is the momentum buffer (initialised with the first gradient, as torch does)."""
+    (``mnas_sgd_step``).  ``flat_m`` is the momentum buffer (initialised with the first gradient, as torch does).  Parameter
+    groups and decoupled decay as :class:`FlatAdam`; ``trust_ratio="lars"``."""
+    _trust_name = "lars"
 
     def __init__(self, params, flat_p, flat_g, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0,
                  **extras):
@@ -342,8 +550,13 @@ class FlatSGD(FlatAdam):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         super().__init__(params, flat_p, flat_g, lr=lr, weight_decay=weight_decay, grad_scale=grad_scale, **extras)
         for k in ("betas", "eps"):
-            self.param_groups[0].pop(k, None)
-        self.param_groups[0].update(momentum=momentum, dampening=dampening, nesterov=nesterov)
+            self.defaults.pop(k, None)
+        self.defaults.update(momentum=momentum, dampening=dampening, nesterov=nesterov)
+        for g in self.param_groups:
+            g.pop("betas", None)
+            g.pop("eps", None)
+            for k in ("momentum", "dampening", "nesterov"):
+                g.setdefault(k, self.defaults[k])
 
     def _launch(self, a, b, g, ex=None):
         args = (self.flat_p.data_ptr() + 4 * a, self.flat_g.data_ptr() + 4 * a,
@@ -355,6 +568,39 @@ class FlatSGD(FlatAdam):
         else:
             L.check(self._lib.mnas_sgd_step_ex(*args, ctypes.byref(ex), L.cur_stream()), "sgd_step_ex")
 
+    def _launch_seg(self, g, segs, ex):
+        L.check(self._lib.mnas_sgd_step_seg(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.flat_m.data_ptr(),
+                                            float(g["momentum"]), float(g["dampening"]), 1 if g["nesterov"] else 0, self.step_count,
+                                            float(self.grad_scale), ctypes.byref(segs),
+                                            ctypes.byref(ex) if ex is not None else None, L.cur_stream()), "sgd_step_seg")
+
+
+def norm_bias_groups(model: nn.Module, weight_decay: float):
+    """Two parameter groups: tensors with ``ndim <= 1`` (BatchNorm weights and biases, conv / linear biases) get no weight decay
+    and no trust ratio, everything else ``weight_decay`` -- torchvision's ``--norm-weight-decay 0`` and the published MnasNet
+    setting.  For ``Trainer(param_groups=...)`` (as a callable: ``lambda m: norm_bias_groups(m, 1e-5)``) or the optimizers."""
+    decay, no_decay = [], []
+    for p in model.parameters():
+        (no_decay if p.ndim <= 1 else decay).append(p)
+    return [{"params": decay, "weight_decay": weight_decay}, {"params": no_decay, "weight_decay": 0.0, "trust": False}]
+
+
+def stage_lr_groups(model: nn.Module, lr: float, decay: float, groups=None):
+    """Layer-wise learning-rate decay for fine-tuning: the head trains at ``lr``, ``model.features[k]`` at
+    ``lr * decay ** (len(model.features) - 1 - k)`` (the eight MnasNet stages: ``decay ** (7 - k)``).  ``groups``: a list of group
+    dicts to split by stage, their other keys kept (``stage_lr_groups(m, lr, d, norm_bias_groups(m, wd))``: at most 18 groups);
+    None: all of the model's parameters."""
+    feats = model.features
+    stage_of = {id(p): k for k, child in enumerate(feats) for p in child.parameters()}
+    out = []
+    for g in (groups if groups is not None else [{"params": list(model.parameters())}]):
+        by_stage = {}
+        for p in g["params"]:
+            by_stage.setdefault(stage_of.get(id(p), len(feats)), []).append(p)
+        for k in sorted(by_stage, reverse=True):
+            out.append({**g, "params": by_stage[k], "lr": lr * decay ** max(0, len(feats) - 1 - k)})
+    return out
+
 
 class Trainer:
     """Owns flat parameter / gradient / Adam-moment buffers for ``model`` (a FineTuneModelPool or anything with
@@ -362,12 +608,21 @@ class Trainer:
     ``trainer.optimizer`` is a :class:`FlatAdam` (a ``torch.optim.Optimizer``): hand it to the reference's schedulers and
     checkpoint it with ``optimizer.state_dict()`` exactly as train.py does.  ``clip_grad_norm=``, ``skip_nonfinite=`` and
     ``ema_decay=`` go to the optimizer (see :class:`FlatAdam`); in a distributed trainer the norm is taken after the all-reduce with
-    ``grad_scale = 1/world``, i.e. over the mean gradient, and is bit-identical on every rank."""
+    ``grad_scale = 1/world``, i.e. over the mean gradient, and is bit-identical on every rank.
+
+    ``param_groups=`` (a list of torch-style group dicts, or a callable ``model -> list``, e.g. :func:`norm_bias_groups` and
+    :func:`stage_lr_groups`; parameters no group names join a default group), ``decoupled_weight_decay=`` (AdamW; also for RMSprop and
+    SGD), ``trust_ratio=`` / ``trust_coef=`` go to the optimizer too.  ``optimizer="lamb"`` is Adam with the LAMB trust ratio,
+    ``optimizer="lars"`` SGD with the LARS one; :meth:`trust_ratios` reads them by parameter name.  ``optimizer="adamw"`` has always
+    been accepted as plain Adam (the name is matched by prefix) and still is: pass ``decoupled_weight_decay=True`` for AdamW.  Data
+    parallel needs no further collective: the per-tensor norms are taken after the all-reduce, on buffers that are identical on
+    every rank, by a summation that does not depend on the grid."""
 
     def __init__(self, model: nn.Module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  criterion: Optional[nn.Module] = None, distributed: bool = False, process_group=None,
                  early_bucket_stage: int = 5, optimizer: str = "adam", meters=None, teacher: Optional[nn.Module] = None,
-                 **optimizer_kwargs):
+                 param_groups=None, decoupled_weight_decay: bool = False, trust_ratio: Optional[str] = None,
+                 trust_coef: float = 1e-3, **optimizer_kwargs):
         self.model = model
         self.teacher = teacher           # knowledge distillation: step() runs it in eval mode and wraps the target (_teach)
         self.meters = meters             # metrics.DeviceMeters / MultiLabelMeters or None: train.py:447,453-468 on the device
@@ -427,21 +682,60 @@ class Trainer:
             self.engine.join_stages = self.schedule.join_stages
             self.engine.reset_programs()
         # train.py:218-231: --optimizer adam | rmsprop | sgd, each constructed with lr only
+        # "lamb" = Adam with the LAMB trust ratio, "lars" = SGD with the LARS one.  "adamw" has always been taken as plain Adam by
+        # the prefix match below and still is: decoupled decay is asked for with decoupled_weight_decay=True.
+        if optimizer == "lamb":
+            optimizer, trust_ratio = "adam", "lamb"
+        elif optimizer == "lars":
+            optimizer, trust_ratio = "sgd", "lars"
+        params = self._resolve_groups(param_groups, head + eng_params)
+        optimizer_kwargs = dict(optimizer_kwargs, decoupled_weight_decay=decoupled_weight_decay, trust_ratio=trust_ratio,
+                                trust_coef=trust_coef)
         if optimizer.startswith("adam"):
-            self.optimizer = FlatAdam(head + eng_params, self.flat_p, self.flat_g, lr=lr, betas=betas, eps=eps,
+            self.optimizer = FlatAdam(params, self.flat_p, self.flat_g, lr=lr, betas=betas, eps=eps,
                                       weight_decay=weight_decay, grad_scale=1.0 / self.world, **optimizer_kwargs)
         elif optimizer.startswith("rmsprop"):
-            self.optimizer = FlatRMSprop(head + eng_params, self.flat_p, self.flat_g, lr=lr, weight_decay=weight_decay,
+            self.optimizer = FlatRMSprop(params, self.flat_p, self.flat_g, lr=lr, weight_decay=weight_decay,
                                          grad_scale=1.0 / self.world, **optimizer_kwargs)
         elif optimizer.startswith("sgd"):
-            self.optimizer = FlatSGD(head + eng_params, self.flat_p, self.flat_g, lr=lr, weight_decay=weight_decay,
+            self.optimizer = FlatSGD(params, self.flat_p, self.flat_g, lr=lr, weight_decay=weight_decay,
                                      grad_scale=1.0 / self.world, **optimizer_kwargs)
         else:
             raise ValueError("Optimizer not supported")            # train.py:231
 
+    def _resolve_groups(self, param_groups, every):
+        """``param_groups`` (None, a list of group dicts, or a callable model -> such a list) -> what the optimizer is built from.
+        Parameters that no group names join one further group that takes the constructor's defaults."""
+        if param_groups is None:
+            return every
+        groups = param_groups(self.model) if callable(param_groups) else param_groups
+        groups = [dict(g, params=list(g["params"])) for g in groups]
+        known = {id(p) for p in every}
+        named = set()
+        for g in groups:
+            for p in g["params"]:
+                if id(p) not in known:
+                    raise ValueError("a parameter group names a tensor that is not a parameter of the model")
+                if id(p) in named:
+                    raise ValueError("a parameter appears in more than one parameter group")
+                named.add(id(p))
+        groups = [g for g in groups if g["params"]]
+        rest = [p for p in every if id(p) not in named]
+        if rest:
+            groups.append({"params": rest})
+        return groups
+
+    def trust_ratios(self):
+        """{parameter name: the last step's trust ratio} (``optimizer="lamb"`` / ``"lars"``; ONE host read).  Frozen parameters
+        are absent, a ``trust=False`` group's read 1.0."""
+        names = {id(p): k for k, p in self.model.named_parameters()}
+        every = self.optimizer._all_params
+        return {names.get(id(every[i]), "param%d" % i): r for i, r in self.optimizer.trust_ratios().items()}
+
     # convenience mirrors of the optimizer's hyper-parameters / state
     @property
     def lr(self):
+        """group 0's learning rate (with several parameter groups: set the others through ``optimizer.param_groups`` or a scheduler)"""
         return self.optimizer.param_groups[0]["lr"]
 
     @lr.setter
