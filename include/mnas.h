@@ -29,6 +29,23 @@
  *   row 2 c1                              row 6 invstd
  *   row 3 c2                              row 7 (reserved)
  *   Frozen statistics (mnas_bn_frozen_tables): rows 5, 6 hold the running mean and 1/sqrt(running_var+eps), c1 = s, c2 = c3 = 0.
+ *   Who touches which rows (tests/plan_access.py is this, per launch-list slot, and tests/test_gpu_plan_access.py holds it to the kernels):
+ *     mnas_bn_fwd_finalize        writes 0, 1 and, training, 5, 6          mnas_bn_frozen_tables   writes 0..6
+ *     act-on-load (scale, shift)  reads 0, 1 (two pointers)               dy-on-load (coef)       reads 0..4
+ *     every BatchNorm-backward reduce, fused (red_bn) or mnas_bn_bwd_reduce (bnbuf): reads 0, 1 (the mask) and 5, 6 (xhat)
+ *     mnas_bn_bwd_finalize / mnas_bwd_post: read 0, 5, 6, write 2..4; their frozen twins read 0, 5, 6 and write nothing
+ *     row 7 is touched by nobody.
+ *
+ * Partial tables (all fp32, all fully overwritten by their producer, no memset needed; "cols" is the producer's nparts unless the
+ * library picks it, in which case the host-side query named below says how many):
+ *   statistics and reduce partials      float[2][C][cols]   conv / stem / tconv: cols = nparts; depthwise: mnas_dw_rows;
+ *                                                           mnas_se_bwd_apply: mnas_se_bwd_apply_cols; mnas_bn_bwd_reduce: nparts
+ *   weight-gradient partials            float[rows][Co][taps*Ci] (depthwise: float[rows][k*k][C]); rows = nsplit / nparts
+ *                                       (depthwise: mnas_dw_rows which = 1, 3, 7)
+ *   A finalize reads exactly rows x the row size it is told.  Two-level reductions (more than 256 rows) fold every 128-row chunk
+ *   into the chunk's first row, in place: those rows are read and then overwritten, the other rows are only read.
+ *   mnas_se_proj_finalize reads all N*kseg slabs and overwrites slab n*kseg of every image with the image's gated sum.
+ *   mnas_se_bwd_reduce's scratch is float[splits][N][C] = mnas_se_scratch_bytes, written and consumed inside the call.
  */
 #ifndef MNAS_H
 #define MNAS_H
