@@ -459,7 +459,11 @@ def test_dw_bwd(shape, phase):
 # ---------------------------------------------------------------------------------------------------
 # stride-2 depthwise (SepConv(reduce=True), mnasnet.py:73-81; csrc/mnas_dw2.hip): forward + statistics, input gradient, weight
 # gradient through mnas_dw_fwd / mnas_dw_bwd with stride = 2; odd planes, 5x5, more than 256 channel pairs (two channel blocks)
-@pytest.mark.parametrize("shape", [(2, 12, 12, 48, 3), (3, 13, 11, 72, 5), (2, 9, 9, 600, 3), (5, 7, 8, 32, 5)])
+# + the corners of dw2_plan: C = 8 (4 channel pairs per block, 64 pixel lanes), C = 200 (100 pairs, 2 pixel lanes, 56 idle threads),
+# C = 520 (two channel blocks, the second with 4 pairs), 1 x 1 and 2 x 2 planes (Ho = Wo = 1: nparts above the pixel count)
+@pytest.mark.parametrize("shape", [(2, 12, 12, 48, 3), (3, 13, 11, 72, 5), (2, 9, 9, 600, 3), (5, 7, 8, 32, 5),
+                                   (2, 6, 5, 8, 3), (2, 5, 7, 200, 5), (2, 5, 4, 520, 3), (3, 1, 1, 16, 3), (1, 1, 1, 8, 5),
+                                   (2, 2, 2, 24, 5), (2, 2, 2, 8, 3)])
 def test_dw_stride2(shape):
     """+ the bounds of test_dw_fwd / test_dw_bwd at stride 2"""
     lib = L.load()
