@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of the MNASNet train step (src/train.py:423-440 of the reference) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full]
 
 Workload (BASELINE.json configs[1]/[2]): MNASNet-1.0 = Mnasnet(cut_channels_first=False) + FineTuneModelPool
 head '512', num_classes 1000, bs=256 per GPU, synthetic 3x224x224 fp32 batches resident in HBM,
@@ -15,10 +15,16 @@ synchronize; `ms_per_step` in the JSON line is that window's time / K.  --min-se
 seconds of timed work exist and reports the median window.  --dump-outputs DIR writes what the last timed step returned to its
 caller (loss, logits, gradients, updated parameters, BatchNorm buffers) as DIR/<name>.npy.
 
-Extra objects in the JSON line:
+A plain run does what the headline figure needs and nothing else: set-up, the untimed steps, the timed window(s), the dump if
+asked for, the result line.  Everything else the benchmark measures is behind --full, off by default: the roofline and per-kernel
+objects, the box calibration probes and the CPU baseline.  --full changes neither the number of steps run before the timed window
+nor their inputs, so --dump-outputs writes the same arrays with and without it.
+
+Extra objects in the JSON line with --full:
   roofline     -- for the kernel class that takes the most time in the step: algorithmic bytes it must move
                   (its input and output tensors once, bf16 NHWC) / its launch time measured with
                   HIP events recorded around every launch of that class inside the timed region.
+  box          -- what this GPU sustains (copy GB/s, packed-FMA TFLOP/s, clocks) before the warm-up and after the timed windows.
   cpu_baseline -- the CPU oracle (oracle/mnasnet_oracle.py, a port of the reference's eager path; the
                   reference sources do not travel to the GPU box) running the same step at bs=32 on the host
                   cores, rank 0, N=1 only.  A reported baseline, not the optimisation target.
@@ -111,11 +117,18 @@ def parse():
     ap.add_argument("--dump-state", type=str, default="",
                     help="TESTS: after the timed windows every rank writes <dir>/rank<r>.json (sha256 of its flat parameter buffer, "
                          "the bucket schedule of its last step, whether it ran the roofline calibration)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-box", action="store_true", help="skip the box calibration probes (copy GB/s, packed-FMA TFLOP/s, clocks)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline / kernel_classes objects (every conv-kernel "
+                         "launch bracketed with HIP events in two untimed steps, the dominant class in the last timed step), the box "
+                         "calibration probes before the warm-up and after the timed windows, and the CPU baseline (--gpus 1).  "
+                         "--no-roofline, --no-box and --no-cpu-baseline take single parts out again")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-box", action="store_true", help="with --full: skip the box calibration probes (copy GB/s, packed-FMA "
+                                                          "TFLOP/s, clocks)")
     ap.add_argument("--smi", action="store_true", help="also keep a rocm-smi / amd-smi snapshot in the box object: a CHILD process, started before this "
                                                       "process touches the GPU and never when a profiler / tool library is preloaded")
-    ap.add_argument("--no-roofline", action="store_true", help="do not bracket kernels with HIP events")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: do not bracket kernels with HIP events; with or without "
+                                                               "it: skip the four untimed steps of that calibration")
     ap.add_argument("--auto-graphs", type=float, default=0.92,
                     help="host-bound guard: if, after the warm-up, the host needs more than this share of a step's wall time to enqueue it "
                          "(MAX over ranks), the launch lists are replayed as hipGraphs (Engine.use_graphs: 0.6 ms of host time per step at "
@@ -133,6 +146,8 @@ def parse():
         args.batch = 64 if args.clusters else 256
     if args.dump_outputs and args.clusters:
         ap.error("--dump-outputs covers the single-shape step, not --clusters")
+    if args.smi and not args.full:
+        ap.error("--smi adds to the box object, which is measured with --full only")
     return args
 
 
@@ -662,7 +677,7 @@ def main():
             os.environ["MASTER_PORT"] = str(sk.getsockname()[1])
     # opt-in child process, BEFORE anything in this process touches the GPU and never with a tool library mapped (smi_snapshot
     # refuses by itself: rocprofv3's preloaded library has initialised the GPU before main() runs)
-    smi = smi_snapshot() if (rank == 0 and args.smi and not args.no_box) else None
+    smi = smi_snapshot() if (rank == 0 and args.full and args.smi and not args.no_box) else None
     if not args.one_device:
         ndev = torch.cuda.device_count()             # counts devices without initialising the GPU
         if ndev < max(1, (args.gpus if distributed else 1)) or local_rank >= max(ndev, 1):
@@ -711,7 +726,7 @@ def main():
         overrides.append("--one-device (functional test of the multi-rank path: all ranks on cuda:0 over gloo; NOT a measurement)")
     if args.force_distributed:
         overrides.append("--force-distributed (functional test: the multi-rank code path as a one-rank RCCL job)")
-    profile = (not args.no_roofline) and rank == 0
+    profile = args.full and (not args.no_roofline) and rank == 0
     ALL_OPS = {L.OP_CONV_GEMM, L.OP_CONV_WGRAD, L.OP_DW_FWD, L.OP_DW_BWD, L.OP_BN_BWD_REDUCE, L.OP_STEM_FWD, L.OP_STEM_WGRAD,
                L.OP_ADD_ACT, L.OP_PW_BWD, L.OP_POOL_ACT, L.OP_POOL_BWD, L.OP_DY_MAT, L.OP_TCONV_DGRAD,
                L.OP_SE_SCALE, L.OP_SE_BWD_REDUCE, L.OP_SE_BWD_APPLY}
@@ -741,7 +756,7 @@ def main():
     # 75 ms of full vector load and 12 GiB of copies, on rank 0 only, changed the thermal / clock state the windows were measured
     # in); every rank runs it (the MAX-over-ranks time must not depend on which rank was heated), rank 0 reports
     box, probe = None, None
-    if not args.no_box:
+    if args.full and not args.no_box:
         probe = BoxProbe(L.load(), dev)
         box = {"before": probe.measure()}
     for _ in range(args.warmup):
@@ -782,6 +797,8 @@ def main():
     # ---- roofline calibration (untimed, rank 0): bracket EVERY conv-kernel launch with HIP events for two steps, find the
     # kernel class with the largest time, then bracket only that class inside the timed region (bracketing all ~190
     # launches costs 7 % of the step rate; one class costs < 1 %)
+    # Without --full nothing is bracketed, on any rank; the four steps run all the same, as they do on ranks > 0: what the timed
+    # steps start from, and so what --dump-outputs writes, must not depend on --full
     calib, dom_key = None, None
     if not args.no_roofline:                 # every rank runs the same extra steps (they contain collectives)
         if profile:
@@ -934,7 +951,7 @@ def main():
         res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if args.h2d and world == 1:
         res["pcie_inclusive"] = h2d_mode(trainer, model, x, target, args.steps, dev)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(args.cpu_seconds, 5 if (args.k5 or args.se) else None, 0.25 if args.se else 0.0)
     print(json.dumps(res))
     if distributed:

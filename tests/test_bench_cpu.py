@@ -116,3 +116,25 @@ def test_steps_default_is_one_window():
     finally:
         sys.argv = argv
     assert a.steps == 7 and a.min_seconds == 0 and a.dump_outputs == ""
+
+
+def test_full_is_off_by_default(capsys):
+    """A plain command line measures the headline figure only; the roofline, box and CPU-baseline legs hang on --full, and --smi,
+    which adds to the box object, is refused without it."""
+    import sys
+
+    import pytest
+    b = _bench()
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "1"]
+        assert b.parse().full is False
+        sys.argv += ["--full", "--smi"]
+        a = b.parse()
+        assert a.full is True and not (a.no_roofline or a.no_box or a.no_cpu_baseline)
+        sys.argv = ["bench.py", "--smi"]
+        with pytest.raises(SystemExit):
+            b.parse()
+    finally:
+        sys.argv = argv
+    assert "--full" in capsys.readouterr().err

@@ -158,14 +158,14 @@ def test_real_engine_world2_mixed_shapes(tmp_path):
 def test_bench_multi_rank_path_on_one_gpu():
     """bench.py's own N > 1 code path (rank-0 broadcast inside Trainer, barrier + MAX-over-ranks timing, calibration steps on every
     rank, only rank 0 printing) as the driver launches it -- `python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2` --
-    with --one-device (both ranks on cuda:0 over gloo): ONE JSON line, n_gpus 2, weak scaling, global batch = 2 x per-GPU batch, a
-    roofline object, no cpu_baseline (rank 0 at N = 1 only), and the override recorded so that the line can never pass for a
+    with --one-device (both ranks on cuda:0 over gloo) and --full: ONE JSON line, n_gpus 2, weak scaling, global batch = 2 x per-GPU
+    batch, a roofline object, no cpu_baseline (rank 0 at N = 1 only), and the override recorded so that the line can never pass for a
     measurement."""
     import json
     root = os.path.dirname(HERE)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-           "--batch", "32", "--size", "64", "--min-seconds", "0", "--one-device", "--no-box"]
+           "--batch", "32", "--size", "64", "--min-seconds", "0", "--one-device", "--full", "--no-box"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -229,6 +229,30 @@ def test_bench_dump_outputs_repeatable(tmp_path):
     assert np.abs(a["grads"]).max() > 0
 
 
+def test_bench_plain_run_is_lean_and_full_changes_no_output(tmp_path):
+    """A plain run reports the headline figure and nothing that costs runs of its own: no roofline, kernel_classes, box or
+    cpu_baseline object.  --full brings them back (the CPU baseline is left out here: it alone takes longer than the rest of the
+    test) and changes nothing about the steps: the same number of them before the timed window, the same inputs, so the dumped
+    arrays of the two runs are equal bit for bit."""
+    import numpy as np
+    root = os.path.dirname(HERE)
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "32",
+            "--size", "64", "--auto-graphs", "0"]
+    moved = ("roofline", "kernel_classes", "bracketed_ms_per_step", "box", "cpu_baseline")
+    plain = _bench_line(base + ["--dump-outputs", str(tmp_path / "plain")])
+    assert not [k for k in moved if k in plain], sorted(plain)
+    for k, v in (("unit", "images/sec"), ("higher_is_better", True), ("dtype", "bf16"), ("steps", 3), ("warmup", 2), ("windows", 1)):
+        assert plain[k] == v, k
+    # value and ms_per_step say the same window: batch / ms_per_step, up to the line's rounding (0.0005 ms and 0.05 img/s)
+    assert plain["value"] > 0 and abs(plain["value"] - 32 * 1e3 / plain["ms_per_step"]) <= 0.00051 / plain["ms_per_step"] * plain["value"] + 0.06
+    full = _bench_line(base + ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    assert full["roofline"]["launches_per_step"] >= 1 and full["kernel_classes"] and "read_GBps" in full["box"]["after"]
+    assert full["metric"] == plain["metric"] and "cpu_baseline" not in full
+    for n in ("loss", "logits", "grads", "params", "bn_buffers"):
+        a, b = np.load(tmp_path / "plain" / (n + ".npy")), np.load(tmp_path / "full" / (n + ".npy"))
+        assert np.array_equal(a, b), "%s depends on --full" % n
+
+
 def test_bench_distributed_path_on_rccl_one_rank():
     """bench.py's N > 1 branches on the REAL backend: `--gpus 1 --force-distributed` initialises the process group on "nccl" (= RCCL)
     with device_id, builds Trainer(distributed=True) (rank-0 broadcast, two gradient buckets all-reduced asynchronously on RCCL's
@@ -266,7 +290,7 @@ def test_real_engine_world4_one_gpu(tmp_path):
 
 
 def test_bench_world4_dry_run_on_one_gpu(tmp_path):
-    """The driver's multi-GPU command line, dry: plain `python3 bench.py --gpus 4 --one-device --batch 32 --steps 5 --warmup 2`
+    """The driver's multi-GPU command line, dry: plain `python3 bench.py --gpus 4 --one-device --batch 32 --steps 5 --warmup 2 --full`
     (bench.py starts its ranks as a CHILD torch.distributed.run on a free port; nothing is exec'ed from a process that has
     touched the GPU).  ONE JSON line, n_gpus 4, global batch 128; every rank finished with bit-equal parameters and the same
     bucket order; only rank 0 ran the roofline calibration; per-rank BatchNorm statistics differ."""
@@ -275,7 +299,7 @@ def test_bench_world4_dry_run_on_one_gpu(tmp_path):
     root = os.path.dirname(HERE)
     dump = str(tmp_path / "state")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--one-device", "--batch", "32", "--steps", "5",
-           "--warmup", "2", "--min-seconds", "0", "--dump-state", dump]
+           "--warmup", "2", "--min-seconds", "0", "--full", "--dump-state", dump]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-3000:]

@@ -1,11 +1,12 @@
-"""Copy what tools/collect_round.sh left in gpurun_out/ into profiles/ under the round tag:  python3 tools/install_profiles.py r03
+"""Copy what tools/collect_round.sh left in its output folder (BENCH_OUT, default bench_out/) into profiles/ under the round tag:
+python3 tools/install_profiles.py r03
 (kernel trace, timeline, PMC passes, SQ / MFMA tables, the default bench line, the variant benches folded into ONE json, the
 per-launch list of the fused-block run)."""
 import json, os, shutil, sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r05"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src, dst = os.path.join(root, "gpurun_out"), os.path.join(root, "profiles")
+src, dst = os.environ.get("BENCH_OUT") or os.path.join(root, "bench_out"), os.path.join(root, "profiles")
 COPY = {"prof_%s_kernel_trace.txt": "%s_kernel_trace.txt", "prof_%s_timeline.txt": "%s_timeline.txt",
         "prof_%s_pmc_fetch_size.txt": "%s_pmc_fetch_size.txt", "prof_%s_pmc_write_size.txt": "%s_pmc_write_size.txt",
         "%s_pmc_per_class.json": "%s_pmc_per_class.json", "%s_sq_counters.txt": "%s_sq_counters.txt",

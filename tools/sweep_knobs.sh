@@ -1,12 +1,13 @@
 #!/bin/bash
 # Whole-step sweep of the engine's grid knobs (bench.py overrides), one line per setting, the default interleaved:  bash tools/sweep_knobs.sh
 cd ${GRAFT_REPO_ROOT:-$PWD}
+OUT=${BENCH_OUT:-$PWD/bench_out}; mkdir -p $OUT
 run() {  # name, env assignments...
   name=$1; shift
-  env "$@" python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-box > gpurun_out/knob.txt 2>/dev/null
-  python3 - "$name" <<'PY'
+  env "$@" python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-box > $OUT/knob.txt 2>/dev/null
+  python3 - "$name" $OUT/knob.txt <<'PY'
 import sys, json
-d = json.loads([l for l in open("gpurun_out/knob.txt") if l.startswith("{")][-1])
+d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])
 kc = d["kernel_classes"]
 print("%-28s %9.1f img/s %7.3f ms  " % (sys.argv[1], d["value"], d["ms_per_step"]) + " ".join("%s=%.3f" % (k.replace("k_", ""), v["ms_per_step"]) for k, v in list(kc.items())[:6]), flush=True)
 PY
