@@ -18,6 +18,20 @@ same observable behaviour as autograd's AccumulateGrad, without ~110 tiny copy k
 accumulate their ``layers`` contributions; in train mode ``conv.bias.grad`` is exactly zero (batch-statistics
 BatchNorm cancels the bias; the reference gets ~1e-5 rounding noise there).
 
+Several forwards may be alive at once (up to _MAX_PROGRAMS_PER_SHAPE per shape and mode, any number of shapes and modes, no-grad
+forwards in between): a Program owns its activations and BatchNorm coefficient blocks, so a backward depends only on its own
+program, and any interleaving of forwards and backwards gives, bit for bit, the outputs, input gradients, running statistics (forward
+order) and accumulated ``.grad`` (backward order) of the same jobs run one after the other (tests/test_gpu_lifetimes.py).
+Stale state: what is NOT per program is read at backward time where it lives then -- the packed weights (re-packed by every forward),
+``conv.bias`` / the stem's and squeeze-excite's weights (read in place) and, for the stem's weight gradient, the caller's batch.  The
+rule is autograd's for saved tensors: between a forward and its backward no parameter of the subtree and (when the stem trains)
+not the batch may be modified in place, and no parameter or BatchNorm buffer may get new storage.  The forward keeps their
+``_version`` counters and the storage signature on its lease and the backward compares them (Engine.check_unchanged): a change
+raises a RuntimeError that names it and asks for the forward again, instead of returning a finite gradient of nothing.  Replacing
+storage (``p.data = ...``) while a forward is alive makes the NEXT forward raise too (reset_programs) until that output is dropped.
+Not seen: writes that bypass the version counter (``p.data.mul_()``, kernels writing through raw pointers such as Trainer's fused
+optimizers) -- do not run Trainer.step between a module-path forward and its backward.
+
 Frozen BatchNorm statistics: a TRACKED forward of a subtree that is entirely in eval mode (``model.train();
 model.features.eval()``, classifiers.FineTuneModelPool.freeze_bn) runs the frozen program (launch_plan.LaunchPlan,
 frozen_bn): the eval forward, bit for bit, with its activations kept (the same launches without squeeze-excite; with
@@ -250,10 +264,13 @@ class _Lease:
     """Ties a Program's activation buffers to the autograd graph of ONE forward.  The program is handed back when
     backward has consumed it OR when the graph is dropped without a backward (exception between forward and backward,
     LR finder, BatchNorm recalibration pass, ...): ``ctx`` dies with the graph and takes this object with it."""
-    __slots__ = ("prog", "consumed", "__weakref__")
+    __slots__ = ("prog", "consumed", "sig", "versions", "x_version", "__weakref__")
 
-    def __init__(self, prog):
+    def __init__(self, prog, sig=None, versions=(), x_version=None):
         self.prog, self.consumed = prog, False
+        # forward-time facts, compared in backward (Engine.check_unchanged): the storage signature, every parameter's version counter
+        # and, where the backward reads the batch, the batch's
+        self.sig, self.versions, self.x_version = sig, versions, x_version
         prog.busy = True
 
     def release(self):
@@ -278,7 +295,10 @@ class _EngineFn(torch.autograd.Function):
                            frozen_bn=frozen, first_trainable=first)
         out = prog.run_forward(x)
         ctx.eng = eng
-        ctx.lease = _Lease(prog) if track else None
+        ctx.lease = None
+        if track:
+            ctx.lease = _Lease(prog, eng._sig, tuple(p._version for p in eng.params),
+                               prog.x_ref._version if prog.patch_x_bwd is not None else None)
         return out
 
     @staticmethod
@@ -293,6 +313,7 @@ class _EngineFn(torch.autograd.Function):
                                "(retain_graph=True is not supported through mnasnet_pytorch_amd modules)")
         prog = lease.prog
         try:
+            eng.check_unchanged(lease)
             accumulate = eng.prepare_grads()
             dx = prog.run_backward(gout.contiguous().float(), eng.on_stage_done)
             eng.finish_grads(accumulate)
@@ -638,6 +659,29 @@ class Engine:
         p = Program(self, N, H, W, training, need_dx, pooled, in_u8, frozen_bn=frozen_bn, first_trainable=first_trainable)
         lst.append(p)
         return p
+
+    # ---- forward-time state a backward depends on ---------------------------------------------------
+    def _param_name(self, p):
+        for name, q in self.root.named_parameters():
+            if q is p:
+                return name
+        return "<parameter of shape %s>" % (tuple(p.shape),)
+
+    def check_unchanged(self, lease: _Lease):
+        """A backward reads the packed weights, some parameters and (stem weight gradient) the batch where they live NOW, against
+        activations of the forward: it is only the gradient of that forward if none of them changed since.  Raises otherwise
+        (module docstring, "Stale state"); host-side only, nothing is launched."""
+        if lease.sig is not None and self._signature() != lease.sig:
+            raise RuntimeError("a parameter or BatchNorm buffer was given new storage (p.data = ..., .to(), ...) after the forward this "
+                               "backward belongs to: its launch lists still name the old storage; run the forward again")
+        for p, v in zip(self.params, lease.versions):
+            if p._version != v:
+                raise RuntimeError("parameter %s was modified in place between a forward and its backward (optimizer step, "
+                                   "weight swap, mul_ ...): the backward would read the new weights against the old "
+                                   "activations; run the forward again" % self._param_name(p))
+        if lease.x_version is not None and lease.prog.x_ref is not None and lease.prog.x_ref._version != lease.x_version:
+            raise RuntimeError("the input batch was modified in place between a forward and its backward: the stem's weight "
+                               "gradient reads the batch in backward; run the forward again (or pass a copy)")
 
     # ---- .grad bookkeeping (AccumulateGrad semantics on a flat buffer) -----------------------------
     def prepare_grads(self):

@@ -76,17 +76,25 @@ class _HeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, head, x, *params):
         seeds = head.next_seeds()
-        us, logits = head.forward_layers(x, seeds)
-        ctx.head, ctx.seeds, ctx.us = head, seeds, us
+        # forward-time facts the backward needs: the mode decides whether the dropout masks apply (the masks are never stored, the
+        # backward re-derives them from the seeds), the version counters say whether the weights are still the forward's
+        training = bool(head.owner.training)
+        us, logits = head.forward_layers(x, seeds, training)
+        ctx.head, ctx.seeds, ctx.us, ctx.training = head, seeds, us, training
+        ctx.versions = tuple(p._version for p in head.params())
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         head = ctx.head
+        for (name, p), v in zip(head.named_params(), ctx.versions):
+            if p._version != v:
+                raise RuntimeError("classifier parameter %s was modified in place between a forward and its backward: the head's "
+                                   "input gradient would use the new weights; run the forward again" % name)
         grads = [(torch.empty_like(l.lin.weight), torch.empty_like(l.lin.bias) if l.lin.bias is not None else None)
                  for l in head.layers]
         dx = head.backward_layers(ctx.us, ctx.seeds, dlogits.contiguous().float(), grads, accumulate=False,
-                                  need_dx=ctx.needs_input_grad[1])
+                                  need_dx=ctx.needs_input_grad[1], training=ctx.training)
         flat = []
         for (dw, db), l in zip(grads, head.layers):
             flat.append(dw)
@@ -121,6 +129,15 @@ class NativeHead:
                 out.append(l.lin.bias)
         return out
 
+    def named_params(self):
+        """(name, parameter) in the order of params(); the name is the Linear's index in the layer list"""
+        out = []
+        for i, l in enumerate(self.layers):
+            out.append(("linear[%d].weight" % i, l.lin.weight))
+            if l.lin.bias is not None:
+                out.append(("linear[%d].bias" % i, l.lin.bias))
+        return out
+
     def next_seeds(self) -> List[int]:
         self.calls += 1
         return [_mix(self.seed0, self.calls, i) for i in range(len(self.layers))]
@@ -132,17 +149,18 @@ class NativeHead:
         if x.dim() != 2 or x.shape[1] != self.layers[0].lin.in_features:
             raise ValueError("head input must be (N, %d), got %s" % (self.layers[0].lin.in_features, tuple(x.shape)))
 
-    def _desc(self, l: _Layer, N: int, seed: int) -> L.MnasHeadLinear:
+    def _desc(self, l: _Layer, N: int, seed: int, training: Optional[bool] = None) -> L.MnasHeadLinear:
+        """training: the mode of the forward this descriptor belongs to (None: the owner's mode now)"""
         a = L.MnasHeadLinear()
         a.N, a.I, a.O = N, l.lin.in_features, l.lin.out_features
         a.relu = 1 if l.relu else 0
-        a.drop_p = l.p if self.owner.training else 0.0
+        a.drop_p = l.p if (self.owner.training if training is None else training) else 0.0
         a.seed = seed
         a.w = l.lin.weight.data_ptr()
         a.b = L.ptr(l.lin.bias)
         return a
 
-    def forward_layers(self, x, seeds):
+    def forward_layers(self, x, seeds, training: Optional[bool] = None):
         """-> ([input of every layer], logits).  x: (N, I0) fp32 contiguous."""
         self._check(x)
         x = x.contiguous().float()
@@ -152,19 +170,20 @@ class NativeHead:
             if not (l.lin.weight.is_contiguous() and l.lin.weight.dtype == torch.float32):
                 raise RuntimeError("head weights must be contiguous fp32")
             y = torch.empty((N, l.lin.out_features), dtype=torch.float32, device=x.device)
-            a = self._desc(l, N, seed)
+            a = self._desc(l, N, seed, training)
             a.x, a.y = x.data_ptr(), y.data_ptr()
             L.check(self.lib.mnas_head_linear_fwd(C.byref(a), L.cur_stream()), "head_linear_fwd")
             us.append(x)
             x = y
         return us, x
 
-    def backward_layers(self, us, seeds, dz, grads, accumulate: bool, need_dx: bool = True):
-        """dz: gradient of the logits.  grads[i] = (dW, db or None) tensors written (or accumulated into).  -> dx or None"""
+    def backward_layers(self, us, seeds, dz, grads, accumulate: bool, need_dx: bool = True, training: Optional[bool] = None):
+        """dz: gradient of the logits.  grads[i] = (dW, db or None) tensors written (or accumulated into).  -> dx or None.
+        training: the mode the forward ran in (its dropout masks apply again); None: the owner's mode now"""
         N = dz.shape[0]
         for i in range(len(self.layers) - 1, -1, -1):
             l = self.layers[i]
-            a = self._desc(l, N, seeds[i])
+            a = self._desc(l, N, seeds[i], training)
             a.x, a.dz = us[i].data_ptr(), dz.data_ptr()
             a.dw, a.db = grads[i][0].data_ptr(), L.ptr(grads[i][1])
             a.accumulate = 1 if accumulate else 0

@@ -240,6 +240,22 @@ def test_dropped_graph_releases_its_program():
     assert len([p for lst in eng.programs.values() for p in lst]) == 2
     (a.sum() + b.sum()).backward()
     assert not any(p.busy for lst in eng.programs.values() for p in lst)
+    # ... and what the two live programs accumulate is what two serial steps accumulate, bit for bit.  Dropout off for this part:
+    # a and b then are equal terms, so the order autograd picks for their backwards cannot matter (with the masks on it would: a
+    # shared block's slice takes a's three applications and b's three in that order; tests/test_gpu_lifetimes.py fixes the order)
+    from gpu_util import bits_equal
+    _no_dropout(m)
+    m.zero_grad(set_to_none=True)
+    a, b = m(x), m(x)
+    (a.sum() + b.sum()).backward()
+    assert not any(p.busy for lst in eng.programs.values() for p in lst)
+    m2 = build("512").train()
+    _no_dropout(m2)
+    for _ in range(2):
+        m2(x).sum().backward()
+    for (k, p), q in zip(m.named_parameters(), m2.parameters()):
+        assert p.grad is not None and q.grad is not None, k
+        bits_equal(p.grad, q.grad, k)
 
 
 def test_second_backward_raises():
