@@ -73,7 +73,7 @@ typedef struct MnasGradIn {
     const float* coef;    /* float[5][C] */
 } MnasGradIn;
 
-int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, and + mnas_grad_sqnorm / mnas_*_step_ex, and + mnas_head_cross_entropy_soft / mnas_img_mix, and + mnas_img_aug, and + mnas_head_cross_entropy_kd, and + mnas_*_step_seg, all additive: no layout or opcode changed, so still 8; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
+int mnas_version(void);                 /* ABI version: 8 (+ the image batch transform and the photometric image ops, and + mnas_grad_sqnorm / mnas_*_step_ex, and + mnas_head_cross_entropy_soft / mnas_img_mix, and + mnas_img_aug, and + mnas_head_cross_entropy_kd, and + mnas_*_step_seg, and + mnas_img_erase / mnas_philox4x32_10, all additive: no layout or opcode changed, so still 8; round 6: + mnas_probe_copy4 / _read; 7 = round 5: + mnas_se_fc_*; 6 = struct layouts changed in rounds 2, 3, twice in round 4 -- 4 = the tiled-block forms,
                                          * 5 = squeeze-excite on load: MnasConvGemm.gate, MnasPwBwd.seg_px -- and in round 5: 6 = the opt-in
                                          * forms that lost their A/B are gone (MnasPwBwd.dy_out / red4, MnasDwBwd.src_* / g_gate / g_bias,
                                          * mnas_dw_exp_*, mnas_irb_*, mnas_gram*, mnas_se_bn_assemble); their opcode numbers stay retired) */
@@ -1142,6 +1142,59 @@ int64_t mnas_img_aug_workspace_bytes(int n, int H, int W, int max_ops, int need_
  * and write nothing for one they refuse (a chain longer than max_ops, or a statistics op at a stage whose bit is clear, included). */
 int mnas_img_aug(const MnasImgAug* items, int n, int H, int W, int max_ops, int stats_stages, int fill_rgb, const void* in,
                  void* out, void* workspace, void* stream);
+
+/* ---- device random numbers (csrc/mnas_rng.h; additive within ABI 8): Philox4x32-10, a counter-based generator -- the four output
+ * words are a pure function of a 128-bit counter c = {c0, c1, c2, c3} and a 64-bit key {k0, k1}, so a CPU test can state every
+ * byte a kernel derives from them.  Ten rounds; each round computes, in 32-bit words with 32 x 32 -> 64-bit products,
+ *     c' = {hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)},   M0 = 0xD2511F53, M1 = 0xCD9E8D57,
+ * and then moves the key on: k0 += 0x9E3779B9, k1 += 0xBB67AE85.  Known answers (counter, key -> output):
+ *     00000000 00000000 00000000 00000000, 00000000 00000000 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *     ffffffff ffffffff ffffffff ffffffff, ffffffff ffffffff -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *     243f6a88 85a308d3 13198a2e 03707344, a4093822 299f31d0 -> d16cfe09 94fdcceb 5001e420 24126ea1
+ * The host entry below runs the header's function on the CPU (no GPU needed): ctr[4], key[2] in, out[4]. */
+void mnas_philox4x32_10(const uint32_t* ctr, const uint32_t* key, uint32_t* out);
+
+/* ---- Random Erasing on uint8 images (csrc/mnas_imge.hip; additive within ABI 8, outside the launch lists): Zhong et al. 2017 on
+ * the (n, 3, H, W) uint8 NCHW batch the stem reads, IN PLACE.  One descriptor per image per launch; the box is rows [y0, y1) x
+ * columns [x0, x1) of every plane:
+ *     NONE   the image is not touched
+ *     CONST  byte fill[c] in plane c
+ *     NOISE  pixel (n, c, y, x), with k the launch's box position:
+ *                r    = philox4x32_10(counter {x >> 3, y, 3 n + c, k}, key {seed & 0xffffffff, seed >> 32})
+ *                word = r[(x & 7) >> 1];   half = (x & 1) ? word >> 16 : word & 0xffff
+ *                byte = table[c * 4096 + (half & 4095)]
+ *            one Philox call serves the eight pixels x >> 3 of a row.  y and x are coordinates in the IMAGE, not in the box: a pixel
+ *            gets the same byte whichever box covers it at position k, and different k (or seeds) give independent streams.
+ * table: 3 x 4096 bytes on the device, built by the caller -- erasing.erase_table carries N(mean_c, std_c) noise to byte space
+ * through a 12-bit quantile table, T_c[i] = clamp(floor(255 (mean_c + std_c Phi^-1((i + 0.5) / 4096)) + 0.5), 0, 255); the kernel
+ * evaluates no transcendental, so the bytes are exact.  A byte cannot hold the noise's tails: entries past 0 or 255 clamp.
+ * Several boxes per image are several launches, one per box position k, in order (the scheme mnas_img_aug uses for op positions):
+ * where boxes overlap the later position wins. */
+#define MNAS_IMGE_NONE  0              /* not touched */
+#define MNAS_IMGE_CONST 1              /* fill[c] in plane c */
+#define MNAS_IMGE_NOISE 2              /* table[c][12 bits of Philox] per pixel */
+typedef struct MnasImgErase {          /* 32 bytes */
+    int32_t mode;                      /* MNAS_IMGE_* */
+    int32_t y0, x0, y1, x1;            /* 0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W; empty boxes are allowed */
+    uint8_t fill[3];                   /* read by CONST */
+    uint8_t pad;                       /* 0 */
+    int32_t reserved[2];               /* 0 */
+} MnasImgErase;
+/* Host-side validation, no launch: every item's mode known, box ordered and inside the image, pad and reserved 0 -- every field of
+ * every item, whatever its mode (fill takes any value); n in [0, 65535], H, W in [1, MNAS_IMGX_MAX_OUT].  0 or MNAS_EINVAL.
+ * items_host: HOST. */
+int mnas_img_erase_check(const MnasImgErase* items_host, int n, int H, int W);
+/* items (n descriptors), x (n*3*H*W bytes, contiguous, ANY alignment) and table (3 * 4096 bytes, or null when no item is NOISE):
+ * device.  One launch, in place on x: only the bytes inside the boxes are written and no byte of x is read.  grid (3 * bands, n)
+ * with bands = ceil(H / 64): one workgroup = one plane of one image x one band of the BOX's rows (ceil(box rows / bands) each);
+ * the workgroups of a NONE image, of an empty box and of bands past the box's last row return after reading the descriptor, so
+ * the work is the erased area's, not the batch's.  A workgroup of a NOISE image first copies its plane's 4096 table bytes into LDS.
+ * One lane = one 16-byte-aligned group of a box row: a group wholly inside the row goes out as one 16-byte store, a row's head and
+ * tail as aligned 4-byte and single-byte stores; x0, W and the base address are arbitrary.  Plain vector stores, no atomics.
+ * position: k above.  Run the host check first; the kernel re-checks each descriptor it reads and writes nothing for one it
+ * refuses (a NOISE item with a null table included). */
+int mnas_img_erase(const MnasImgErase* items, int n, int H, int W, void* x, const void* table, uint64_t seed, uint32_t position,
+                   void* stream);
 
 #ifdef __cplusplus
 }

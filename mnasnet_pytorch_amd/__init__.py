@@ -15,9 +15,11 @@ from .metrics import DeviceMeters, MultiLabelMeters, accuracy  # noqa: F401
 from .losses import DistillCrossEntropyLoss, DistillTarget, HardDice, MixCrossEntropyLoss, MultiClassBCELoss  # noqa: F401
 from .mixing import DeviceMix, MixedTarget  # noqa: F401
 from .augment import DeviceRandAugment, aug_apply  # noqa: F401
+from .erasing import DeviceRandomErasing, erase_table  # noqa: F401
 
 __all__ = ["Mnasnet", "ConvBlock", "SepConv", "MBConv_block", "MBConv", "load_model", "FineTuneModelPool",
            "ClusterRandomSampler", "DistributedClusterSampler", "DeviceTransform", "ImageBatch", "collate_decoded",
            "DevicePipeline", "DeviceColorJitter", "DeviceRandomGrayscale", "DeviceMeters", "accuracy",
            "MultiLabelMeters", "MultiClassBCELoss", "HardDice", "MixCrossEntropyLoss", "DeviceMix", "MixedTarget",
-           "DeviceRandAugment", "aug_apply", "DistillCrossEntropyLoss", "DistillTarget"]
+           "DeviceRandAugment", "aug_apply", "DistillCrossEntropyLoss", "DistillTarget",
+           "DeviceRandomErasing", "erase_table"]

@@ -136,6 +136,15 @@ class MnasImgAug(C.Structure):
 IMGA_MAX_OPS = 4
 
 
+class MnasImgErase(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("y0", C.c_int32), ("x0", C.c_int32), ("y1", C.c_int32), ("x1", C.c_int32),
+                ("fill", C.c_uint8 * 3), ("pad", C.c_uint8), ("reserved", C.c_int32 * 2)]
+
+
+IMGE_NONE, IMGE_CONST, IMGE_NOISE = 0, 1, 2          # MNAS_IMGE_*
+IMGE_TABLE = 4096                                     # table entries per channel
+
+
 class MnasOp(C.Structure):
     _fields_ = [("opcode", C.c_int32), ("i", C.c_int32 * 15), ("d", C.c_double * 4), ("p", c_void_p * 16)]
 
@@ -473,6 +482,9 @@ SYMBOLS = {
     "mnas_img_aug_check": (c_int, [C.POINTER(MnasImgAug), c_int, c_int, c_int]),
     "mnas_img_aug_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "mnas_img_aug": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mnas_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "mnas_img_erase_check": (c_int, [C.POINTER(MnasImgErase), c_int, c_int, c_int]),
+    "mnas_img_erase": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, C.c_uint64, C.c_uint32, c_void_p]),
 }
 
 _lib = None
