@@ -669,6 +669,58 @@ int mnas_mlabel_metrics(const void* logits, const void* target, int N, int C, co
 int mnas_mlabel_hard_dice(const void* logits, const void* target, int N, int C, float threshold_logit, int deduct_intersection,
                           void* scratch, void* out, void* stream);
 
+/* ---- multi-label loss (csrc/mnas_mlabel.hip; build-defined -- the reference has plain BCE only): per-element asymmetric focal
+ * loss (Ridnik et al., "Asymmetric Loss for Multi-Label Classification"; gamma+ = gamma- = gamma, m = 0 is the sigmoid focal loss
+ * without its alpha term), pos_weight, binary label smoothing and mixed label rows, in mnas_mlabel_bce's two launches.
+ * logits z, labels Y, weights w: fp32 [N][C] (w NULL: 1); pos_weight p: fp32 [C] (NULL: 1); partner: int64 [N] and lam: fp32 [N],
+ * both or neither.
+ *
+ * Arithmetic rule (fp32; sp(x) = max(x,0) + log1p(exp(-|x|)); sigma = the piecewise sigmoid above, 1 - sigma its other branch --
+ * exp(-|z|)/(1+exp(-|z|)) for z >= 0, 1/(1+exp(-|z|)) for z < 0 -- never a subtraction):
+ *   mixed rows   y = fma(lam_n, Y[n][c], (1 - lam_n) * Y[partner_n][c])            (no partner: y = Y[n][c])
+ *   smoothing    t = fma(1 - eps, y, eps/2)                                         (eps = 0: t = y, no operation)
+ *   L+ = sp(-z)  F+ = exp(-(gamma+ * sp(z)))                                        (gamma+ = 0: F+ = 1, no exp)
+ *   sigma_m = sigma - m;   m = 0:  F- = exp(-(gamma- * sp(-z))), L- = sp(z)         (log sigma = -sp(-z): no cancellation)
+ *                          m > 0, sigma_m > 0:  F- = exp(gamma- * log(sigma_m)), L- = -log1p(-sigma_m)
+ *                          m > 0, sigma_m <= 0: L- = 0, F- = 0 (gamma- = 0: 1): the element's negative part and its gradient are 0
+ *                          (gamma- = 0: F- = 1, no exp)
+ *   e   = fma(1 - t, F- * L-, (p t) * (F+ * L+));   the row sum adds fma(e, w, .)
+ *   loss = sum(e w) / D, D = N*C (reduction MNAS_MLABEL_MEAN) or N (MNAS_MLABEL_ROWS: summed over the classes, averaged over the
+ *          rows); row sums in fp32 in k_mlabel_row's fixed order, the N row sums added in double, one rounding to fp32
+ *   dlogits = (w * fma(1 - t, dneg, (p t) * dpos)) * (float)(1/D)     -- the focusing weights are differentiated:
+ *     dpos = -(F+ * fma(gamma+ * sigma, L+, 1 - sigma))                             (gamma+ = 0: -(1 - sigma))
+ *     dneg = F- * fma(gamma- * (1 - sigma), sp(z), sigma)                           (m = 0; gamma- = 0: sigma) -- no division by 1 - sigma
+ *     dneg = (sigma (1 - sigma)) * fma(gamma- * exp((gamma- - 1) * log(sigma_m)), L-, F- / (1 - sigma_m))    (m > 0, sigma > m strictly)
+ *   Powers are expf / logf / log1pf only, never powf.  Each multiply that feeds an add is the fma written above; every other operation
+ *   rounds on its own.
+ *   With gamma+ = gamma- = 0, m = 0 and no pos_weight the element is mnas_mlabel_bce's own (e = max(z,0) - z*t + log1p(exp(-|z|)),
+ *   gradient w (sigma - t) / D) on the mixed, smoothed t; with eps = 0, no partner and MNAS_MLABEL_MEAN besides, the call is
+ *   mnas_mlabel_bce(focal = 0) bit for bit: loss, dlogits, scratch and meters block.
+ *   Meters: a class of row n is true iff the RAW label (before mixing and smoothing) of the row's dominant image is exactly 1 --
+ *   row n when lam_n >= 0.5, row partner_n otherwise; prediction rules, F1, HardDice and the block update as above.
+ *   Bad rows: partner_n outside [0, N) or lam_n not in [0, 1] (NaN included).  Such a row reads no partner row (nothing is read
+ *   out of bounds); its labels are NaN, so its row loss, the batch loss and its gradient row are NaN (nonfinite_steps counts the
+ *   step; an optimizer's skip_nonfinite sees the gradient); the meters count it against its own labels.  Other rows' gradients
+ *   do not change.
+ *   Refused on the host with MNAS_EINVAL before any launch, nothing written: a NULL logits / labels / cfg / scratch / loss, N or
+ *   C < 1, a scratch not 16-byte aligned, partner without lam or lam without partner, gamma+ or gamma- outside {0} u [1, 16],
+ *   m outside [0, 0.5], eps outside [0, 1), any of them NaN, an unknown reduction, a non-zero reserved field, a negative meter weight.
+ *   Scratch: mnas_mlabel_scratch_bytes(N), the layout above (`scale` is not written).  dlogits NULL: forward only, the same loss
+ *   bits; meters NULL or not: the same loss and dlogits bits.  Two launches in every configuration: the gradient is final after
+ *   the row launch.  16-byte loads and stores when C % 4 == 0 and logits, labels, weights, pos_weight and dlogits are 16-byte
+ *   aligned, scalar ones otherwise. */
+#define MNAS_MLABEL_MEAN 0
+#define MNAS_MLABEL_ROWS 1
+typedef struct MnasMlabelLoss {
+    float gamma_pos, gamma_neg, margin, smoothing;
+    int reduction;                               /* MNAS_MLABEL_MEAN / MNAS_MLABEL_ROWS */
+    int reserved[3];                             /* 0 */
+} MnasMlabelLoss;
+int mnas_mlabel_loss(const void* logits, const void* labels, const void* partner /* int64[N] or NULL */,
+                     const void* lam /* fp32[N], NULL iff partner is NULL */, const void* weights, const void* pos_weight,
+                     int N, int C, const MnasMlabelLoss* cfg, void* scratch, void* loss, void* dlogits,
+                     MnasMultiLabelMeters* meters, int64_t n_loss, int64_t n_dice, int64_t n_f1, void* stream);
+
 /* ---- squeeze-and-excitation of the SE variant of MBConv_block (BASELINE config 4; build-defined -- the reference has no SE
  * block; csrc/mnas_se.hip, restated in oracle.se_apply).  a = the activated depthwise output (act-on-load of y2), u = the
  * excite logits fp32 [N][C] (mnas_pool_act -> mnas_head_linear_fwd x2 produce them).

@@ -12,8 +12,9 @@ from .sampler import ClusterRandomSampler, DistributedClusterSampler  # noqa: F4
 from .transforms import (DeviceColorJitter, DevicePipeline, DeviceRandomGrayscale, DeviceTransform, ImageBatch,  # noqa: F401
                          collate_decoded)
 from .metrics import DeviceMeters, MultiLabelMeters, accuracy  # noqa: F401
-from .losses import DistillCrossEntropyLoss, DistillTarget, HardDice, MixCrossEntropyLoss, MultiClassBCELoss  # noqa: F401
-from .mixing import DeviceMix, MixedTarget  # noqa: F401
+from .losses import (DistillCrossEntropyLoss, DistillTarget, HardDice, MixCrossEntropyLoss, MultiClassBCELoss,  # noqa: F401
+                     MultiLabelLoss)
+from .mixing import DeviceMix, MixedLabels, MixedTarget  # noqa: F401
 from .augment import DeviceRandAugment, aug_apply  # noqa: F401
 from .erasing import DeviceRandomErasing, erase_table  # noqa: F401
 
@@ -22,4 +23,4 @@ __all__ = ["Mnasnet", "ConvBlock", "SepConv", "MBConv_block", "MBConv", "load_mo
            "DevicePipeline", "DeviceColorJitter", "DeviceRandomGrayscale", "DeviceMeters", "accuracy",
            "MultiLabelMeters", "MultiClassBCELoss", "HardDice", "MixCrossEntropyLoss", "DeviceMix", "MixedTarget",
            "DeviceRandAugment", "aug_apply", "DistillCrossEntropyLoss", "DistillTarget",
-           "DeviceRandomErasing", "erase_table"]
+           "DeviceRandomErasing", "erase_table", "MultiLabelLoss", "MixedLabels"]

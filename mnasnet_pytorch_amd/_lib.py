@@ -315,7 +315,16 @@ class MnasMultiLabelMeters(C.Structure):
                                         "last_dice_sum", "last_f1_sum")]
 
 
-GRADNORM_MAX_PARTS = 1024                                       # MNAS_GRADNORM_MAX_PARTS
+MLABEL_MEAN, MLABEL_ROWS = 0, 1                                 # MNAS_MLABEL_MEAN / MNAS_MLABEL_ROWS
+
+
+class MnasMlabelLoss(C.Structure):
+    """include/mnas.h: HOST struct of mnas_mlabel_loss's settings (32 bytes)"""
+    _fields_ = [("gamma_pos", c_float), ("gamma_neg", c_float), ("margin", c_float), ("smoothing", c_float),
+                ("reduction", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+GRADNORM_MAX_PARTS = 1024                                    # MNAS_GRADNORM_MAX_PARTS
 
 
 class MnasGradStats(C.Structure):
@@ -378,6 +387,8 @@ SYMBOLS = {
     "mnas_mlabel_scratch_bytes": (c_int64, [c_int]),
     "mnas_mlabel_bce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "mnas_mlabel_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, C.POINTER(MnasMlabelLoss),
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "mnas_mlabel_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
                                     c_void_p]),
     "mnas_mlabel_hard_dice": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),

@@ -7,7 +7,8 @@ Two entry points share the same kernels:
   ``model(x)`` / ``criterion(out, target)`` / ``loss.backward()`` of train.py:434-439 work unchanged;
 * :meth:`NativeHead.loss_and_grad` -- logits, cross-entropy, and the whole backward of the head in 8 launches without
   autograd; ``Trainer.step`` takes this path when the criterion is a plain ``nn.CrossEntropyLoss`` or this package's
-  ``MultiClassBCELoss`` (the multi-label branch: :meth:`NativeHead.bce`, csrc/mnas_mlabel.hip), ``MixCrossEntropyLoss``
+  ``MultiClassBCELoss`` (the multi-label branch: :meth:`NativeHead.bce`, csrc/mnas_mlabel.hip), ``MultiLabelLoss`` (that branch's
+  asymmetric focal loss, pos_weight, smoothing and mixed label rows: :meth:`NativeHead.mlabel`), ``MixCrossEntropyLoss``
   (:meth:`NativeHead.cross_entropy_soft`) or ``DistillCrossEntropyLoss`` (class weights and a teacher's logits:
   :meth:`NativeHead.cross_entropy_kd`).
 
@@ -282,6 +283,17 @@ class NativeHead:
                                criterion.balance_param, need_grad=need_grad, meters=meters,
                                meter_weights=(N, N, N if f1_n is None else f1_n))
 
+    def mlabel(self, logits, target, criterion, weights=None, need_grad=True, meters=None, f1_n=None):
+        """-> (loss 0-d tensor, dlogits or None) of a losses.MultiLabelLoss ``criterion`` (mnas_mlabel_loss: asymmetric focusing,
+        pos_weight, smoothing, two launches).  target: an (N, C) label matrix (converted with .float()) or a mixing.MixedLabels,
+        whose rows are mixed on load.  ``meters`` (a metrics.MultiLabelMeters): the same launches also update its block with the
+        weights N, N and ``f1_n`` (default N), every row counted against its dominant image's labels."""
+        from .losses import multilabel_loss
+        N = logits.shape[0]
+        labels, partner, lam, weights, pw = criterion.prepare(logits, target, weights)
+        return multilabel_loss(logits, labels, partner, lam, weights, pw, *criterion.settings(), need_grad=need_grad, meters=meters,
+                               meter_weights=(N, N, N if f1_n is None else f1_n))
+
     def check_targets(self):
         """Host check of the device-side "target out of range" flag that mnas_head_cross_entropy raises (the loss is NaN from
         that step on; ATen asserts on the device instead).  Synchronises: call it next to a ``loss.item()``, not per step.
@@ -300,13 +312,15 @@ class NativeHead:
         """Forward, loss and full backward of the head without autograd.  Parameter gradients are ACCUMULATED into
         ``p.grad`` (which must exist: Trainer points them into its flat gradient buffer).  -> (logits, loss, dx).
         ``criterion``: None / an nn.CrossEntropyLoss -> cross-entropy with ``ignore_index``; a losses.MultiClassBCELoss -> :meth:`bce`;
-        a losses.MixCrossEntropyLoss -> :meth:`cross_entropy_soft` (``target``: a class vector or a mixing.MixedTarget); a
+        a losses.MultiLabelLoss -> :meth:`mlabel` (``target``: a label matrix or a mixing.MixedLabels); a losses.MixCrossEntropyLoss -> :meth:`cross_entropy_soft` (``target``: a class vector or a mixing.MixedTarget); a
         losses.DistillCrossEntropyLoss -> :meth:`cross_entropy_kd` (``target``: either of those, or a losses.DistillTarget)."""
-        from .losses import DistillCrossEntropyLoss, MixCrossEntropyLoss, MultiClassBCELoss
+        from .losses import DistillCrossEntropyLoss, MixCrossEntropyLoss, MultiClassBCELoss, MultiLabelLoss
         seeds = self.next_seeds()
         us, logits = self.forward_layers(x, seeds)
         if type(criterion) is MultiClassBCELoss:             # the class itself, as Trainer routes it
             loss, dl = self.bce(logits, target, criterion, meters=meters, f1_n=f1_n)
+        elif type(criterion) is MultiLabelLoss:
+            loss, dl = self.mlabel(logits, target, criterion, meters=meters, f1_n=f1_n)
         elif type(criterion) is MixCrossEntropyLoss:
             loss, dl = self.cross_entropy_soft(logits, target, criterion.label_smoothing, criterion.ignore_index, meters=meters)
         elif type(criterion) is DistillCrossEntropyLoss:

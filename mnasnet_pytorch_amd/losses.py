@@ -5,6 +5,9 @@ builds ``MultiClassBCELoss()`` and ``HardDice(threshold=0.5)`` when ``--multi_cl
 * :class:`MultiClassBCELoss` -- same constructor and ``forward(outputs, targets, weights=None)``.  BCE-with-logits, mean-reduced,
   optional element weights, optional focal transform of the MEAN (as the reference applies it).  Differentiable with respect to
   ``outputs``.  ``Trainer`` recognises this class and runs the whole step without autograd (head.NativeHead.bce).
+* :class:`MultiLabelLoss` -- not from the reference: that branch's current recipe in the same two launches -- per-element asymmetric
+  focal loss, ``pos_weight``, binary label smoothing, and label rows mixed on load from a ``mixing.MixedLabels`` (include/mnas.h
+  "multi-label loss"; head.NativeHead.mlabel).  ``Trainer`` recognises this class too; :func:`multilabel_loss` is the functional form.
 * :class:`HardDice` -- same constructor; returns a 0-d fp32 device tensor without a host sync.
 * :class:`MixCrossEntropyLoss` -- not from the reference: cross-entropy with label smoothing over class indices or over the two
   labels per row of a mixed batch (mixing.MixedTarget; csrc/mnas_head.hip, include/mnas.h "soft-target cross-entropy").  ``Trainer``
@@ -18,6 +21,7 @@ the fp32 sigmoid rounds onto the threshold), so the threshold must lie inside (0
 holds ``(1 - pt) ** (focus_param - 1)``).  No CPU path: tensors must live on the MI355X."""
 from __future__ import annotations
 
+import ctypes
 import math
 
 import torch
@@ -112,6 +116,151 @@ class MultiClassBCELoss(nn.Module):
     def forward(self, outputs, targets, weights=None):
         targets, weights = self.prepare(outputs, targets, weights)
         return _BCEFn.apply(outputs, targets, weights, bool(self.use_focal_weights), self.focus_param, self.balance_param)
+
+
+REDUCTIONS = {"mean": L.MLABEL_MEAN, "rows": L.MLABEL_ROWS}
+
+
+def check_multilabel_settings(gamma_pos, gamma_neg, margin, label_smoothing, reduction):
+    """the ranges mnas_mlabel_loss accepts (include/mnas.h "multi-label loss"), as ValueErrors"""
+    for name, g in (("gamma_pos", gamma_pos), ("gamma_neg", gamma_neg)):
+        g = float(g)
+        if not (g == 0.0 or 1.0 <= g <= 16.0):
+            raise ValueError("%s must be 0 or lie in [1, 16] (the gradient holds the focusing weight to the power gamma - 1), got %r"
+                             % (name, g))
+    if not 0.0 <= float(margin) <= 0.5:
+        raise ValueError("margin must lie in [0, 0.5], got %r" % (margin,))
+    if not 0.0 <= float(label_smoothing) < 1.0:
+        raise ValueError("label_smoothing must lie in [0, 1), got %r" % (label_smoothing,))
+    if reduction not in REDUCTIONS:
+        raise ValueError("reduction must be 'mean' (over N*C) or 'rows' (summed over the classes, averaged over the rows), got %r"
+                         % (reduction,))
+
+
+def split_labels(target):
+    """an (N, C) label matrix or a mixing.MixedLabels -> (labels, partner or None, lam or None)"""
+    from .mixing import MixedLabels
+    if isinstance(target, MixedLabels):
+        return target.labels, target.partner, target.lam
+    return target, None, None
+
+
+def multilabel_loss(logits, labels, partner=None, lam=None, weights=None, pos_weight=None, gamma_pos=0.0, gamma_neg=0.0, margin=0.0,
+                    label_smoothing=0.0, reduction="mean", need_grad=True, meters=None, meter_weights=None):
+    """mnas_mlabel_loss on (N, C) fp32 contiguous device tensors -> (loss 0-d tensor, dlogits or None): the asymmetric focal loss
+    with ``pos_weight`` (fp32 (C,)), binary label smoothing and, with ``partner`` (int64 (N,)) and ``lam`` (fp32 (N,)), label rows
+    mixed on load.  ``meters`` (a metrics.MultiLabelMeters) with ``meter_weights = (n_loss, n_dice, n_f1)``: the same launches also
+    move its block, every row counted against its dominant image's labels."""
+    _on_device("logits", logits)
+    if logits.dim() != 2:
+        raise ValueError("logits must be (N, C), got %s" % (tuple(logits.shape),))
+    N, Cn = logits.shape
+    dev = logits.device
+    if (partner is None) != (lam is None):
+        raise ValueError("partner and lam come together (a mixing.MixedLabels holds both)")
+    for name, t, dt, shape in (("logits", logits, torch.float32, (N, Cn)), ("labels", labels, torch.float32, (N, Cn)),
+                               ("partner", partner, torch.int64, (N,)), ("lam", lam, torch.float32, (N,)),
+                               ("weights", weights, torch.float32, (N, Cn)), ("pos_weight", pos_weight, torch.float32, (Cn,))):
+        if t is None:
+            continue
+        _on_device(name, t, dev)
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError("%s must be contiguous %s of shape %s, got %s %s" % (name, dt, shape, t.dtype, tuple(t.shape)))
+    check_multilabel_settings(gamma_pos, gamma_neg, margin, label_smoothing, reduction)
+    lib = L.load()
+    cfg = L.MnasMlabelLoss(float(gamma_pos), float(gamma_neg), float(margin), float(label_smoothing), REDUCTIONS[reduction])
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dl = torch.empty_like(logits) if need_grad else None
+    scratch = _scratch(lib, N, dev)
+    blk, (n_loss, n_dice, n_f1) = 0, (0, 0, 0)
+    if meters is not None:
+        blk = meters.kernel_args(dev)
+        n_loss, n_dice, n_f1 = (int(v) for v in meter_weights)
+    L.check(lib.mnas_mlabel_loss(logits.data_ptr(), labels.data_ptr(), L.ptr(partner), L.ptr(lam), L.ptr(weights), L.ptr(pos_weight),
+                                 N, Cn, ctypes.byref(cfg), scratch.data_ptr(), loss.data_ptr(), L.ptr(dl), blk, n_loss, n_dice, n_f1,
+                                 L.cur_stream()), "mlabel_loss")
+    return loss, dl
+
+
+class _MLFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, outputs, labels, partner, lam, weights, pos_weight, settings):
+        loss, dl = multilabel_loss(outputs.detach().float().contiguous(), labels, partner, lam, weights, pos_weight, *settings,
+                                   need_grad=ctx.needs_input_grad[0])
+        ctx.dl, ctx.dtype = dl, outputs.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return (ctx.dl * grad_output).to(ctx.dtype), None, None, None, None, None, None
+
+
+class MultiLabelLoss(nn.Module):
+    """The multi-label branch's current recipe in the BCE loss's two launches (not from the reference; include/mnas.h "multi-label
+    loss"): the asymmetric focal loss of Ridnik et al. -- per ELEMENT, the focusing weights differentiated --
+
+        e = w * ( pos_weight_c * t * (1 - s)^gamma_pos * -log(s)  +  (1 - t) * s_m^gamma_neg * -log(1 - s_m) ),
+        s = sigmoid(z),  s_m = max(s - margin, 0),  t = (1 - label_smoothing) * y + label_smoothing / 2
+
+    ``gamma_pos = gamma_neg = gamma, margin = 0`` is the sigmoid focal loss without its alpha term; everything 0 is
+    ``F.binary_cross_entropy_with_logits(weight=, pos_weight=)``.  ``reduction``: ``"mean"`` over N*C, or ``"rows"`` -- summed over
+    the classes, averaged over the rows.  ``forward(outputs, targets, weights=None)``: ``targets`` an ``(N, C)`` label matrix
+    (soft values allowed; integer matrices are converted with ``.float()``) or a ``mixing.MixedLabels``, whose rows are mixed on
+    load; ``weights`` (``(N, C)``) are dropped unless ``use_weight_mask`` is set, as for :class:`MultiClassBCELoss`.
+    ``pos_weight``: a registered buffer ``(C,)`` (it moves with ``.to()`` / ``.cuda()``) or None.  Differentiable with respect to
+    ``outputs`` only.  ``Trainer`` recognises this class and runs the whole step without autograd (head.NativeHead.mlabel).  A row
+    whose partner index or weight is out of range makes the loss and its gradient row NaN.  With a margin the negative part is
+    computed from the rounded sigmoid, ``-log1p(-(s - margin))``: it is capped at ``-log(margin)``, and a margin below 2**-24
+    (other than 0) would make it infinite where the sigmoid rounds to 1 -- use 0 or a real margin.  No CPU path."""
+
+    def __init__(self, gamma_pos: float = 0.0, gamma_neg: float = 0.0, margin: float = 0.0, pos_weight=None, label_smoothing: float = 0.0,
+                 use_weight_mask: bool = False, reduction: str = "mean"):
+        super().__init__()
+        check_multilabel_settings(gamma_pos, gamma_neg, margin, label_smoothing, reduction)
+        self.gamma_pos, self.gamma_neg, self.margin = float(gamma_pos), float(gamma_neg), float(margin)
+        self.label_smoothing, self.use_weight_mask, self.reduction = float(label_smoothing), bool(use_weight_mask), reduction
+        self.register_buffer("pos_weight", check_class_weight(pos_weight))
+
+    def settings(self):
+        return (self.gamma_pos, self.gamma_neg, self.margin, self.label_smoothing, self.reduction)
+
+    def prepare(self, outputs, targets, weights=None):
+        """shape and device checks -> (labels, partner or None, lam or None, weights or None, pos_weight or None), the tensors
+        fp32 / int64 contiguous on the outputs' device"""
+        from .mixing import MixedLabels
+        if not isinstance(outputs, torch.Tensor) or outputs.dim() != 2:
+            raise ValueError("outputs must be (N, C), got %s" % (tuple(getattr(outputs, "shape", ())),))
+        _on_device("outputs", outputs)
+        if isinstance(targets, MixedLabels):
+            targets.check_device(outputs.device)
+        labels, partner, lam = split_labels(targets)
+        if not isinstance(labels, torch.Tensor) or labels.shape != outputs.shape:
+            raise ValueError("targets must be an (N, C) = %s label matrix or a MixedLabels around one, got %s"
+                             % (tuple(outputs.shape), tuple(getattr(labels, "shape", ()))))
+        if weights is not None and weights.shape != outputs.shape:
+            raise ValueError("weights must be %s, got %s" % (tuple(outputs.shape), tuple(weights.shape)))
+        _on_device("targets", labels, outputs.device)
+        labels = labels.detach().float().contiguous()
+        if weights is not None and self.use_weight_mask:
+            _on_device("weights", weights, outputs.device)
+            weights = weights.detach().float().contiguous()
+        else:
+            weights = None
+        pw = self.pos_weight
+        if pw is not None:
+            if pw.numel() != outputs.shape[1]:
+                raise ValueError("pos_weight has %d entries, the outputs %d classes" % (pw.numel(), outputs.shape[1]))
+            _on_device("pos_weight", pw, outputs.device)
+        return labels, partner, lam, weights, pw
+
+    def forward(self, outputs, targets, weights=None):
+        labels, partner, lam, weights, pw = self.prepare(outputs, targets, weights)
+        return _MLFn.apply(outputs, labels, partner, lam, weights, pw, self.settings())
+
+    def extra_repr(self):
+        return "gamma_pos=%g, gamma_neg=%g, margin=%g, label_smoothing=%g, pos_weight=%s, reduction=%r" % (
+            self.gamma_pos, self.gamma_neg, self.margin, self.label_smoothing,
+            "None" if self.pos_weight is None else "(%d,)" % self.pos_weight.numel(), self.reduction)
 
 
 def soft_cross_entropy(logits, a, b=None, lam=None, label_smoothing=0.0, ignore_index=-100, rows=None, bad=None, need_grad=True,

@@ -1,7 +1,8 @@
 """Batch mixing -- Mixup (Zhang et al. 2018) and CutMix (Yun et al. 2019) -- on the uint8 batches the stem reads, on the GPU
 (csrc/mnas_imgm.hip; the arithmetic is stated in include/mnas.h "batch mixing").  The mixed batch stays ``(N, 3, H, W)`` uint8 on
 the device; the two labels and the weight of every row travel as a :class:`MixedTarget`, which ``losses.MixCrossEntropyLoss`` and
-``Trainer.step`` take in place of the class vector.
+``Trainer.step`` take in place of the class vector.  A multi-label batch travels as a :class:`MixedLabels` (the unmixed ``(N, C)``
+label matrix, the partner row indices and the weights), which ``losses.MultiLabelLoss`` takes in place of the label matrix.
 
     mix = DeviceMix(mixup_alpha=0.2, cutmix_alpha=1.0)
     trainer = Trainer(model, criterion=MixCrossEntropyLoss(label_smoothing=0.1))
@@ -69,6 +70,58 @@ class MixedTarget:
 
     def __repr__(self):
         return "MixedTarget(N=%d, device=%s)" % (len(self), self.device)
+
+
+class MixedLabels:
+    """The labels of a mixed multi-label batch: row n is ``lam[n]`` of the label row ``labels[n]`` and ``1 - lam[n]`` of
+    ``labels[partner[n]]``.  ``labels``: fp32 ``(N, C)`` (soft values allowed), the UNMIXED label matrix; ``partner``: int64
+    ``(N,)`` row indices; ``lam``: fp32 ``(N,)`` in [0, 1]; all three on one MI355X device.  ``losses.MultiLabelLoss`` forms the
+    mixed row on load (include/mnas.h "multi-label loss"); nothing is gathered or materialised."""
+
+    def __init__(self, labels: torch.Tensor, partner: torch.Tensor, lam: torch.Tensor):
+        for name, t, dt, nd in (("labels", labels, torch.float32, 2), ("partner", partner, torch.int64, 1), ("lam", lam, torch.float32, 1)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != nd:
+                raise TypeError("MixedLabels.%s must be a %d-D %s tensor" % (name, nd, dt))
+        if not (labels.shape[0] == partner.shape[0] == lam.shape[0]):
+            raise ValueError("labels, partner and lam must have the same number of rows, got %d, %d, %d"
+                             % (labels.shape[0], partner.numel(), lam.numel()))
+        if not (labels.device == partner.device == lam.device):
+            raise RuntimeError("labels, partner and lam must be on one device, got %s, %s, %s" % (labels.device, partner.device, lam.device))
+        self.labels, self.partner, self.lam = labels.detach().contiguous(), partner.contiguous(), lam.contiguous()
+
+    @property
+    def device(self):
+        return self.labels.device
+
+    @property
+    def shape(self):
+        return self.labels.shape
+
+    def __len__(self):
+        return self.labels.shape[0]
+
+    def to(self, device, non_blocking: bool = False) -> "MixedLabels":
+        return MixedLabels(*(t.to(device, non_blocking=non_blocking) for t in (self.labels, self.partner, self.lam)))
+
+    def check_device(self, device):
+        """the kernels take raw device pointers: everything on ``device``, an MI355X"""
+        if self.device.type != "cuda":
+            raise RuntimeError("a MixedLabels must be on the MI355X (no CPU path)")
+        if self.device != torch.device(device):
+            raise RuntimeError("the MixedLabels is on %s, the logits on %s (the kernels take raw device pointers)" % (self.device, device))
+
+    def dominant(self) -> torch.Tensor:
+        """``(N, C)``: the label row of the image that carries the larger weight, row n when ``lam >= 0.5``: what the multi-label
+        meters count a row against"""
+        return torch.where((self.lam >= 0.5).unsqueeze(1), self.labels, self.labels.index_select(0, self.partner))
+
+    def dense(self) -> torch.Tensor:
+        """``(N, C)``: the materialised ``lam Y + (1 - lam) Y[partner]``, for a criterion that takes a soft label matrix"""
+        lam = self.lam.unsqueeze(1)
+        return lam * self.labels + (1.0 - lam) * self.labels.index_select(0, self.partner)
+
+    def __repr__(self):
+        return "MixedLabels(N=%d, C=%d, device=%s)" % (len(self), self.labels.shape[1], self.device)
 
 
 def cutmix_box(h: int, w: int, lam: float, cy: int, cx: int):
@@ -154,14 +207,17 @@ class DeviceMix:
     def apply(x: torch.Tensor, target: torch.Tensor, draws):
         """Run explicit draws (:meth:`describe`'s records) -> ``(mixed uint8 batch, MixedTarget)``.  ``x``: contiguous ``(N, 3, H, W)``
         uint8 on an MI355X, left as it is (the pass is out of place); ``target``: int64 ``(N,)`` on the same device.  Checked by
-        ``mnas_img_mix_check``; descriptors, partner indices and weights go up in one pinned non-blocking copy."""
+        ``mnas_img_mix_check``; descriptors, partner indices and weights go up in one pinned non-blocking copy.  A floating
+        ``(N, C)`` label matrix as ``target`` (the multi-label branch) -> ``(mixed uint8 batch, MixedLabels(target, partner
+        indices, weights))``: the same bytes from the same draws, no gather and no launch more."""
         if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
             raise RuntimeError("DeviceMix runs on the MI355X only (no CPU path): x must be a CUDA tensor")
         if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
             raise ValueError("x must be a contiguous (N, 3, H, W) uint8 batch, got %s %s" % (tuple(x.shape), x.dtype))
         n, _, h, w = x.shape
-        if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or target.shape != (n,):
-            raise ValueError("target must be int64 of shape (N,)")
+        matrix = isinstance(target, torch.Tensor) and target.is_floating_point() and target.dim() == 2 and target.shape[0] == n
+        if not matrix and (not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or target.shape != (n,)):
+            raise ValueError("target must be int64 of shape (N,), or a floating (N, C) label matrix")
         if target.device != x.device:
             raise RuntimeError("target is on %s, x on %s (the kernels take raw device pointers)" % (target.device, x.device))
         if len(draws) != n:
@@ -175,6 +231,8 @@ class DeviceMix:
         dev = x.device
         if n == 0:
             z = torch.empty(0, dtype=torch.int64, device=dev)
+            if matrix:
+                return out, MixedLabels(target.float(), z, torch.empty(0, dtype=torch.float32, device=dev))
             return out, MixedTarget(z, z.clone(), torch.empty(0, dtype=torch.float32, device=dev))
         # one host buffer: [n MnasImgMix (32 bytes each) | n int64 partner indices | n fp32 weights]
         host = torch.empty(44 * n, dtype=torch.uint8).pin_memory()
@@ -184,6 +242,8 @@ class DeviceMix:
         with torch.cuda.device(dev):
             buf = host.to(dev, non_blocking=True)
             L.check(lib.mnas_img_mix(buf.data_ptr(), n, h, w, x.data_ptr(), out.data_ptr(), L.cur_stream()), "mnas_img_mix")
+            if matrix:                   # the loss reads the partner's label row through the index: nothing is gathered here
+                return out, MixedLabels(target.float(), buf[32 * n:40 * n].view(torch.int64), buf[40 * n:].view(torch.float32))
             target = target.contiguous()
             partner = target.index_select(0, buf[32 * n:40 * n].view(torch.int64))
         return out, MixedTarget(target, partner, buf[40 * n:].view(torch.float32))

@@ -816,6 +816,12 @@ class Trainer:
         from .losses import MultiClassBCELoss
         return type(self.criterion) is MultiClassBCELoss
 
+    def _mlloss(self):
+        """the criterion is this package's MultiLabelLoss itself (the multi-label branch's asymmetric focal loss, pos_weight,
+        smoothing, mixed label rows); a subclass keeps the module path, as for the other criteria"""
+        from .losses import MultiLabelLoss
+        return type(self.criterion) is MultiLabelLoss
+
     def _mixce(self):
         """the criterion is this package's MixCrossEntropyLoss itself (label smoothing, mixed batches); a subclass keeps the module
         path, as for the other criteria"""
@@ -830,9 +836,15 @@ class Trainer:
 
     def _check_target(self, target):
         """a mixing.MixedTarget goes to a MixCrossEntropyLoss or a DistillCrossEntropyLoss (or a subclass of either) only, a
-        losses.DistillTarget to a DistillCrossEntropyLoss (or a subclass) only: refused before anything is launched"""
-        from .losses import DistillCrossEntropyLoss, DistillTarget, MixCrossEntropyLoss
-        from .mixing import MixedTarget
+        losses.DistillTarget to a DistillCrossEntropyLoss (or a subclass) only, a mixing.MixedLabels to a MultiLabelLoss (or a
+        subclass) only: refused before anything is launched"""
+        from .losses import DistillCrossEntropyLoss, DistillTarget, MixCrossEntropyLoss, MultiLabelLoss
+        from .mixing import MixedLabels, MixedTarget
+        if isinstance(target, MixedLabels):
+            if not isinstance(self.criterion, MultiLabelLoss):
+                raise TypeError("a MixedLabels (a label matrix, partner rows and a weight per row) needs criterion=MultiLabelLoss(...); "
+                                "%s takes no mixed label matrix" % type(self.criterion).__name__)
+            return
         if isinstance(target, DistillTarget):
             if not isinstance(self.criterion, DistillCrossEntropyLoss):
                 raise TypeError("a DistillTarget (labels and a teacher's logits) needs criterion=DistillCrossEntropyLoss(...); %s takes "
@@ -883,8 +895,10 @@ class Trainer:
     def _check_meters(self, meters):
         """the meters' kind against the criterion's, before anything is launched (the constructor, every forward_backward and
         validate call it: ``criterion`` and ``meters`` are plain attributes)"""
-        from .losses import DistillCrossEntropyLoss, MixCrossEntropyLoss, MultiClassBCELoss
+        from .losses import DistillCrossEntropyLoss, MixCrossEntropyLoss, MultiClassBCELoss, MultiLabelLoss
         from .metrics import MultiLabelMeters
+        if meters is not None and isinstance(self.criterion, MultiLabelLoss) and not isinstance(meters, MultiLabelMeters):
+            raise ValueError("a MultiLabelLoss step feeds MultiLabelMeters, not %s" % type(meters).__name__)
         if isinstance(meters, MultiLabelMeters) and isinstance(self.criterion, (nn.CrossEntropyLoss, MixCrossEntropyLoss,
                                                                                DistillCrossEntropyLoss)):
             raise ValueError("MultiLabelMeters count (N, C) multi-label targets; a cross-entropy criterion takes class indices "
@@ -927,9 +941,9 @@ class Trainer:
         m, c = self.model, self.criterion
         if not self.native_step:
             return None
-        if self._multilabel() or self._mixce() or self._distill():
-            pass                   # losses.MultiClassBCELoss / MixCrossEntropyLoss / DistillCrossEntropyLoss: every setting is
-                                   # covered (head.NativeHead.bce, .cross_entropy_soft, .cross_entropy_kd)
+        if self._multilabel() or self._mlloss() or self._mixce() or self._distill():
+            pass                   # losses.MultiClassBCELoss / MultiLabelLoss / MixCrossEntropyLoss / DistillCrossEntropyLoss: every
+                                   # setting is covered (head.NativeHead.bce, .mlabel, .cross_entropy_soft, .cross_entropy_kd)
         elif type(c) is not nn.CrossEntropyLoss:
             return None
         elif c.weight is not None or c.reduction != "mean" or getattr(c, "label_smoothing", 0.0) != 0.0:
@@ -955,8 +969,9 @@ class Trainer:
 
     def step(self, x: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """One iteration of train.py:427-440.  Returns the loss tensor (no host sync).  ``target``: what the criterion takes -- class
-        indices, an (N, C) label matrix (MultiClassBCELoss), a mixing.MixedTarget (MixCrossEntropyLoss, DistillCrossEntropyLoss) or a
-        losses.DistillTarget (DistillCrossEntropyLoss), on either path.  With ``teacher=`` given the teacher's eval forward runs
+        indices, an (N, C) label matrix (MultiClassBCELoss, MultiLabelLoss), a mixing.MixedTarget (MixCrossEntropyLoss,
+        DistillCrossEntropyLoss), a mixing.MixedLabels (MultiLabelLoss) or a losses.DistillTarget (DistillCrossEntropyLoss), on either
+        path.  With ``teacher=`` given the teacher's eval forward runs
         first and the target is wrapped into a DistillTarget (:meth:`_teach`)."""
         self._check_target(target)                           # before zero_grad: a refused target leaves the step untouched
         if self.teacher is not None:
@@ -977,7 +992,7 @@ class Trainer:
         already there: two calls between ``optimizer.zero_grad()`` and ``optimizer.step()`` sum their gradients, which is what
         the world-2 test uses to emulate two data-parallel ranks in one process).  Fires the engine's stage-done callback."""
         from .losses import DistillTarget
-        from .mixing import MixedTarget
+        from .mixing import MixedLabels, MixedTarget
         self._check_meters(self.meters)                      # before any launch, on either path
         self._check_target(target)
         head = self._native_head()
@@ -988,7 +1003,7 @@ class Trainer:
             if hasattr(self.model, "_sync_input_norm"):
                 self.model._sync_input_norm()
             eng.check_input(x)                               # same checks as Engine.forward: the launch lists take raw pointers
-            if not isinstance(target, (torch.Tensor, MixedTarget, DistillTarget)) or target.device != x.device:
+            if not isinstance(target, (torch.Tensor, MixedTarget, MixedLabels, DistillTarget)) or target.device != x.device:
                 raise RuntimeError("target must be a tensor on the input's device (%s)" % (x.device,))
             u8 = x.dtype == torch.uint8 and eng._in_norm is not None
             x = x.contiguous() if u8 else x.float().contiguous()
@@ -1000,7 +1015,8 @@ class Trainer:
             head.calls = self.optimizer.step_count           # dropout masks follow the CHECKPOINTED step count: a resumed run does
                                                              # not replay the masks of the first steps
             # with meters: the loss kernels also rank every row's target and move the meters block -- no launch more
-            if self._multilabel():
+            if self._multilabel() or self._mlloss():
+                # (a MultiLabelLoss: also a MixedLabels, counted against each row's dominant image)
                 # train.py:429 target.float(); the meters' weights are the reference's: input.size(0) for the loss and Dice,
                 # input.size(1) for F1 (train.py:447, 454, 463)
                 self.last_logits, loss, df = head.loss_and_grad(f.view(f.size(0), -1), target, meters=self._ml_meters(),
@@ -1018,6 +1034,8 @@ class Trainer:
             loss.backward()
             if isinstance(target, DistillTarget):
                 target = target.target                       # the meters count the labels
+            if isinstance(target, MixedLabels):
+                target = target.dominant()                   # the meters count the labels of the image with the larger weight
             if self._ml_meters() is not None:
                 if self._label_matrix(out, target):
                     self.meters.update(out.detach(), target, loss.detach(), f1_n=x.shape[1])
@@ -1050,7 +1068,8 @@ class Trainer:
         transforms.DevicePipeline / DeviceTransform over an ImageBatch), the engine's eval-mode forward with the fused pool, the
         native head without dropout, and the cross-entropy kernels that also move ``meters`` (default: a fresh DeviceMeters with
         top-1 / top-5).  With this package's MultiClassBCELoss as the criterion it is the multi-label pass (train.py:575-587): (N, C)
-        targets, the BCE kernels, and a MultiLabelMeters (loss, HardDice(0.5), macro-F1; the default is a fresh one).  With this package's
+        targets, the BCE kernels, and a MultiLabelMeters (loss, HardDice(0.5), macro-F1; the default is a fresh one); with its
+        MultiLabelLoss the same pass with that loss, on plain label matrices.  With this package's
         MixCrossEntropyLoss it is the single-label pass with the smoothed loss, on plain int64 targets; with its DistillCrossEntropyLoss
         the hard term alone (class weights and smoothing applied; there is no teacher in validation).  Any input shape works: the engine keeps one eval program per shape.  A model or criterion the native head
         does not cover runs as ``model(x)`` / ``criterion`` / ``meters.update``.  Distributed trainers broadcast rank 0's
@@ -1058,9 +1077,9 @@ class Trainer:
         train/eval flags are restored on the way out, also when a batch raises.  Returns ``meters.read()``.  The same pass under the
         EMA weights: :meth:`validate_ema`."""
         from .metrics import DeviceMeters, MultiLabelMeters
-        multilabel = self._multilabel()
+        multilabel, mlloss = self._multilabel(), self._mlloss()
         if meters is None:
-            meters = MultiLabelMeters(self.device) if multilabel else DeviceMeters((1, 5), self.device)
+            meters = MultiLabelMeters(self.device) if multilabel or mlloss else DeviceMeters((1, 5), self.device)
         self._check_meters(meters)
         model = self.model
         modes = [(mod, mod.training) for mod in model.modules()]
@@ -1086,6 +1105,8 @@ class Trainer:
                         _, logits = head.forward_layers(f.view(f.size(0), -1), [0] * len(head.layers))   # eval: the seeds are unused
                         if multilabel:                                     # train.py:575-587: weights N, N and input.size(1)
                             head.bce(logits, target, self.criterion, need_grad=False, meters=meters, f1_n=x.shape[1])
+                        elif mlloss:                                       # the same pass with this loss, on plain label matrices
+                            head.mlabel(logits, target, self.criterion, need_grad=False, meters=meters, f1_n=x.shape[1])
                         elif self._mixce():                                # the smoothed loss on plain class indices
                             head.cross_entropy_soft(logits, target, self.criterion.label_smoothing, self.criterion.ignore_index,
                                                     need_grad=False, meters=meters)
